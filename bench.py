@@ -166,9 +166,13 @@ class ApiStep:
         the workspace's second stream, not yet on the current one (see __call__)."""
         R = self.R
         if self.one_call:
-            return R.forward_backward_views(self.views, *self.params, None, self.dL, workspace=self.ws, join=join, **kw)[4]
+            r = R.forward_backward_views(self.views, *self.params, None, self.dL, workspace=self.ws, join=join, **kw)
+            self.last = (r[0], r[1], r[2], r[4])
+            return r[4]
         color, inv, radii, st = R.forward_views(self.views, *self.params, None, workspace=self.ws)
-        return R.backward_views(st, *self.params, None, self.dL, workspace=self.ws, **kw)
+        g = R.backward_views(st, *self.params, None, self.dL, workspace=self.ws, **kw)
+        self.last = (color, inv, radii, g)      # what this call handed its caller (workspace tensors: the next call overwrites them)
+        return g
 
     def autotune(self):
         """The forward's fill configuration for THIS step on THIS box: Workspace.tune, the library's own tuner (what a training loop
@@ -198,6 +202,7 @@ class ApiStep:
 
     cands = None        # tuner candidates (None: the library's default list)
     tuned = None
+    last = None         # (color, invdepth, radii, gradients dict) of the last fwd_bwd
     wire_us = 0.0       # rank_step_8gpu only: a one-wavefront idle kernel of this length in front of the collective stands in for
                         # the xGMI hop a communicator of ONE rank does not make (sks_prof_spin)
     no_collective = False   # rank_step_8gpu only: the step without its exchange (forward + backward into the shard)
@@ -261,6 +266,39 @@ def timed(fn, steps, warmup, sync):
         out = fn()
     sync()
     return time.perf_counter() - t0, out
+
+
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 1 << 22          # an output of more elements is written as this many of them: a fixed, seeded sample (sorted indices)
+
+
+def dump_outputs(torch, dirpath, step, out):
+    """--dump-outputs: what the timed step computed in its last call -- the forward's image, inverse depth and radii and the
+    backward's gradients of this process's views, and the step's result (`out`: the mean of the joint gradients over all views) --
+    as DIR/<name>.npy, float32.  Call right behind the timed region, before anything launches on the step's workspace again.
+    Returns {name: "full" | "sample of N of M"} for the result line."""
+    import numpy as np
+    arrays = {}
+    if step.last is not None:
+        color, inv, radii, g = step.last
+        arrays.update(color=color, invdepth=inv, radii=radii)
+        arrays.update({"dL_d" + k: v for k, v in g.items() if v is not None})
+    arrays["dL_dmeans3D_mean"] = out
+    os.makedirs(dirpath, exist_ok=True)
+    written, total = {}, 0
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            a = flat[idx.to(flat.device)].float().cpu().numpy()
+            written[name] = f"sample of {DUMP_SAMPLE} of {flat.numel()} (seed 0)"
+        else:
+            a = flat.float().cpu().numpy().reshape(tuple(t.shape))
+            written[name] = "full"
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, f"--dump-outputs: more than {DUMP_MAX_BYTES} bytes"
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return written
 
 
 def prof_stride(steps):
@@ -417,7 +455,9 @@ def run_single(args, torch, dev, wl):
     prof = not args.no_prof
     stride = int(os.environ.get("SKS_PROF_EVERY", "0")) or prof_stride(args.steps)
 
-    def measure(one_call):
+    dumped = None
+
+    def measure(one_call, dump=False):
         """W warm-up + K timed steps of one form; the forward compositor launches of every n-th TIMED step carry a hipEvent pair
         (hipExtLaunchKernelGGL: stamped from the kernel's own dispatch, on the launch stream -- a bracketed step costs ~13 us of
         queue time, so the sample is 5 .. 25 of the K launches), topped up to ROOF_MIN_LAUNCHES behind the timed region by
@@ -431,6 +471,9 @@ def run_single(args, torch, dev, wl):
             _lib.prof_enable(True, every=stride, kinds=(0,))
             _lib.prof_read(0), _lib.prof_read(1)
         dt_, out_ = timed(st, args.steps, 0, sync)         # THE timed region: exactly K steps
+        if dump:
+            nonlocal dumped
+            dumped = dump_outputs(torch, args.dump_outputs, st, out_)
         pf_ = None
         if prof:
             have = _lib.prof_count(0)
@@ -466,7 +509,7 @@ def run_single(args, torch, dev, wl):
         torch.cuda.empty_cache()
         return pf_, cfg
 
-    step, dt, out, pf = measure(forms[0] == "one")
+    step, dt, out, pf = measure(forms[0] == "one", dump=bool(args.dump_outputs))
     step2 = dt2 = pf2 = None
     if len(forms) == 2:
         step2, dt2, out2, pf2 = measure(True)
@@ -503,6 +546,8 @@ def run_single(args, torch, dev, wl):
                    "form": "one call" if step.one_call else "two calls", "path": PATHS[step.one_call]},
     }
     res["config"]["autotuned"] = step.tuned
+    if dumped is not None:
+        res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     alg_bytes = 4.0 * H * W * (C + 1) * V
     if dt2 is not None:
         # the same step through sks_forward_backward, K steps timed the same way: an extra, not the headline (see PATHS)
@@ -1142,6 +1187,7 @@ def run_sharded(args, torch, dist, dev, wl, world, rank):
         _lib.prof_enable(True, every=stride, kinds=(0,))
         _lib.prof_read(0), _lib.prof_read(1)
     dt, out = timed(step, args.steps, 0, sync)      # THE timed region: exactly K steps
+    dumped = dump_outputs(torch, args.dump_outputs, step, out) if args.dump_outputs and rank == 0 else None
     dt = max_over_ranks(dt)
     pf = None
     if prof:
@@ -1208,6 +1254,8 @@ def run_sharded(args, torch, dist, dev, wl, world, rank):
     }
     if one_call_extra:
         res["one_call_step"] = one_call_extra
+    if dumped is not None:
+        res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if pf and pf[1]:
         res["roofline"] = roofline_entry(4.0 * H * W * (C + 1) * len(local), pf, wl["name"], args.steps,
                                          traffic_scale=len(local) / V)
@@ -1293,11 +1341,17 @@ def main():
     ap.add_argument("--no-dropin", action="store_true", help="skip the literal drop-in iteration extra (its single-view "
                     "launches would mix into per-kernel averages of a rocprofv3 run)")
     ap.add_argument("--no-extras", action="store_true", help="only the headline measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed step computed in its last call (rank 0: its views' image, "
+                         "inverse depth, radii and gradients, and the mean joint gradient) as DIR/<name>.npy, float32; an output "
+                         f"of more than {DUMP_SAMPLE} elements as a fixed, seeded sample of that many (at most 64 MB in all)")
     ap.add_argument("--form", default="both", choices=["both", "one", "two"],
                     help="N = 1: the step as two C-ABI calls (sks_forward + sks_backward: the headline), as one (sks_forward_backward, "
                          "which needs an upstream gradient independent of the image), or both (default: the headline is the two "
                          "calls, the one call is reported beside it)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # asked for N GPUs without a launcher around us: start one rank per GPU as CHILD processes (nothing here has

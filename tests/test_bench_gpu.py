@@ -72,3 +72,25 @@ def test_sharded_extras_at_world_2_on_one_device(device):
     for tag in ("api_step", "loop_dense", "loop_sparse"):
         assert r["strong_scaling"][tag]["ms_per_step"] > 0
     assert r["frame_sharded"]["frames_per_s_all_ranks"] > 0 and r["mean_equals_one_gpu"] == "bit for bit"
+
+
+def test_dump_outputs_writes_the_last_timed_step(device, tmp_path):
+    """--dump-outputs: the timed step's last outputs as float32 .npy files (the colour planes as a seeded sample), at most 64 MB,
+    consistent with each other; --steps is the number of timed steps."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    r = _run([sys.executable, "bench.py", "--steps", "7", "--warmup", "2", "--no-extras", "--no-cpu-baseline", "--form", "two",
+              "--dump-outputs", str(out)])
+    assert r["steps"] == 7 and r["ms_per_step"] > 0 and r["dumped_outputs"]["dir"] == str(out)
+    names = set(r["dumped_outputs"]["arrays"])
+    assert {"color", "invdepth", "radii", "dL_dmeans3D", "dL_dmeans3D_mean"} <= names
+    assert {p.name for p in out.iterdir()} == {n + ".npy" for n in names}
+    a = {n: np.load(out / (n + ".npy")) for n in names}
+    assert all(x.dtype == np.float32 and np.isfinite(x).all() for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["invdepth"].shape == (4, 1, 1000, 1000) and a["radii"].shape == (4, 17) and a["dL_dmeans3D"].shape == (4, 17, 3)
+    assert a["color"].shape == (1 << 22,) and r["dumped_outputs"]["arrays"]["color"].startswith("sample of")
+    assert (a["radii"] >= 0).all() and np.array_equal(a["radii"], np.round(a["radii"])) and a["radii"].max() > 0
+    # the step's result is the mean of the per-view joint gradients the same call handed back
+    mean = a["dL_dmeans3D"].astype(np.float64).mean(0)
+    assert np.allclose(a["dL_dmeans3D_mean"], mean, rtol=1e-5, atol=1e-6 * np.abs(mean).max())
