@@ -60,7 +60,9 @@ extern "C" {
 /* bits 16..18: binned path (P > SKS_SMALL_P), the views of a call are processed as (value + 1) VIEW GROUPS (at most 7, at most V):
    the binning kernels run once for all views, the forward's fill + composite launch and the backward's tile launch once per group.
    No result bit depends on it.  sks_forward_backward uses it to run group g's backward on the second stream while group g + 1's
-   forward streams on the first; sks_backward must be given the value its sks_forward had (like every other flag). */
+   forward streams on the first; sks_backward must be given the value its sks_forward had (like every other flag).  A field of
+   zero asks for the default: one group, unless the build sets SKS_BIN_FB_GROUPS or the process's SKS_BIN_GROUPS environment
+   variable (a tuning sweep; read once) names another count -- the same for every entry point. */
 #define SKS_BIN_GROUPS_SHIFT 16
 #define SKS_BIN_GROUPS(n) ((unsigned)(((n) - 1) & 7) << SKS_BIN_GROUPS_SHIFT)
 #define SKS_FILL_LINEAR (1u << 21)  /* tuning/tests: forward fill blocks always in linear (pass-major) mode */
@@ -144,7 +146,13 @@ int sks_backward(int V, int P, int C, int W, int H,
  * After an error behind the hand-over `stream` is made to wait for what aux_stream already holds, whatever fb_flags says.
  * fb_flags: SKS_FB_NO_JOIN = `stream` does NOT wait for the backward at the end: the caller has more to enqueue behind the
  * gradients on aux_stream -- a view-sharded step's collective on the joint gradients, which then also hides under the forward --
- * and makes `stream` wait for aux_stream itself (an event recorded on aux_stream, hipStreamWaitEvent on stream). */
+ * and makes `stream` wait for aux_stream itself (an event recorded on aux_stream, hipStreamWaitEvent on stream).  With a distinct
+ * aux_stream the gradients are ordered on aux_stream on EVERY branch: where the call ran its two halves one after the other on
+ * `stream` (P == 0, SKS_DEBUG_SYNC, the binned path in one view group) aux_stream is made to wait for all of it.
+ * The view-group count of a binned call is resolved by sks_forward, sks_backward and this call alike: SKS_BIN_GROUPS(n) in `flags`,
+ * or, when the field is zero, the build's default (one group) / the SKS_BIN_GROUPS environment variable of a tuning sweep.  One
+ * rule in one place rather than a count injected here: a state this call made is then walked by a later sks_backward with the
+ * caller's flags group for group as its forward laid it out, and no result bit depends on the count. */
 #define SKS_FB_NO_JOIN 1u
 int sks_forward_backward(int V, int P, int C, int W, int H,
                          const float* viewmatrix, const float* projmatrix,

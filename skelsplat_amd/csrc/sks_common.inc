@@ -210,10 +210,23 @@ constexpr int BIN_MAX_GROUPS = 7;       // view groups of one call (the 64-word 
 #endif
 constexpr int BIN_FB_GROUPS = SKS_BIN_FB_GROUPS;
 // views per group / number of groups for a call's SKS_BIN_GROUPS request (both sides of a forward / backward pair derive them
-// from the same flags and V)
+// from the same flags and V).  Every binned entry point -- sks_forward, sks_backward, sks_forward_backward -- resolves the count
+// HERE and nowhere else: a field of zero (the caller chose no count) is the build's default BIN_FB_GROUPS, or the SKS_BIN_GROUPS
+// environment variable of a tuning sweep (read once per process), so a state's later backward walks the groups its forward laid out
+// whichever entry point made either half.
+inline int bin_groups_default()
+{
+    static const int n = [] {
+        const char* e = getenv("SKS_BIN_GROUPS");
+        const int want = (e && atoi(e) > 0) ? atoi(e) : BIN_FB_GROUPS;
+        return want < 1 ? 1 : (want > BIN_MAX_GROUPS ? BIN_MAX_GROUPS : want);
+    }();
+    return n;
+}
 inline void bin_groups(unsigned flags, int V, int& vg, int& ng)
 {
-    int want = 1 + (int)((flags >> SKS_BIN_GROUPS_SHIFT) & 7u);
+    const unsigned field = (flags >> SKS_BIN_GROUPS_SHIFT) & 7u;
+    int want = field ? 1 + (int)field : bin_groups_default();
     if (want > BIN_MAX_GROUPS) want = BIN_MAX_GROUPS;
     if (want > V) want = V;
     vg = (V + want - 1) / want;

@@ -234,6 +234,34 @@ struct FbEvents {   // created by a thread's first combined call, reused by ever
     int dev = -1;
 };
 thread_local FbEvents tl_fb_events;
+// The calling thread's events for a combined call that hands over through `ngroups` group events (0 = only geom / done): created
+// on first use, re-created when the thread moved to another device.
+int fb_events(int ngroups, FbEvents*& out)
+{
+    FbEvents& ev = tl_fb_events;
+    int cur_dev = 0;
+    HIP_TRY(hipGetDevice(&cur_dev));
+    if (ev.geom && ev.dev != cur_dev) {   // (events belong to a device: a thread that moved to another one gets new ones)
+        (void)hipEventDestroy(ev.geom);
+        (void)hipEventDestroy(ev.done);
+        for (hipEvent_t& e : ev.grp)
+            if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        ev.geom = ev.done = nullptr;
+    }
+    // hand-over between two queues of ONE device: a device-scope release is all the waiting side needs (the default,
+    // a system-scope fence, is what a host reader of the event would want)
+    unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
+    if (const char* e = getenv("SKS_FB_EVENT_FLAGS")) evf = (unsigned)strtoul(e, nullptr, 0);   // tuning
+    if (!ev.geom) {
+        ev.dev = cur_dev;
+        HIP_TRY(hipEventCreateWithFlags(&ev.geom, evf));
+        HIP_TRY(hipEventCreateWithFlags(&ev.done, evf));
+    }
+    for (int gi = 0; gi < ngroups && gi < FB_MAX_EVENTS; gi++)
+        if (!ev.grp[gi]) HIP_TRY(hipEventCreateWithFlags(&ev.grp[gi], evf));
+    out = &ev;
+    return 0;
+}
 
 }  // namespace
 
@@ -523,13 +551,8 @@ int sks_forward_backward(int V, int P, int C, int W, int H, const float* viewmat
                          float* dL_dfeatures, float* dL_dmeans3D_mean, void* stream, void* aux_stream, unsigned fb_flags)
 {
     const bool small = P <= SKS_SMALL_P && !(flags & SKS_FORCE_BINNED);
-    if (!small && aux_stream && aux_stream != stream && !((flags >> SKS_BIN_GROUPS_SHIFT) & 7u)) {
-        // the binned path overlaps by VIEW GROUPS (the backward of a group starts from what the forward's compositor left per
-        // pixel of ITS views): unless the caller chose a count, BIN_FB_GROUPS of them
-        static const int env = [] { const char* e = getenv("SKS_BIN_GROUPS"); return e ? atoi(e) : 0; }();   // tuning sweeps
-        const int want = env > 0 ? env : BIN_FB_GROUPS;
-        flags |= SKS_BIN_GROUPS(want < 1 ? 1 : (want > BIN_MAX_GROUPS ? BIN_MAX_GROUPS : want));
-    }
+    // the binned path overlaps by VIEW GROUPS (the backward of a group starts from what the forward's compositor left per pixel of
+    // ITS views); how many: bin_groups, as for sks_forward / sks_backward (the flags stay the caller's)
     int vg = V, ng = 1;
     if (!small && V >= 1) bin_groups(flags, V, vg, ng);
     struct Ctx {
@@ -572,33 +595,24 @@ int sks_forward_backward(int V, int P, int C, int W, int H, const float* viewmat
                                   cov3D_precomp, scale_modifier, flags, out_color, out_invdepth, radii, geom, binning, bin_capacity,
                                   num_rendered_dev, nullptr, nullptr, stream, nullptr))
             return rc;
-        return backward_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, bg, means3D, features, opacities, scales, rotations,
-                             cov3D_precomp, scale_modifier, flags, radii, geom, binning, bin_capacity, dL_dout_color, dL_dout_invdepth,
-                             accum, dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, dL_dfeatures,
-                             dL_dmeans3D_mean, stream, BWD_RENDER | BWD_GEOM, -1);
+        if (int rc = backward_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, bg, means3D, features, opacities, scales,
+                                   rotations, cov3D_precomp, scale_modifier, flags, radii, geom, binning, bin_capacity, dL_dout_color,
+                                   dL_dout_invdepth, accum, dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D,
+                                   dL_dfeatures, dL_dmeans3D_mean, stream, BWD_RENDER | BWD_GEOM, -1))
+            return rc;
+        // SKS_FB_NO_JOIN: the caller enqueues what follows the gradients on aux_stream -- they must be ordered THERE on this branch
+        // as on the overlapped ones (aux_stream waits for everything the call put on `stream`)
+        if (no_join && aux_stream && aux_stream != stream) {
+            FbEvents* ev = nullptr;
+            if (int rc = fb_events(0, ev)) return rc;
+            HIP_TRY(hipEventRecord(ev->done, (hipStream_t)stream));
+            HIP_TRY(hipStreamWaitEvent((hipStream_t)aux_stream, ev->done, 0));
+        }
+        return 0;
     }
-    FbEvents& ev = tl_fb_events;
-    int cur_dev = 0;
-    HIP_TRY(hipGetDevice(&cur_dev));
-    if (ev.geom && ev.dev != cur_dev) {   // (events belong to a device: a thread that moved to another one gets new ones)
-        (void)hipEventDestroy(ev.geom);
-        (void)hipEventDestroy(ev.done);
-        for (hipEvent_t& e : ev.grp)
-            if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        ev.geom = ev.done = nullptr;
-    }
-    // hand-over between two queues of ONE device: a device-scope release is all the waiting side needs (the default,
-    // a system-scope fence, is what a host reader of the event would want)
-    unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-    if (const char* e = getenv("SKS_FB_EVENT_FLAGS")) evf = (unsigned)strtoul(e, nullptr, 0);   // tuning
-    if (!ev.geom) {
-        ev.dev = cur_dev;
-        HIP_TRY(hipEventCreateWithFlags(&ev.geom, evf));
-        HIP_TRY(hipEventCreateWithFlags(&ev.done, evf));
-    }
-    if (!small)
-        for (int gi = 0; gi < ng; gi++)
-            if (!ev.grp[gi]) HIP_TRY(hipEventCreateWithFlags(&ev.grp[gi], evf));
+    FbEvents* evp = nullptr;
+    if (int rc = fb_events(small ? 0 : ng, evp)) return rc;
+    FbEvents& ev = *evp;
     struct Run {
         // small path: behind the geometry kernel, i.e. behind everything the caller enqueued -- the whole backward
         static int after_geom(void* p)

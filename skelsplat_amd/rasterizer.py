@@ -749,8 +749,10 @@ def forward_backward_views(views: ViewBatch, means3D, features, opacities, scale
     later ones replay both records through the combined entry point.  overlap=False: the combined entry point, one stream.
     join=False: the current stream is NOT made to wait for the backward; the caller enqueues what follows the gradients -- a
     view-sharded step's collective -- on `workspace.aux_stream(dev)` (under the forward, too) and then calls `workspace.join(dev)`.
-    (On the paths that do not overlap -- first call, binned path, overlap=False -- the gradients are on the current stream and
-    join() is a no-op hand-over in the other direction: aux waits for the current stream first, so the same caller code is right.)"""
+    Whatever path the call takes, with join=False the gradients are ordered on the second stream when it returns, so the
+    same caller code is right everywhere: where the halves run one after the other on the current stream (the first call of a
+    shape, P == 0, debug, the binned path in one view group, overlap=False) the second stream is made to wait for it -- by the
+    library (sks_forward_backward with SKS_FB_NO_JOIN) or, where no second stream reaches the library, here."""
     if workspace is None:
         raise ValueError("forward_backward_views needs a Workspace (outputs, scratch and the second stream live there)")
     lib = _lib.load()
