@@ -368,7 +368,19 @@ int sks_adam_multi(int n_tensors, float* const* params, const float* const* grad
  * rotation (frames,P,4), opacity (frames,P), exp_avg/exp_avg_sq (frames,P,11), slots (frames,Vf,P,3), counters
  * (frames,2).  group_mask (bit j = view j of EVERY frame) and last_view are per frame (0 <= last_view < Vf); features,
  * the optimiser's hyper-parameters and the limb pairs are shared.  Each frame's results are bit-identical to running
- * it alone with frames = 1. */
+ * it alone with frames = 1.
+ *
+ * sks_loop_fused_step_es (since sks_version 12): the same step with the reference's opt_early_stopping criterion run PER FRAME
+ * on the device, as sks_loop_adam_step_es runs it for one scene: the tail workgroup of frame f feeds the criterion its views'
+ * losses (S_v / max(N_v, 1) as fp32, plus lambda x the limb loss of the pre-step xyz) in iteration order, after the geometry
+ * backward and before the optimiser step.  When it fires at the k-th iteration of the group, frame f steps at once on the first
+ * k views (view k's scaling / rotation / opacity gradients win, counters[f][0] advances by k, the LR schedule is taken at that
+ * iteration), the geometry of the updated parameters is written as usual, and es_state[f][1] and es_host_flags[f] receive the
+ * iteration.  At every later launch frame f costs nothing: its compositing-backward workgroups read the stopped word and
+ * leave, and its tail workgroup leaves before writing anything (parameters, moments, slots, counters, geometry, radii, loss
+ * sums).  The other frames go on; each frame stays bit-identical to sks_loop_adam_step_es running it alone.
+ * es_state: frames x (2 + 2 * es_window) ints on the device, zero at the start of the frames, each frame's slice laid out as
+ * sks_loop_adam_step_es's state; 1 <= es_window <= 16; es_host_flags: pinned HOST memory of `frames` ints, or NULL. */
 int sks_loop_fused_step(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
                         const float* tanfovx /*HOST V*/, const float* tanfovy /*HOST V*/, const float* features,
                         float scale_modifier, unsigned flags, int* radii, void* geom, const float* gt,
@@ -380,6 +392,18 @@ int sks_loop_fused_step(int V, int P, int C, int W, int H, const float* viewmatr
                         const int* view_wh /*HOST V x {W,H} or NULL*/, const size_t* gt_offsets /*HOST V or NULL*/,
                         int frames, const float* const* hm_factors /*HOST 4 or NULL, as for sks_backward_fused_loss*/,
                         void* stream);
+int sks_loop_fused_step_es(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                           const float* tanfovx /*HOST V*/, const float* tanfovy /*HOST V*/, const float* features,
+                           float scale_modifier, unsigned flags, int* radii, void* geom, const float* gt,
+                           const double* gt_totals, void* accum, double* loss_sums, float* packed, float* slots,
+                           unsigned long long group_mask, int last_view, float* xyz, float* scaling, float* rotation,
+                           float* opacity, float* exp_avg, float* exp_avg_sq, int* counters, int acc_steps,
+                           const double* lr_sched /*HOST 5*/, const double* lrs /*HOST 3*/, const double* adam /*HOST 3*/,
+                           float lambda_consistency, const int* limb /*HOST 8 or NULL*/,
+                           const int* view_wh /*HOST V x {W,H} or NULL*/, const size_t* gt_offsets /*HOST V or NULL*/,
+                           int frames, const float* const* hm_factors /*HOST 4 or NULL, as for sks_backward_fused_loss*/,
+                           int* es_state, int es_window, float es_tolerance, int* es_host_flags /*pinned HOST frames or NULL*/,
+                           void* stream);
 
 /* Measurement hook used by bench.py (no reference counterpart; state per HOST THREAD, like the error text): while enabled, the dominant kernel of sks_forward
  * (kind 0: forward compositor) and of sks_backward (kind 1: backward compositor) is bracketed by hipEvents recorded

@@ -25,6 +25,11 @@ struct BwdArgs {
     const float* hm_col = nullptr;
     const float* hm_cmin = nullptr;
     const float* hm_den = nullptr;
+    // early-stopping variant of the fused-loss kernel (ES, sks_loop_fused_step_es): es_stop[f * es_stride] != 0 when frame
+    // f = view / es_views has stopped -- written only by the previous launch's step tail, on the same stream
+    const int* es_stop = nullptr;
+    int es_stride = 0;
+    int es_views = 1;
 };
 
 // ------------------------------------------------------------------------------------------------------------
@@ -304,11 +309,17 @@ __device__ __forceinline__ unsigned rlu(unsigned x, int lane) { return (unsigned
 // Image sizes and plane offsets are per view (ViewTan::w/h, ViewOff): with the fused loss nothing dense is written, so one
 // launch carries a group of views with different sensors.
 // HMF (with LOSS): the heat-maps are given by their separable factors (BwdArgs::hm_*) instead of planes.
-template <int CG, bool DFEAT, bool LOSS, bool HMF = false>
+// ES (with LOSS): per-frame early stopping -- a workgroup whose frame has stopped leaves before anything else (the step tail
+// reads none of what it would write), so a stopped frame costs the launch nothing but that one load.
+template <int CG, bool DFEAT, bool LOSS, bool HMF = false, bool ES = false>
 __global__ __launch_bounds__(256, (DFEAT || CG > 20) ? 1 : 4) void k_render_bwd_wave(BwdArgs a, ViewTan vt, ViewOff vo)
 {
     static_assert(!(DFEAT && LOSS), "the fused-loss variant has no feature gradient");
     static_assert(LOSS || !HMF, "heat-map factors belong to the fused-loss variant");
+    static_assert(LOSS || !ES, "early stopping belongs to the fused-loss variant");
+    if constexpr (ES) {
+        if (a.es_stop[(size_t)((int)blockIdx.y / a.es_views) * a.es_stride] != 0) return;   // (workgroup-uniform)
+    }
     constexpr int NV = LOSS ? NACC + 1 : NACC + (DFEAT ? CG : 0);
     __shared__ float s_red[2][4][NV];
     // gridDim.z workgroups share the BWD_SPLITS partial-sum slots of a (view, Gaussian): workgroup sp owns slots sp,

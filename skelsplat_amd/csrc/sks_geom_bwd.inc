@@ -537,7 +537,11 @@ __global__ void k_mean_views(int V, int P, const float* __restrict__ dmeans3D, f
 //   B  the optimiser step (slots, mean over views, limb gradient, LR schedule, Adam) -- sks_loop_dev.h;
 //   C  geometry forward of the UPDATED parameters, i.e. the geom / radii the next group's compositor reads.
 // Same arithmetic in the same order as the separate kernels (bit-identical results).
+// ES (sks_loop_fused_step_es): frame f runs the early-stopping criterion on its own slice of aa.es_state between A and B,
+// exactly as k_loop_adam does for one scene: a cut inside the group shortens the step (views, winning view, iterations,
+// the LR schedule's iteration); a frame that stopped at an earlier launch leaves at once and writes nothing.
 // ------------------------------------------------------------------------------------------------------------
+template <bool ES = false>
 __global__ __launch_bounds__(256) void k_step_tail(GeomBwdArgs ga, ViewTan vt, sksloop::AdamArgs aa, int V, Geom g, int* radii)
 {
     __shared__ float s_xyz[256 * 3];
@@ -555,6 +559,11 @@ __global__ __launch_bounds__(256) void k_step_tail(GeomBwdArgs ga, ViewTan vt, s
         aa.grads += (size_t)vb * P * 11; aa.slots += (size_t)vb * P * 3;
         aa.xyz += (size_t)f * P * 3; aa.scaling += (size_t)f * P * 3; aa.rotation += (size_t)f * P * 4; aa.opacity += (size_t)f * P;
         aa.m += (size_t)f * P * 11; aa.vv += (size_t)f * P * 11; aa.counters += 2 * f;
+    }
+    if constexpr (ES) {
+        aa.es_state += (size_t)f * (2 + 2 * aa.es_window);
+        if (aa.es_host_flag) aa.es_host_flag += f;
+        if (aa.es_state[1] != 0) return;   // stopped at an earlier launch (workgroup-uniform; only this workgroup writes it)
     }
     // the optimiser's scalar work (LR schedule, bias corrections: double transcendentals) needs no gradient: started
     // first, it is finished long before phase A's loads are back
@@ -583,6 +592,22 @@ __global__ __launch_bounds__(256) void k_step_tail(GeomBwdArgs ga, ViewTan vt, s
         if (lane < ga.P) geom_bwd_finish(ga, vt, vg, lane, gs, n_view);
     }
     __syncthreads();   // every view's packed gradients are written (same workgroup, same L1)
+    if constexpr (ES) {
+        // the criterion on the loss sums phase A just wrote and the pre-step xyz adam_block_begin parked in s_xyz
+        __shared__ unsigned long long s_mask;
+        __shared__ int s_cut[3];
+        if (tid == 0)
+            sksloop::early_stop_decide(aa, aa.es_state, aa.es_host_flag, s_xyz,
+                                       [&](int v) { return (const double*)ga.loss_sums + 2 * (size_t)(vb + v); }, &s_mask, s_cut);
+        __syncthreads();
+        aa.group_mask = s_mask; aa.last_view = s_cut[0];
+        if (s_cut[1] != aa.acc_steps) {   // fired inside the group (workgroup-uniform): the step happens at that iteration,
+            aa.acc_steps = s_cut[1];      // so the LR schedule and the counters begin again from there
+            sksloop::adam_block_begin(aa, s_xyz, s_d, s_it);
+            __syncthreads();
+            if (tid == 0) sksloop::adam_step_sizes(aa, s_d, s_hyp);
+        }
+    }
     const sksloop::AdamLdsParams mirror{ s_np, s_np + 3 * P, s_np + 6 * P, s_np + 10 * P };
     sksloop::adam_block_finish(aa, s_xyz, s_hyp, s_d, s_it, &mirror, /*step_sizes_ready=*/true);
     __syncthreads();   // the parameters are updated

@@ -77,7 +77,9 @@ __global__ __launch_bounds__(256) void k_loop_adam(AdamArgs a)
         const int p = threadIdx.x;
         if (p < a.P) { s_xyz[3 * p] = a.xyz[3 * p]; s_xyz[3 * p + 1] = a.xyz[3 * p + 1]; s_xyz[3 * p + 2] = a.xyz[3 * p + 2]; }
         __syncthreads();
-        if (p == 0) sksloop::early_stop_decide(a, s_xyz, &s_mask, s_cut);
+        if (p == 0)
+            sksloop::early_stop_decide(a, a.es_state, a.es_host_flag, s_xyz,
+                                       [&a](int v) { return sksloop::loss_sums_of(a, v); }, &s_mask, s_cut);
         __syncthreads();
         if (s_cut[2]) return;            // the scene stopped at an earlier launch: parameters, moments, counters stay
         a.group_mask = s_mask; a.last_view = s_cut[0]; a.acc_steps = s_cut[1];

@@ -61,10 +61,13 @@ __device__ __forceinline__ const double* loss_sums_of(const AdamArgs& a, int v)
 // fires at the k-th iteration of this group, only the first k views refresh their slots, view k's scaling / rotation / opacity
 // gradients win, the optimiser steps at once (train.py:182) and the scene has ended: every later launch of the step does
 // nothing.  out: cut[0] = last view, cut[1] = iterations of this step, cut[2] = 1 if the scene had stopped before.
+// `st`: the scene's state (AdamArgs::es_state layout), `host_flag`: pinned int or nullptr, `sums_of(v)`: view v's {S, N}.
+// Callers: k_loop_adam (one scene, sums from loss_sums_of) and the fused step tail (one scene per workgroup, sums it wrote).
 constexpr int ES_MAX_WINDOW = 16;
-__device__ inline void early_stop_decide(const AdamArgs& a, const float* s_xyz, unsigned long long* mask_out, int* cut)
+template <class SumsOf>
+__device__ inline void early_stop_decide(const AdamArgs& a, int* st, int* host_flag, const float* s_xyz, SumsOf sums_of,
+                                         unsigned long long* mask_out, int* cut)
 {
-    int* st = a.es_state;
     cut[0] = a.last_view; cut[1] = a.acc_steps; cut[2] = 0;
     *mask_out = a.group_mask;
     if (st[1] != 0) { cut[2] = 1; return; }
@@ -85,7 +88,7 @@ __device__ inline void early_stop_decide(const AdamArgs& a, const float* s_xyz, 
     for (int k = 0; k < a.acc_steps; k++) {
         const int v = (it0 + k - 1) % a.V;
         mask |= 1ull << v;
-        const double* sn = loss_sums_of(a, v);
+        const double* sn = sums_of(v);
         const double cnt = sn[1] < 1.0 ? 1.0 : sn[1];
         const float loss = (float)(sn[0] / cnt) + cons;
         st[2 + n % ring] = __float_as_int(loss);
@@ -97,7 +100,7 @@ __device__ inline void early_stop_decide(const AdamArgs& a, const float* s_xyz, 
         }
         if (fire) {
             st[1] = it0 + k;
-            if (a.es_host_flag) *a.es_host_flag = it0 + k;
+            if (host_flag) *host_flag = it0 + k;
             cut[0] = v; cut[1] = k + 1;
             *mask_out = mask;
             break;

@@ -164,23 +164,25 @@ inline int bwd_wave_groups(int V, int P, unsigned flags)
     return pairs <= BWD_WG_PAIRS16 ? 16 : (pairs <= BWD_WG_PAIRS8 ? 8 : 4);
 }
 
-// the fused-loss variant of the wave-resident backward: heat-maps as planes or (a.hm_row) as separable factors
+// the fused-loss variant of the wave-resident backward: heat-maps as planes or (a.hm_row) as separable factors;
+// ES: the per-frame early-stopping instantiations (sks_loop_fused_step_es, a.es_stop set)
+template <bool ES = false>
 inline void launch_bwd_loss(const BwdArgs& a, const ViewTan& vt, const ViewOff& vo, dim3 grid, int cg, hipStream_t st)
 {
     if (a.hm_row) {
         switch (cg) {
-            case 4: hipLaunchKernelGGL((k_render_bwd_wave<4, false, true, true>), grid, dim3(256), 0, st, a, vt, vo); break;
-            case 16: hipLaunchKernelGGL((k_render_bwd_wave<16, false, true, true>), grid, dim3(256), 0, st, a, vt, vo); break;
-            case 20: hipLaunchKernelGGL((k_render_bwd_wave<20, false, true, true>), grid, dim3(256), 0, st, a, vt, vo); break;
-            default: hipLaunchKernelGGL((k_render_bwd_wave<32, false, true, true>), grid, dim3(256), 0, st, a, vt, vo); break;
+            case 4: hipLaunchKernelGGL((k_render_bwd_wave<4, false, true, true, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
+            case 16: hipLaunchKernelGGL((k_render_bwd_wave<16, false, true, true, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
+            case 20: hipLaunchKernelGGL((k_render_bwd_wave<20, false, true, true, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
+            default: hipLaunchKernelGGL((k_render_bwd_wave<32, false, true, true, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
         }
         return;
     }
     switch (cg) {
-        case 4: hipLaunchKernelGGL((k_render_bwd_wave<4, false, true>), grid, dim3(256), 0, st, a, vt, vo); break;
-        case 16: hipLaunchKernelGGL((k_render_bwd_wave<16, false, true>), grid, dim3(256), 0, st, a, vt, vo); break;
-        case 20: hipLaunchKernelGGL((k_render_bwd_wave<20, false, true>), grid, dim3(256), 0, st, a, vt, vo); break;
-        default: hipLaunchKernelGGL((k_render_bwd_wave<32, false, true>), grid, dim3(256), 0, st, a, vt, vo); break;
+        case 4: hipLaunchKernelGGL((k_render_bwd_wave<4, false, true, false, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
+        case 16: hipLaunchKernelGGL((k_render_bwd_wave<16, false, true, false, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
+        case 20: hipLaunchKernelGGL((k_render_bwd_wave<20, false, true, false, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
+        default: hipLaunchKernelGGL((k_render_bwd_wave<32, false, true, false, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
     }
 }
 
@@ -276,7 +278,7 @@ void sks_set_error_(const char* msg)  // used by the other translation units of 
 {
     snprintf(g_err, sizeof(g_err), "%s", msg);
 }
-int sks_version(void) { return 11; }
+int sks_version(void) { return 12; }
 
 int sks_scratch_bytes(int V, int P, int C, int W, int H, size_t bin_capacity, size_t* geom, size_t* binning, size_t* accum)
 {
@@ -740,14 +742,17 @@ int sks_geometry(int V, int P, int C, int W, int H, const float* viewmatrix, con
     return 0;
 }
 
-int sks_loop_fused_step(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
-                        const float* tanfovx, const float* tanfovy, const float* features, float scale_modifier,
-                        unsigned flags, int* radii, void* geom, const float* gt, const double* gt_totals, void* accum,
-                        double* loss_sums, float* packed, float* slots, unsigned long long group_mask, int last_view,
-                        float* xyz, float* scaling, float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq,
-                        int* counters, int acc_steps, const double* lr_sched, const double* lrs, const double* adam,
-                        float lambda_consistency, const int* limb, const int* view_wh, const size_t* gt_offsets, int frames,
-                        const float* const* hm_factors, void* stream)
+// sks_loop_fused_step and (es_state != nullptr) sks_loop_fused_step_es: the same two launches, the latter in the early-stopping
+// instantiations of both kernels
+static int loop_fused_step_impl(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                                const float* tanfovx, const float* tanfovy, const float* features, float scale_modifier,
+                                unsigned flags, int* radii, void* geom, const float* gt, const double* gt_totals, void* accum,
+                                double* loss_sums, float* packed, float* slots, unsigned long long group_mask, int last_view,
+                                float* xyz, float* scaling, float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq,
+                                int* counters, int acc_steps, const double* lr_sched, const double* lrs, const double* adam,
+                                float lambda_consistency, const int* limb, const int* view_wh, const size_t* gt_offsets,
+                                int frames, const float* const* hm_factors, int* es_state, int es_window, float es_tolerance,
+                                int* es_host_flags, void* stream)
 {
     if (int rc = check_common(V, P, C, W, H)) return rc;
     if (P < 1 || P > 64) return fail(-1, "fused step needs 1 <= P <= 64 (got %d)", P);
@@ -770,22 +775,64 @@ int sks_loop_fused_step(int V, int P, int C, int W, int H, const float* viewmatr
                                                   exp_avg, exp_avg_sq, counters, acc_steps, lr_sched, lrs, adam,
                                                   lambda_consistency, limb))
         return fail(-2, "%s", err);
+    const bool es = es_state != nullptr;
+    if (es) { aa.es_state = es_state; aa.es_window = es_window; aa.es_tol = es_tolerance; aa.es_host_flag = es_host_flags; }
     Geom g = geom_from(geom, V, P, W, H);
     g.cover = nullptr;   // no forward render on this path
     BwdArgs a{ P, C, W, H, flags, g, features, nullptr, gt, nullptr, (float*)accum, nullptr, nullptr };
     if (hm_factors) { a.hm_row = hm_factors[0]; a.hm_col = hm_factors[1]; a.hm_cmin = hm_factors[2]; a.hm_den = hm_factors[3]; }
+    if (es) { a.es_stop = es_state + 1; a.es_stride = 2 + 2 * es_window; a.es_views = Vf; }
     dim3 grid(P, V, bwd_wave_groups(V, P, flags));   // see launch_bwd_small
     {
         ProfScope prof(1, st);
-        launch_bwd_loss(a, vt, vo, grid, pick_cg(C), st);
+        if (es) launch_bwd_loss<true>(a, vt, vo, grid, pick_cg(C), st);
+        else launch_bwd_loss(a, vt, vo, grid, pick_cg(C), st);
     }
     STAGE_CHECK("render-backward(fused loss)");
     GeomBwdArgs ga{ P, C, W, H, flags, viewmatrix, projmatrix, xyz, opacity, scaling, rotation, nullptr, scale_modifier, radii,
                     (const float*)accum, BWD_SPLITS, gt_totals, loss_sums, packed, nullptr, nullptr, nullptr, nullptr, nullptr,
                     nullptr, nullptr };
-    hipLaunchKernelGGL(k_step_tail, dim3(frames), dim3(256), 0, st, ga, vt, aa, Vf, g, radii);
+    if (es) hipLaunchKernelGGL(k_step_tail<true>, dim3(frames), dim3(256), 0, st, ga, vt, aa, Vf, g, radii);
+    else hipLaunchKernelGGL(k_step_tail<false>, dim3(frames), dim3(256), 0, st, ga, vt, aa, Vf, g, radii);
     STAGE_CHECK("step tail");
     return 0;
+}
+
+int sks_loop_fused_step(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                        const float* tanfovx, const float* tanfovy, const float* features, float scale_modifier,
+                        unsigned flags, int* radii, void* geom, const float* gt, const double* gt_totals, void* accum,
+                        double* loss_sums, float* packed, float* slots, unsigned long long group_mask, int last_view,
+                        float* xyz, float* scaling, float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq,
+                        int* counters, int acc_steps, const double* lr_sched, const double* lrs, const double* adam,
+                        float lambda_consistency, const int* limb, const int* view_wh, const size_t* gt_offsets, int frames,
+                        const float* const* hm_factors, void* stream)
+{
+    return loop_fused_step_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, features, scale_modifier, flags, radii,
+                                geom, gt, gt_totals, accum, loss_sums, packed, slots, group_mask, last_view, xyz, scaling,
+                                rotation, opacity, exp_avg, exp_avg_sq, counters, acc_steps, lr_sched, lrs, adam,
+                                lambda_consistency, limb, view_wh, gt_offsets, frames, hm_factors, nullptr, 0, 0.0f, nullptr,
+                                stream);
+}
+
+int sks_loop_fused_step_es(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                           const float* tanfovx, const float* tanfovy, const float* features, float scale_modifier,
+                           unsigned flags, int* radii, void* geom, const float* gt, const double* gt_totals, void* accum,
+                           double* loss_sums, float* packed, float* slots, unsigned long long group_mask, int last_view,
+                           float* xyz, float* scaling, float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq,
+                           int* counters, int acc_steps, const double* lr_sched, const double* lrs, const double* adam,
+                           float lambda_consistency, const int* limb, const int* view_wh, const size_t* gt_offsets, int frames,
+                           const float* const* hm_factors, int* es_state, int es_window, float es_tolerance,
+                           int* es_host_flags, void* stream)
+{
+    if (!es_state)
+        return fail(-2, "loop_fused_step_es: es_state is required (sks_loop_fused_step is the step without a criterion)");
+    if (es_window < 1 || es_window > sksloop::ES_MAX_WINDOW)
+        return fail(-1, "loop_fused_step_es: window %d out of range [1, %d]", es_window, sksloop::ES_MAX_WINDOW);
+    return loop_fused_step_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, features, scale_modifier, flags, radii,
+                                geom, gt, gt_totals, accum, loss_sums, packed, slots, group_mask, last_view, xyz, scaling,
+                                rotation, opacity, exp_avg, exp_avg_sq, counters, acc_steps, lr_sched, lrs, adam,
+                                lambda_consistency, limb, view_wh, gt_offsets, frames, hm_factors, es_state, es_window,
+                                es_tolerance, es_host_flags, stream);
 }
 
 int sks_prof_spin(double microseconds, void* stream)

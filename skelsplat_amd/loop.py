@@ -673,6 +673,27 @@ class MultiViewLoop:
         return self.gm._xyz.detach()
 
 
+def _frame_criterion(early_stopping):
+    """FrameBatchLoop's `early_stopping` -> None (off) or (window, tolerance) of the reference's criterion, which the frame
+    batch runs per frame on the device; anything else is refused."""
+    es = early_stopping
+    if isinstance(es, str):
+        if es not in early_stopping_strategy:
+            raise ValueError(f"early_stopping = {es!r}: expected one of {sorted(early_stopping_strategy)}")
+        es = early_stopping_strategy[es]()
+    if type(es) is NotStopping:
+        return None
+    if type(es) is not OptEarlyStopping:
+        raise ValueError("FrameBatchLoop runs the early-stopping criterion per frame on the device: it takes "
+                         "'opt_early_stopping' or an OptEarlyStopping; a host-side callable needs MultiViewLoop")
+    w = es.window_size
+    if not isinstance(w, (int, np.integer)) or not 1 <= int(w) <= 16:
+        raise ValueError(f"OptEarlyStopping.window_size = {w!r}: the device criterion keeps 1 .. 16")
+    if es.loss_history:
+        raise ValueError("OptEarlyStopping has a loss history already: every frame starts from an empty one")
+    return int(w), float(es.repeat_tolerance)
+
+
 class FrameBatchLoop:
     """F independent frames seen by the SAME cameras, optimised side by side in the sparse fused step.
 
@@ -686,10 +707,16 @@ class FrameBatchLoop:
     `gaussians`: a GaussianModel of ONE frame after training_setup() -- the template for the initial scaling /
     rotation / opacity, the one-hot features and the optimiser's configuration; its own tensors are not touched.
     Parameters live stacked: xyz / scaling (F,P,3), rotation (F,P,4), opacity (F,P,1).  F x V <= 64 views per launch.
-    Early stopping (a per-frame host decision, one sync per group) is MultiViewLoop's business, not this class's."""
+
+    `early_stopping` (configs/*.yaml `training.early_stopping`): "no_stopping", "opt_early_stopping", or an OptEarlyStopping
+    with 1 <= window_size <= 16 and an empty history.  The criterion runs per frame on the device, inside the step's tail
+    (sks_loop_fused_step_es): each frame stops at its own iteration, exactly as a MultiViewLoop running it alone with the
+    same criterion, and a stopped frame's workgroups leave at once from then on.  `stopped_at` reads each frame's stopping
+    iteration from pinned memory without waiting; `counters[f, 0]` is frame f's own iteration, while `iteration` stays the
+    number of iterations enqueued.  Host-side criteria (any other callable) read every loss back: MultiViewLoop runs those."""
 
     def __init__(self, gaussians, cameras, frames, dataset="h36m", accumulation_steps=4, lambda_consistency=1e-5,
-                 antialiasing=False, use_graph=False, factored=True):
+                 antialiasing=False, use_graph=False, factored=True, early_stopping="no_stopping"):
         import ctypes
         gm = gaussians
         self.gm = gm
@@ -721,6 +748,14 @@ class FrameBatchLoop:
         self.exp_avg_sq = torch.zeros((F, P, 11), device=dev)
         self.counters = torch.zeros((F, 2), dtype=torch.int32, device=dev)
         self.accumulated_grads = torch.zeros((F, V, P, 3), device=dev)    # train.py:121, one V-slot buffer per frame
+        # per-frame early stopping on the device: (window, tolerance) or None; the state of every frame's criterion (the
+        # layout of sks_loop_adam_step_es's, one row per frame) and the pinned flags the tail writes the stopping iteration to
+        self._es = _frame_criterion(early_stopping)
+        self._es_state = self._es_flags = None
+        if self._es is not None:
+            self._es_state = torch.zeros((F, 2 + 2 * self._es[0]), dtype=torch.int32, device=dev)
+            self._es_flags = torch.zeros(F, dtype=torch.int32).pin_memory()
+            self._es_flags_np = self._es_flags.numpy()
         self._packed = torch.zeros((F * V, P, 11), device=dev)
         self._sums = torch.zeros((F * V, 2), dtype=torch.float64, device=dev)
         cfg = gm.opt_cfg
@@ -787,6 +822,13 @@ class FrameBatchLoop:
             pts = points if torch.is_tensor(points) else torch.as_tensor(np.asarray(points))
             if tuple(pts.shape) != (F, P, 3):
                 raise ValueError(f"points must be (F,P,3) = {(F, P, 3)}, got {tuple(pts.shape)}")
+            if self._es is not None:
+                # a frame still running may yet write its flag from work enqueued before: let it drain first (once every
+                # frame has stopped, nothing writes a flag any more, and the next frames start at once)
+                if not self._es_flags_np.all():
+                    torch.cuda.current_stream(self.device).synchronize()
+                self._es_flags_np[:] = 0
+                self._es_state.zero_()
             self.xyz.copy_(pts.to(device=self.device, dtype=torch.float32))
             self.scaling.copy_(self._init[0].expand(F, P, 3))
             self.rotation.copy_(self._init[1].expand(F, P, 4))
@@ -824,17 +866,22 @@ class FrameBatchLoop:
                                                 None, antialiasing=self.antialiasing, raw_params=True, out=self._fstate,
                                                 frames=self.F)
                 self._geom_valid = True
+            es = {} if self._es is None else dict(es_state=self._es_state, es_window=self._es[0], es_tolerance=self._es[1],
+                                                  es_flags=self._es_flags)
             R.loop_fused_step(self._fstate, self.stats_all, self.features, self._packed, self._sums, self.accumulated_grads,
                               group_mask, last_view, self.xyz, self.scaling, self.rotation, self.opacity, self.exp_avg,
                               self.exp_avg_sq, self.counters, n_iters, self._sched, self._lrs, self._adam,
-                              self.lambda_consistency, self._limb)
+                              self.lambda_consistency, self._limb, **es)
         s = self._sums.view(self.F, self.V, 2)
         self.last_losses = (s[..., 0], s[..., 1])       # per (frame, view) {S, N}: loss = S / N
 
     def step_group(self, parameters_untouched=False):
         """(parameters_untouched: as MultiViewLoop.step_group)
         Iterations self.iteration+1 .. the next optimiser step of EVERY frame (train.py:130-222; the frames share the
-        iteration counter, the view order and therefore the group's view mask)."""
+        iteration counter, the view order and therefore the group's view mask).  With early stopping, nothing is enqueued
+        once every frame has stopped."""
+        if self._all_stopped():
+            return self.iteration
         it0 = self.iteration + 1
         it1 = it0
         while it1 % self.acc_steps != 0:
@@ -859,9 +906,28 @@ class FrameBatchLoop:
         self.iteration = it1
         return it1
 
+    @property
+    def stopped_at(self):
+        """Per frame: the iteration early stopping ended it at, or None (so far: read from the pinned flags without waiting;
+        after run() returns, final)."""
+        if self._es is None:
+            return [None] * self.F
+        return [int(x) or None for x in self._es_flags_np]
+
+    def _all_stopped(self):
+        return self._es is not None and bool(self._es_flags_np.all())
+
     def run(self, iterations=500, groups_per_graph=25):
         """All F frames up to `iterations`; returns the joints (F,P,3).  With use_graph, `groups_per_graph` groups are one
-        hipGraph, as in MultiViewLoop.run."""
+        hipGraph, as in MultiViewLoop.run.  With early stopping, the flags are polled between launches without waiting,
+        enqueuing ends once every frame has stopped, and the stream is synchronised once, at the end."""
+        self._enqueue(iterations, groups_per_graph)
+        if self._es is not None:
+            torch.cuda.current_stream(self.device).synchronize()
+        return self.xyz
+
+    def _enqueue(self, iterations, groups_per_graph):
+        """run() without its final synchronisation (FramePipeline drives several loops with it)."""
         if self.use_graph and self.acc_steps % self.V == 0 and self.iteration % self.acc_steps == 0:
             key = ((1 << self.V) - 1, (self.acc_steps - 1) % self.V, self.acc_steps)
             remaining = (iterations - self.iteration) // self.acc_steps
@@ -878,15 +944,14 @@ class FrameBatchLoop:
                         for _ in range(G):
                             self._device_group(*key)
                     self._multi = ((key, G), graph)
-                while remaining >= G:
+                while remaining >= G and not self._all_stopped():
                     self._multi[1].replay()
                     self.iteration += G * self.acc_steps
                     remaining -= G
         chained = False
-        while self.iteration < iterations:
+        while self.iteration < iterations and not self._all_stopped():
             self.step_group(parameters_untouched=chained)
             chained = True
-        return self.xyz
 
     def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25):
         """The reference's outer loop over the frames of a sequence (train.py:74-99) F frames at a time: `points`
@@ -918,7 +983,9 @@ class FramePipeline:
     loops on separate streams fill that hole with each other's backward kernels: on one MI355X (H36M, 4 views, 500
     iterations per frame, heat-map generation included) 292 frames/s one frame at a time, 1 480 with 16 frames per launch,
     1 900-2 100 with 2-4 such loops in flight (tools/bench_frames.py).  Results do not depend on `frames` / `streams`:
-    every frame's trajectory is bit-identical to a MultiViewLoop running it alone."""
+    every frame's trajectory is bit-identical to a MultiViewLoop running it alone.
+    `early_stopping` (as FrameBatchLoop's) goes to every loop; then a stream whose batch has stopped entirely takes the next
+    batch at once, and `stopped_at` holds the last sequence's stopping iterations."""
 
     def __init__(self, gaussians, cameras, frames=16, streams=2, **kw):
         kw.setdefault("use_graph", True)
@@ -926,6 +993,7 @@ class FramePipeline:
         self.device = self.loops[0].device
         self.streams = [torch.cuda.Stream(self.device) for _ in self.loops]
         self.F, self.P = self.loops[0].F, self.loops[0].P
+        self.stopped_at = None       # early stopping: (N,) int64 of the last optimize_sequence, 0 = ran to the end
 
     def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, interleave=100):
         """(N,P,3) initial joints + (N,V,J,2) detections -> (N,P,3) optimised joints (train.py:74-99 over the frames).
@@ -939,6 +1007,14 @@ class FramePipeline:
         out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
         cur = torch.cuda.current_stream(self.device)
         starts = list(range(0, N, F))
+        if self.loops[0]._es is not None:
+            self.stopped_at = torch.zeros(N, dtype=torch.int64, device=self.device)
+            for st in self.streams:
+                st.wait_stream(cur)
+            self._sequence_es(pts, p2d, out, starts, iterations, groups_per_graph, interleave)
+            for st in self.streams:
+                cur.wait_stream(st)
+            return out
         for st in self.streams:
             st.wait_stream(cur)                      # inputs and `out` were produced on the caller's stream
         for w in range(0, len(starts), S):
@@ -960,6 +1036,44 @@ class FramePipeline:
         for st in self.streams:
             cur.wait_stream(st)
         return out
+
+    def _sequence_es(self, pts, p2d, out, starts, iterations, groups_per_graph, interleave):
+        """optimize_sequence with early stopping: every stream keeps its own batch and takes the next one as soon as its
+        batch is done -- all frames stopped (seen in the pinned flags, without waiting) or `iterations` enqueued -- instead
+        of waiting for the other streams' batches.  Results and stopping iterations are copied on the batch's stream."""
+        N, F = pts.shape[0], self.F
+        pending = iter(starts)
+
+        def take(fb, st):
+            b = next(pending, None)
+            if b is None:
+                return None
+            with torch.cuda.stream(st):
+                if b + F <= N:
+                    fb.new_scenes(pts[b:b + F], poses_2d=p2d[b:b + F])
+                else:
+                    idx = [min(b + i, N - 1) for i in range(F)]
+                    fb.new_scenes(pts[idx], poses_2d=p2d[idx])
+            return [fb, st, b, 0]
+
+        step = max(int(interleave), 1)
+        active = [a for a in (take(fb, st) for fb, st in zip(self.loops, self.streams)) if a is not None]
+        while active:
+            nxt = []
+            for slot in active:
+                fb, st, b, k = slot
+                k = min(iterations, k + step)
+                with torch.cuda.stream(st):
+                    fb._enqueue(k, groups_per_graph)
+                    slot[3] = k
+                    if k >= iterations or fb._all_stopped():
+                        n = min(F, N - b)
+                        out[b:b + n] = fb.xyz[:n]
+                        self.stopped_at[b:b + n] = fb._es_state[:n, 1]      # (0: the frame ran to the end)
+                        slot = take(fb, st)
+                if slot is not None:
+                    nxt.append(slot)
+            active = nxt
 
 
 def mpjpe(pred, gt):

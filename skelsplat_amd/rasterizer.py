@@ -1333,11 +1333,14 @@ def _check_heatmaps(views, C, stats):
 
 
 def loop_fused_step(st: ForwardState, stats: GtStats, features, packed, sums, slots, group_mask, last_view, xyz, scaling,
-                    rotation, opacity, exp_avg, exp_avg_sq, counters, acc_steps, lr_sched, lrs, adam, lambda_consistency, limb):
+                    rotation, opacity, exp_avg, exp_avg_sq, counters, acc_steps, lr_sched, lrs, adam, lambda_consistency, limb,
+                    es_state=None, es_window=0, es_tolerance=0.0, es_flags=None):
     """sks_loop_fused_step: fused-loss compositing backward + (geometry backward, Adam step, geometry forward of the
     updated parameters) for one accumulation group; `st` must describe the current parameters and is left describing the
     updated ones.  lr_sched / lrs / adam / limb: ctypes arrays as for sks_loop_adam_step.  A state made with
-    geometry_views(frames=F) steps F independent frames at once (stacked parameter / moment / slot / counter tensors)."""
+    geometry_views(frames=F) steps F independent frames at once (stacked parameter / moment / slot / counter tensors).
+    es_state: (F, 2 + 2 * es_window) int32 device tensor -> sks_loop_fused_step_es, the reference's opt_early_stopping per
+    frame on the device (es_flags: (F,) pinned int32 host tensor that receives each frame's stopping iteration, or None)."""
     lib = _lib.load()
     dev = xyz.device
     V, P, C = st.views.V, st.P, st.C
@@ -1346,16 +1349,27 @@ def loop_fused_step(st: ForwardState, stats: GtStats, features, packed, sums, sl
     feat2 = _f32c(features, "features").reshape(P, -1)
     stream = torch.cuda.current_stream(dev).cuda_stream
     accum = _accum(dev, stream, V, P, C)
+    args = (V, P, C, W, H, st.views.viewmatrix.data_ptr(), st.views.projmatrix.data_ptr(), st.views.tanfovx,
+            st.views.tanfovy, feat2.data_ptr(), st.scale_modifier, st.flags, st.radii.data_ptr(), st.geom.data_ptr(),
+            _lib.ptr(stats.gt), stats.totals.data_ptr(), accum.data_ptr(), sums.data_ptr(), packed.data_ptr(),
+            slots.data_ptr(), group_mask, last_view, xyz.data_ptr(), scaling.data_ptr(), rotation.data_ptr(),
+            opacity.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), counters.data_ptr(), acc_steps, lr_sched, lrs,
+            adam, float(lambda_consistency), limb, st.views.wh, stats.offsets, st.frames,
+            None if stats.factors is None else stats.factors.ptrs)
+    if es_state is None:
+        with torch.cuda.device(dev):
+            rc = lib.sks_loop_fused_step(*args, stream)
+        _lib.check(rc, "sks_loop_fused_step")
+        return
+    if es_state.dtype != torch.int32 or not es_state.is_contiguous() or es_state.device != dev \
+            or tuple(es_state.shape) != (st.frames, 2 + 2 * int(es_window)):
+        raise ValueError(f"es_state must be a contiguous int32 ({st.frames}, {2 + 2 * int(es_window)}) tensor on {dev}")
+    if es_flags is not None and (es_flags.dtype != torch.int32 or es_flags.numel() != st.frames or es_flags.device.type != "cpu"):
+        raise ValueError(f"es_flags must be a pinned int32 host tensor of {st.frames} ints")
     with torch.cuda.device(dev):
-        rc = lib.sks_loop_fused_step(V, P, C, W, H, st.views.viewmatrix.data_ptr(), st.views.projmatrix.data_ptr(),
-                                     st.views.tanfovx, st.views.tanfovy, feat2.data_ptr(), st.scale_modifier, st.flags,
-                                     st.radii.data_ptr(), st.geom.data_ptr(), _lib.ptr(stats.gt), stats.totals.data_ptr(),
-                                     accum.data_ptr(), sums.data_ptr(), packed.data_ptr(), slots.data_ptr(), group_mask,
-                                     last_view, xyz.data_ptr(), scaling.data_ptr(), rotation.data_ptr(), opacity.data_ptr(),
-                                     exp_avg.data_ptr(), exp_avg_sq.data_ptr(), counters.data_ptr(), acc_steps, lr_sched, lrs,
-                                     adam, float(lambda_consistency), limb, st.views.wh, stats.offsets,
-                                     st.frames, None if stats.factors is None else stats.factors.ptrs, stream)
-    _lib.check(rc, "sks_loop_fused_step")
+        rc = lib.sks_loop_fused_step_es(*args, es_state.data_ptr(), int(es_window), float(es_tolerance),
+                                        None if es_flags is None else es_flags.data_ptr(), stream)
+    _lib.check(rc, "sks_loop_fused_step_es")
 
 
 def backward_fused_loss(st: ForwardState, stats: GtStats, means3D, features, opacities, scales, rotations, cov3D_precomp,
