@@ -1,26 +1,31 @@
 #!/usr/bin/env python3
 """bench.py -- rendered+backpropagated views/s of the skeletal-Gaussian rasterizer hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W     (N > 1: one rank per GPU under torch.distributed.run; a plain
-                                                        `python bench.py --gpus N` starts that launcher itself)
+    python bench.py --gpus N --steps K --warmup W [--full]     (N > 1: one rank per GPU under torch.distributed.run; a plain
+                                                                 `python bench.py --gpus N` starts that launcher itself)
+
+A plain run measures the headline alone: it sets up, tunes and warms the step, times the K steps, writes --dump-outputs and
+prints the line (with the `roofline` figure the timed steps' own event pairs give).  --full adds everything else described
+below: the other form of the step, the roofline over eight output sets, the in-run PMC traffic, the CPU baseline, the loop and
+the other BASELINE configs at N = 1, and at N > 1 the one-GPU reference of the same workload and the loop's sharded steps.
 
 A "step" is one accumulation group of the reference loop (train.py:130-222): the V views that share the Gaussian
 parameters are rendered (forward) and back-propagated (backward) through the C ABI with the upstream gradient
 dL/d(render) already resident in HBM, then the per-view joint gradients are averaged (train.py:215-217).
 
 N = 1 (default): BASELINE.json configs[1] -- H36M, 17 joints, 4 views @ 1000x1000 (synthetic skeleton + cameras).
-    Extras on the same line: configs[2] (Panoptic 31 views @ 1920x1080), configs[4] (stress, binned path), the real H36M
-    sensor mix (1002- and 1000-wide views in one group), the full loop step (render + masked-L2 + backward + Adam).
+    Extras on the same line (--full): configs[2] (Panoptic 31 views @ 1920x1080), configs[4] (stress, binned path), the
+    real H36M sensor mix (1002- and 1000-wide views in one group), the full loop step (render + masked-L2 + backward + Adam).
 N > 1: BASELINE.json configs[3] -- the SAME 31 Panoptic views split over the ranks (view v -> rank v % N, strong
     scaling), each rank renders and back-propagates its views, ONE all_gather_into_tensor (RCCL) of the per-view joint
-    gradients per step rebuilds the V slots on every rank.  `value` = 31 views x steps / time; `strong_scaling` holds the
-    same step run by one GPU alone (measured in the same run, all ranks side by side without communication), the speed-up,
-    and the same pair for the loop's dense step and its sparse fused step; frame sharding (every rank its own frames, no
-    communication) is reported as frames/s.
+    gradients per step rebuilds the V slots on every rank.  `value` = 31 views x steps / time; with --full,
+    `strong_scaling` holds the same step run by one GPU alone (measured in the same run, all ranks side by side without
+    communication), the speed-up, and the same pair for the loop's dense step and its sparse fused step; frame sharding
+    (every rank its own frames, no communication) is reported as frames/s.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (forward fill + compositor): algorithmic bytes per
 launch = 4*H*W*(C+1)*V_local (the dense colour + inverse-depth planes it must write) / its average launch
-duration measured with hipEvents on the launch stream.  `cpu_baseline` times the pure-PyTorch restatement
+duration measured with hipEvents on the launch stream.  `cpu_baseline` (--full) times the pure-PyTorch restatement
 (oracle/torch_ref.py) on the host cores for a bounded sample of the same workload.
 """
 import argparse
@@ -450,8 +455,10 @@ def run_single(args, torch, dev, wl):
     # sks_forward_backward, the backward on a second stream BESIDE the forward -- legal only because this benchmark's dL is a
     # resident tensor that does not depend on the image (SURVEY section 8d's synthetic dense dL); reported beside the headline,
     # labelled.  --form one / two restricts the run to one of them (a rocprofv3 --kernel-trace --stats run per form gives
-    # per-kernel averages that are not a mixture); the default measures both.
+    # per-kernel averages that are not a mixture); the default measures both with --full, the headline alone without.
     forms = ("two", "one") if args.form == "both" else (args.form,)
+    if not args.full:
+        forms = forms[:1]
     prof = not args.no_prof
     stride = int(os.environ.get("SKS_PROF_EVERY", "0")) or prof_stride(args.steps)
 
@@ -460,8 +467,8 @@ def run_single(args, torch, dev, wl):
     def measure(one_call, dump=False):
         """W warm-up + K timed steps of one form; the forward compositor launches of every n-th TIMED step carry a hipEvent pair
         (hipExtLaunchKernelGGL: stamped from the kernel's own dispatch, on the launch stream -- a bracketed step costs ~13 us of
-        queue time, so the sample is 5 .. 25 of the K launches), topped up to ROOF_MIN_LAUNCHES behind the timed region by
-        untimed steps of the SAME form with every launch bracketed."""
+        queue time, so the sample is 5 .. 25 of the K launches); with --full topped up to ROOF_MIN_LAUNCHES behind the timed
+        region by untimed steps of the SAME form with every launch bracketed."""
         st = ApiStep(views, params, dL, one_call=one_call)
         st.autotune()                                      # (untimed: Workspace.tune -- the fill configuration for this form on this box)
         for _ in range(args.warmup):
@@ -477,7 +484,7 @@ def run_single(args, torch, dev, wl):
         pf_ = None
         if prof:
             have = _lib.prof_count(0)
-            if have < ROOF_MIN_LAUNCHES:
+            if args.full and have < ROOF_MIN_LAUNCHES:
                 _lib.prof_enable(True, every=1, kinds=(0,))
                 for _ in range(ROOF_MIN_LAUNCHES - have):
                     st()
@@ -516,9 +523,9 @@ def run_single(args, torch, dev, wl):
         assert torch.equal(out, out2)                      # (bit for bit the same gradients either way)
     pb = None
     zero_us = zero_fresh_us = pf_rot = None
-    if prof:
+    nbytes_out = 4.0 * V * (C + 1) * H * W
+    if prof and args.full:
         zero_us = zero_fill_us(torch, V * (C + 1) * H * W, dev, sync)
-        nbytes_out = 4.0 * V * (C + 1) * H * W
         zero_fresh_us = zero_fill_us(torch, V * (C + 1) * H * W, dev, sync, rotate=8) if nbytes_out < 1.2e9 else None
         if nbytes_out < 1.2e9:
             pf_rot, rot_flags = rotating()
@@ -583,7 +590,7 @@ def run_single(args, torch, dev, wl):
                 "avg_launch_us": a_s * 1e6, "launch_us_p10_p50_p90": [round(1e3 * x, 2) for x in pf2[2]], "launches_timed": pf2[1],
                 "achieved": alg_bytes / a_s / 1e9, "frac": alg_bytes / a_s / 1e9 / HBM_PEAK_GBS,
                 "frac_median": alg_bytes / (pf2[2][1] * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             tb = measure_traffic(wl["dataset"])
             if tb:
                 res["roofline"]["traffic_file"] = res["roofline"]["traffic"]
@@ -601,7 +608,7 @@ def run_single(args, torch, dev, wl):
         if pb and pb[1]:
             res["bwd_kernel_avg_us"] = pb[0] * 1e3 / pb[1]
             res["bwd_kernel_us_p10_p50_p90"] = [round(1e3 * x, 2) for x in pb[2]]
-        if not args.no_extras and nbytes_out < 1.2e9:
+        if args.full and not args.no_extras and nbytes_out < 1.2e9:
             # what round 5 reported as the headline: plain stores into the one buffer set the step rewrites -- cache-assisted
             try:
                 sp = ApiStep(views, params, dL, one_call=False)
@@ -622,7 +629,7 @@ def run_single(args, torch, dev, wl):
                 del sp
             except Exception as e:
                 res["same_buffer_plain_stores"] = {"error": repr(e)[:200]}
-    if args.no_extras:
+    if args.no_extras or not args.full:
         return res, scene, params
 
     extras = {}
@@ -1157,16 +1164,18 @@ def run_sharded(args, torch, dist, dev, wl, world, rank):
     local = [v for v in range(V) if v % world == rank]
     gen = torch.Generator(device=dev).manual_seed(0)
     dL_all = torch.randn((V, C, H, W), device=dev, generator=gen)     # identical on every rank
-    n_ref = max(5, args.steps // 10)
-    # (A) one GPU alone: every rank runs the whole 31-view step side by side, no communication.  Its time is the N = 1
-    #     reference of this run; N x 31 views / that time is the weak-scaling aggregate.
-    full = ApiStep(R.ViewBatch.from_cameras(scene.cameras), params, dL_all, one_call=os.environ.get("SKS_BENCH_ONE_CALL") == "1")
-    full.autotune()
-    dt_full, _ = timed(full, n_ref, 3, sync)
-    dt_full = max_over_ranks(dt_full)
-    one_gpu_ms = 1e3 * dt_full / n_ref
-    ref_mean = full().clone()     # what the sharded step must reproduce: the mean over all V views' joint gradients
-    del full
+    if args.full:
+        # (A) one GPU alone: every rank runs the whole 31-view step side by side, no communication.  Its time is the N = 1
+        #     reference of this run; N x 31 views / that time is the weak-scaling aggregate.
+        n_ref = max(5, args.steps // 10)
+        full = ApiStep(R.ViewBatch.from_cameras(scene.cameras), params, dL_all,
+                       one_call=os.environ.get("SKS_BENCH_ONE_CALL") == "1")
+        full.autotune()
+        dt_full, _ = timed(full, n_ref, 3, sync)
+        dt_full = max_over_ranks(dt_full)
+        one_gpu_ms = 1e3 * dt_full / n_ref
+        ref_mean = full().clone()     # what the sharded step must reproduce: the mean over all V views' joint gradients
+        del full
     # (B) the timed region: the same V views, view v on rank v % world, one all_gather of the joint gradients per step
     lviews = R.ViewBatch.from_cameras([scene.cameras[v] for v in local]) if local else None
     dL = dL_all[local].contiguous() if local else None
@@ -1191,24 +1200,26 @@ def run_sharded(args, torch, dist, dev, wl, world, rank):
     dt = max_over_ranks(dt)
     pf = None
     if prof:
-        # topped up to ROOF_MIN_LAUNCHES by untimed steps of the same form behind the timed region -- the same number on every
-        # rank (the steps hold the collective), whatever each rank has sampled
-        extra = max(0, ROOF_MIN_LAUNCHES - (args.steps + stride - 1) // stride)
-        _lib.prof_enable(True, every=1, kinds=(0,))
-        for _ in range(extra):
-            step()
-        torch.cuda.synchronize()
+        if args.full:
+            # topped up to ROOF_MIN_LAUNCHES by untimed steps of the same form behind the timed region -- the same number on
+            # every rank (the steps hold the collective), whatever each rank has sampled
+            extra = max(0, ROOF_MIN_LAUNCHES - (args.steps + stride - 1) // stride)
+            _lib.prof_enable(True, every=1, kinds=(0,))
+            for _ in range(extra):
+                step()
+            torch.cuda.synchronize()
         pf = _lib.prof_read_quantiles(0) if local else None
         _lib.prof_enable(False)
     assert torch.isfinite(out).all()
-    # all_gather: the V rows are summed in view order on every rank -- bit for bit the one-GPU mean; all_reduce re-associates
-    same = bool(torch.equal(out, ref_mean)) if exchange_mode == "all_gather" else \
-        bool(torch.allclose(out, ref_mean, rtol=1e-5, atol=1e-6 * float(ref_mean.abs().max())))
-    assert same, "the sharded step's mean differs from the one-GPU mean"
+    if args.full:
+        # all_gather: the V rows are summed in view order on every rank -- bit for bit the one-GPU mean; all_reduce re-associates
+        same = bool(torch.equal(out, ref_mean)) if exchange_mode == "all_gather" else \
+            bool(torch.allclose(out, ref_mean, rtol=1e-5, atol=1e-6 * float(ref_mean.abs().max())))
+        assert same, "the sharded step's mean differs from the one-GPU mean"
     used_direct = step.direct is not None
     step_one_call = step.one_call
     one_call_extra = None
-    if not step_one_call and not args.no_extras:
+    if args.full and not step_one_call and not args.no_extras:
         # beside it: the one-call form (needs an upstream gradient that does not depend on the image): the rank's backward and the
         # collective run on a second stream under its dense forward.  Every rank issues the same calls: the collectives stay matched
         s1 = ApiStep(lviews, params, dL, V_total=V, exchange=(world, rank, None), one_call=True)
@@ -1232,8 +1243,7 @@ def run_sharded(args, torch, dist, dev, wl, world, rank):
         coll += ", RCCL's C API on the launch stream" if used_direct else ", through torch.distributed"
     what = (f"one all-reduce (pre-multiplied sum, weight V_local / V) of the (P,3) means of the ranks' local joint gradients"
             if exchange_mode == "all_reduce" else f"one all_gather_into_tensor of the ({vmax},P,3) joint gradients")
-    strong = {"ideal_speedup": V / vmax,
-              "api_step": {"one_gpu_ms_per_step": one_gpu_ms, "ms_per_step": ms, "speedup": one_gpu_ms / ms}}
+    strong = {"ideal_speedup": V / vmax}
     res = {
         "metric": METRIC, "value": V * args.steps / dt, "unit": "views/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -1244,14 +1254,18 @@ def run_sharded(args, torch, dist, dev, wl, world, rank):
                    "path": "C ABI sks_forward_backward (the backward beside the dense forward on a second stream) with the step's "
                            "collective and the mean behind the backward on that second stream: hidden under the forward; eager "
                            "launches" if step_one_call else "C ABI sks_forward + sks_backward + collective on one stream, eager launches"},
-        # the SAME 31-view step on one GPU alone, measured in this run (all ranks side by side, no communication): the
-        # reference point for this line's `value` (the N = 1 line of bench.py times a different workload, BASELINE configs[1])
-        "one_gpu_same_workload_views_per_s": V * n_ref / dt_full,
-        "one_gpu_same_workload_ms_per_step": one_gpu_ms,
-        "speedup_vs_one_gpu_same_workload": one_gpu_ms / ms,
-        "mean_equals_one_gpu": "bit for bit" if exchange_mode == "all_gather" else "rtol 1e-5",
-        "weak_scaling_views_per_s": world * V * n_ref / dt_full,
     }
+    if args.full:
+        strong["api_step"] = {"one_gpu_ms_per_step": one_gpu_ms, "ms_per_step": ms, "speedup": one_gpu_ms / ms}
+        res.update({
+            # the SAME 31-view step on one GPU alone, measured in this run (all ranks side by side, no communication): the
+            # reference point for this line's `value` (the N = 1 line of bench.py times a different workload, BASELINE configs[1])
+            "one_gpu_same_workload_views_per_s": V * n_ref / dt_full,
+            "one_gpu_same_workload_ms_per_step": one_gpu_ms,
+            "speedup_vs_one_gpu_same_workload": one_gpu_ms / ms,
+            "mean_equals_one_gpu": "bit for bit" if exchange_mode == "all_gather" else "rtol 1e-5",
+            "weak_scaling_views_per_s": world * V * n_ref / dt_full,
+        })
     if one_call_extra:
         res["one_call_step"] = one_call_extra
     if dumped is not None:
@@ -1262,7 +1276,7 @@ def run_sharded(args, torch, dist, dev, wl, world, rank):
         res["roofline"]["note"] = f"rank 0's launch: its {len(local)} local views"
         res["roofline"]["timed_in"] = ("the timed region of this line" + (": the backward and the step's collective run BESIDE the forward "
                                        "on a second queue there" if step_one_call else ""))
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # (C, D) the loop's own step -- render + masked-L2 + backward + [all_gather] + Adam (train.py:130-222): dense and
         # sparse fused, each alone on one GPU (shard_views=False, all ranks side by side) and sharded over the ranks
         try:
@@ -1322,8 +1336,7 @@ def run_sharded(args, torch, dist, dev, wl, world, rank):
     # the three steps' speed-ups at the top level: north_star's >= 6 x is expected of the DENSE loop step (it is made of bytes,
     # DESIGN.md section 6); the API step's ~35 us of fixed cost and one exchange leave it around 6 x, the sparse step is a
     # 90 us chain of latencies that does not shard
-    res["api_step_speedup_vs_one_gpu"] = strong["api_step"]["speedup"]
-    for tag in ("loop_dense", "loop_sparse"):
+    for tag in ("api_step", "loop_dense", "loop_sparse"):
         if tag in strong:
             res[tag + "_speedup_vs_one_gpu"] = strong[tag]["speedup"]
     return res
@@ -1336,11 +1349,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="default: h36m on one GPU (BASELINE configs[1]), panoptic when sharded (configs[3])")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else this benchmark measures or checks: the other form of the step, "
+                         "the roofline over eight output sets, the CPU baseline, the extras (see the module docstring); the "
+                         "--no-* options below trim a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-prof", action="store_true", help="do not bracket kernels with hipEvents")
     ap.add_argument("--no-dropin", action="store_true", help="skip the literal drop-in iteration extra (its single-view "
                     "launches would mix into per-kernel averages of a rocprofv3 run)")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline measurement")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: the step's forms and their kernel figures only (no "
+                    "loop, no other configurations, no in-run PMC passes)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed step computed in its last call (rank 0: its views' image, "
                          "inverse depth, radii and gradients, and the mean joint gradient) as DIR/<name>.npy, float32; an output "
@@ -1348,7 +1366,7 @@ def main():
     ap.add_argument("--form", default="both", choices=["both", "one", "two"],
                     help="N = 1: the step as two C-ABI calls (sks_forward + sks_backward: the headline), as one (sks_forward_backward, "
                          "which needs an upstream gradient independent of the image), or both (default: the headline is the two "
-                         "calls, the one call is reported beside it)")
+                         "calls; with --full the one call is reported beside it)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -1400,7 +1418,7 @@ def main():
     wl = WORKLOADS[args.workload or ("panoptic" if use_dist else "h36m")]
     if use_dist:
         res = run_sharded(args, torch, dist, dev, wl, world, rank)
-        if world == 1 and not args.no_cpu_baseline:    # (the CPU sample is the N = 1 line's: no rank waits in a collective for it)
+        if world == 1 and args.full and not args.no_cpu_baseline:   # (the CPU sample is the N = 1 line's: no rank waits in a collective for it)
             from skelsplat_amd.scene import SyntheticScene
             sc = SyntheticScene(wl["dataset"], n_views=wl["V"], seed=0)
             _, _, prm = make_scene(torch, wl, dev)
@@ -1408,7 +1426,7 @@ def main():
         dist.barrier()     # all ranks leave the process group together
     else:
         res, scene, params = run_single(args, torch, dev, wl)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(scene, params, n_views=2)
     if rank == 0:
         os.write(real_stdout, (json.dumps(res) + "\n").encode())

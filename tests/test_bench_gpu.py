@@ -23,7 +23,7 @@ def _run(cmd, env=None, timeout=900):
 
 
 def test_headline_line_has_the_contract_fields(device):
-    r = _run([sys.executable, "bench.py", "--steps", "12", "--warmup", "3", "--no-extras", "--no-cpu-baseline"])
+    r = _run([sys.executable, "bench.py", "--steps", "12", "--warmup", "3", "--full", "--no-extras", "--no-cpu-baseline"])
     assert r["n_gpus"] == 1 and r["steps"] == 12 and r["warmup"] == 3 and r["unit"] == "views/s" and r["dtype"] == "f32"
     assert r["config"]["workload"] == "h36m_4view_1000x1000_P17_C17"
     assert abs(r["value"] - 4 / r["ms_per_step"] * 1e3) < 1e-6 * r["value"]
@@ -42,8 +42,8 @@ def test_headline_line_has_the_contract_fields(device):
 
 def test_sharded_step_at_world_1_over_rccl(device):
     """The `--gpus N` code path (views sharded, the backward and the collective on the second stream) with one rank."""
-    r = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "6", "--warmup", "2", "--no-extras", "--no-cpu-baseline"],
-             env={"SKS_BENCH_FORCE_DIST": "1", "MASTER_PORT": "29577"})
+    r = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "6", "--warmup", "2", "--full", "--no-extras",
+              "--no-cpu-baseline"], env={"SKS_BENCH_FORCE_DIST": "1", "MASTER_PORT": "29577"})
     assert r["n_gpus"] == 1 and r["config"]["views_total"] == 31 and r["config"]["views_on_rank0"] == 31
     assert r["config"]["exchange"] in ("all_gather", "all_reduce") and "RCCL" in r["config"]["parallelism"]
     assert r["value"] > 0 and r["roofline"]["frac"] > 0.3
@@ -65,7 +65,7 @@ def test_sharded_extras_at_world_2_on_one_device(device):
     """The same with the extras the driver's multi-GPU run carries (the loop's dense and sparse steps alone and sharded, frame
     sharding): every rank goes through the same collectives and the line still comes out as one."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", "29580", "bench.py", "--gpus", "2", "--steps", "10", "--warmup", "2"]
+           "--master-port", "29580", "bench.py", "--gpus", "2", "--steps", "10", "--warmup", "2", "--full"]
     r = _run(cmd, env={"SKS_BENCH_ONE_DEVICE": "1"})
     assert "loop_error" not in r, r.get("loop_error")
     assert "cpu_baseline" not in r            # the CPU sample belongs to the N = 1 line
@@ -94,3 +94,23 @@ def test_dump_outputs_writes_the_last_timed_step(device, tmp_path):
     # the step's result is the mean of the per-view joint gradients the same call handed back
     mean = a["dL_dmeans3D"].astype(np.float64).mean(0)
     assert np.allclose(a["dL_dmeans3D_mean"], mean, rtol=1e-5, atol=1e-6 * np.abs(mean).max())
+
+
+def test_plain_run_is_the_headline_alone_and_computes_what_full_computes(device, tmp_path):
+    """Without --full the line carries the headline and the `roofline` of the timed steps' own event pairs, nothing measured
+    behind them; the timed step's outputs are bit for bit those of a --full run with the same arguments."""
+    import numpy as np
+    base = [sys.executable, "bench.py", "--gpus", "1", "--steps", "9", "--warmup", "2"]
+    r = _run(base + ["--dump-outputs", str(tmp_path / "plain")])
+    f = _run(base + ["--full", "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert r[k] == f[k], k
+    assert r["n_gpus"] == 1 and abs(r["value"] - 4 / r["ms_per_step"] * 1e3) < 1e-6 * r["value"]
+    assert r["config"]["form"] == "two calls" and r["config"]["autotuned"] is not None
+    assert not {"one_call_step", "cpu_baseline", "same_buffer_plain_stores", "bwd_kernel_avg_us", "panoptic", "stress"} & set(r)
+    assert "one_call_step" in f
+    roof = r["roofline"]
+    assert roof["timed_in"].startswith("the timed region") and "rotating_output_sets" not in roof and 0 < roof["launches_timed"] <= 9
+    assert r["dumped_outputs"]["arrays"] == f["dumped_outputs"]["arrays"]
+    for n in r["dumped_outputs"]["arrays"]:
+        assert np.array_equal(np.load(tmp_path / "plain" / (n + ".npy")), np.load(tmp_path / "full" / (n + ".npy"))), n

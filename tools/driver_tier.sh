@@ -1,13 +1,16 @@
 #!/bin/bash
-# the GPU test tier and the driver's bench line, as the driver runs them at round end (GPU box):  bash tools/driver_tier.sh
-mkdir -p gpurun_out
-( time timeout 1500 python -m pytest tests -x -q -m gpu ) > gpurun_out/pytest_gpu.log 2>&1
-tail -5 gpurun_out/pytest_gpu.log
-( time python bench.py ) > gpurun_out/bench.json 2> gpurun_out/bench.err
-tail -3 gpurun_out/bench.err
-python - <<'PY'
-import json
-r = json.load(open("gpurun_out/bench.json"))
+# the GPU test tier and the full bench line in one go, with the line's key figures printed (GPU box):
+#   bash tools/driver_tier.sh [OUTDIR]      (OUTDIR: where the logs and the line go; default: a fresh directory under /tmp)
+OUT=${1:-$(mktemp -d /tmp/sks_tier.XXXXXX)}
+mkdir -p "$OUT"
+echo "outputs in $OUT"
+( time timeout 1500 python -m pytest tests -x -q -m gpu ) > "$OUT/pytest_gpu.log" 2>&1
+tail -5 "$OUT/pytest_gpu.log"
+( time python bench.py --full ) > "$OUT/bench.json" 2> "$OUT/bench.err"
+tail -3 "$OUT/bench.err"
+python - "$OUT/bench.json" <<'PY'
+import json, sys
+r = json.load(open(sys.argv[1]))
 def show(d, keys):
     return {k: d.get(k) for k in keys}
 print(show(r, ["value", "ms_per_step"]), r["config"]["form"], r["config"]["autotuned"]["fill_role"])

@@ -18,8 +18,8 @@ for WL in h36m panoptic; do
   # is set by hand)
   T1=0; [ $WL = h36m ] && T1=0x300
   rm -rf "$OUT/${WL}_stats" "$OUT/${WL}1_stats"
-  SKS_BENCH_AUTOTUNE=0 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${WL}_stats" -o stats -- python3 "$ROOT/bench.py" --workload $WL --form two --steps 100 --warmup 5 --no-cpu-baseline --no-extras > "$OUT/${WL}_bench_under_rocprof.json" 2> "$OUT/${WL}_stats.log"
-  SKS_BENCH_AUTOTUNE=0 SKS_FWD_TUNE=$T1 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${WL}1_stats" -o stats -- python3 "$ROOT/bench.py" --workload $WL --form one --steps 100 --warmup 5 --no-cpu-baseline --no-extras > "$OUT/${WL}_bench_one_call_under_rocprof.json" 2> "$OUT/${WL}1_stats.log"
+  SKS_BENCH_AUTOTUNE=0 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${WL}_stats" -o stats -- python3 "$ROOT/bench.py" --workload $WL --form two --steps 100 --warmup 5 --full --no-cpu-baseline --no-extras > "$OUT/${WL}_bench_under_rocprof.json" 2> "$OUT/${WL}_stats.log"
+  SKS_BENCH_AUTOTUNE=0 SKS_FWD_TUNE=$T1 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${WL}1_stats" -o stats -- python3 "$ROOT/bench.py" --workload $WL --form one --steps 100 --warmup 5 --full --no-cpu-baseline --no-extras > "$OUT/${WL}_bench_one_call_under_rocprof.json" 2> "$OUT/${WL}1_stats.log"
   rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT/${WL}_w" -o w -- python3 "$ROOT/bench.py" --workload $WL --form two --steps 20 --warmup 3 --no-cpu-baseline --no-prof --no-extras > /dev/null 2> "$OUT/${WL}_w.log"
   rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/${WL}_f" -o f -- python3 "$ROOT/bench.py" --workload $WL --form two --steps 20 --warmup 3 --no-cpu-baseline --no-prof --no-extras > /dev/null 2> "$OUT/${WL}_f.log"
 done
@@ -36,10 +36,10 @@ python3 tools/bench_ssim.py > "$OUT/bench_ssim.txt" 2>/dev/null
 bash tools/pmc_ssim.sh fwd 4,17,1000,1000 > "$OUT/ssim_pmc_fwd.txt" 2>&1
 bash tools/pmc_ssim.sh train 4,17,1000,1000 > "$OUT/ssim_pmc_train.txt" 2>&1
 cd "$ROOT"
-python3 bench.py > "$OUT/h36m_bench.json" 2> "$OUT/h36m_bench.log"
-python3 bench.py --workload panoptic --steps 50 --warmup 5 > "$OUT/panoptic_bench.json" 2> "$OUT/panoptic_bench.log"
+python3 bench.py --full > "$OUT/h36m_bench.json" 2> "$OUT/h36m_bench.log"
+python3 bench.py --full --workload panoptic --steps 50 --warmup 5 > "$OUT/panoptic_bench.json" 2> "$OUT/panoptic_bench.log"
 # the sharded path at world size 1 (RCCL all_gather included, the group also replayed as a hipGraph)
-SKS_BENCH_FORCE_DIST=1 SKS_GRAPH_COLLECTIVES=1 python3 bench.py --steps 50 --warmup 5 > "$OUT/sharded_world1_bench.json" 2> "$OUT/sharded_world1_bench.log"
+SKS_BENCH_FORCE_DIST=1 SKS_GRAPH_COLLECTIVES=1 python3 bench.py --full --steps 50 --warmup 5 > "$OUT/sharded_world1_bench.json" 2> "$OUT/sharded_world1_bench.log"
 python3 tools/width_sweep2.py 1000,1002,1024,1920 0 > "$OUT/width_sweep.txt" 2>&1
 python3 tools/bench_frames.py 1 2 4 8 16 2>/dev/null | grep "frames/s" > "$OUT/frames.txt"
 FACTORED=0 ONLY_BATCH=1 python3 tools/bench_frames.py 16 2>/dev/null | grep "frames/s" | sed 's/^/planes (factored=False): /' >> "$OUT/frames.txt"
