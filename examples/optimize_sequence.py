@@ -2,7 +2,10 @@
 """A whole synthetic SEQUENCE through the hot path, the way the reference's train.py walks a dataset (one frame after the
 other, train.py:74-99) -- but many frames per launch: noisy 2D detections of N frames -> DLT initial guesses -> 500
 iterations of the multi-view loop for every frame (loop.FramePipeline) -> MPJPE per frame.
-python examples/optimize_sequence.py [--frames 64] [--per-launch 16] [--streams 2] [--iters 500]"""
+python examples/optimize_sequence.py [--frames 64] [--per-launch 16] [--streams 2] [--iters 500] [--init host|device]
+--init host (default): the DLT runs on the host, frame by frame, and its points are uploaded; --init device: the detections
+go to the device once and every batch is triangulated there (FramePipeline.optimize_sequence(None, ...)); the timed region
+runs from the detections to the joints either way."""
 import argparse
 import os
 import sys
@@ -25,6 +28,7 @@ def main():
     ap.add_argument("--per-launch", type=int, default=16)
     ap.add_argument("--streams", type=int, default=2)
     ap.add_argument("--iters", type=int, default=500)
+    ap.add_argument("--init", choices=("host", "device"), default="host")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     sc = SyntheticScene(args.dataset, n_views=args.views, seed=0, device=dev)
@@ -35,23 +39,34 @@ def main():
     p2d = np.stack([np.stack([project_points(c, gt[f]) + rng.normal(0, 3.0, (sc.n_points, 2)) for c in sc.cameras])
                     for f in range(args.frames)]).astype(np.float32)
     Pm = triangulation.projection_matrices(sc.cameras)
-    init = np.stack([triangulation.triangulate_poses(Pm, p2d[f])[:, :3] for f in range(args.frames)]).astype(np.float32)
-    gm = GaussianModel().create_from_points(init[0], sc.spatial_lr_scale, sc.n_joints, scene_type=args.dataset, device=dev)
+
+    def host_init():
+        return np.stack([triangulation.triangulate_poses(Pm, p2d[f])[:, :3] for f in range(args.frames)]).astype(np.float32)
+
+    gm = GaussianModel().create_from_points(host_init()[0], sc.spatial_lr_scale, sc.n_joints, scene_type=args.dataset, device=dev)
     gm.training_setup()
     pipe = FramePipeline(gm, sc.cameras, frames=args.per_launch, streams=args.streams, dataset=args.dataset,
                          accumulation_steps=args.views)
-    pipe.optimize_sequence(init, p2d, iterations=args.iters)          # captures the hipGraphs
+    if args.init == "device":
+        p2d_dev = torch.as_tensor(p2d, device=dev)
+        run = lambda: pipe.optimize_sequence(None, p2d_dev, iterations=args.iters, return_initial=True)
+    else:
+        def run():
+            init = host_init()
+            return pipe.optimize_sequence(init, p2d, iterations=args.iters), init
+    run()                                                             # captures the hipGraphs
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    out = pipe.optimize_sequence(init, p2d, iterations=args.iters)
+    out, init = run()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     pred = out.cpu().numpy()
+    init = init.cpu().numpy() if torch.is_tensor(init) else init
     e0 = np.mean([io.mpjpe(init[f], gt[f]) for f in range(args.frames)])
     e1 = np.mean([io.mpjpe(pred[f], gt[f]) for f in range(args.frames)])
     print(f"{args.dataset} V={args.views} {sc.W}x{sc.H}: {args.frames} frames x {args.iters} iterations in {dt * 1e3:.1f} ms "
           f"({args.frames / dt:.0f} frames/s, {args.per_launch} frames per launch on {args.streams} streams); "
-          f"mean MPJPE {e0:.2f} mm (DLT) -> {e1:.2f} mm")
+          f"mean MPJPE {e0:.2f} mm (DLT on the {args.init}) -> {e1:.2f} mm")
 
 
 if __name__ == "__main__":

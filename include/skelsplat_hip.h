@@ -224,6 +224,21 @@ int sks_heatmap_factors(int V, int J, int W, int H, const float* means3D, const 
 int sks_heatmap_totals(int V, int J, int W, int H, const float* row, const float* col, const float* cmin, const float* den,
                        const int* view_wh, double* gt_totals, void* stream);
 
+/* Initial joints of N frames by linear (DLT) triangulation, one launch (reference: triangulation.py:122-150).  Per (frame,
+ * joint) the 2V x 4 homogeneous system with the rows x * P[2] - P[0] and y * P[2] - P[1] of every view, view-major; the result
+ * is the right singular vector of the smallest singular value divided by its fourth component, in float64, by one-sided Jacobi
+ * on the columns of the system itself (no normal equations).  Since sks_version 13.
+ * proj: DOUBLE (V,3,4), K [R|t] per view, with rig_stride = 0 -- or one rig per frame, (N,V,3,4), with rig_stride = V * 12;
+ * the detections (N,V,J,2), pixel x, y: as float (poses_2d) or as double (poses_2d_f64), exactly one of the two;
+ * valid: optional (N,V,J) bytes, 0 = leave this detection out (NULL: all enter);
+ * outputs, at least one of the first two: xyz (N,J,3) float -- what the loop consumes, xyzw rounded to nearest --, xyzw (N,J,4)
+ * double, homogeneous with w == 1 as the reference returns, n_used (N,J) = detections that entered the system.  A joint with
+ * n_used < 2 has no solution: its xyz / xyzw are NaN.  1 <= V <= SKS_MAX_VIEWS.  A frame's result does not depend on N, on its
+ * place in the batch or on the stream. */
+int sks_triangulate(int N, int V, int J, const double* proj, size_t rig_stride, const float* poses_2d,
+                    const double* poses_2d_f64, const unsigned char* valid, float* xyz, double* xyzw, int* n_used,
+                    void* stream);
+
 /* Replaces fusedssim (submodules/fused-ssim/ssim.cu:368-404, binding ext.cpp): img1, img2, ssim_map and the three
  * optional partial-derivative maps (train == true) are (B,CH,H,W) fp32; "same" zero padding. */
 int sks_fused_ssim_fwd(int B, int CH, int H, int W, float C1, float C2, const float* img1, const float* img2,

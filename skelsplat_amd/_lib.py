@@ -77,6 +77,7 @@ SIGNATURES = {
     "sks_loop_fused_step_es": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _vp, C.c_ulonglong, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp,
                                     _vp, _i, _vp, _vp, _i, _f, _vp, _vp]),
+    "sks_triangulate": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sks_prof_enable": (_i, [_i]),
     "sks_prof_spin": (_i, [C.c_double, _vp]),
     "sks_prof_read": (_i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),

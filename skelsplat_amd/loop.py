@@ -131,6 +131,9 @@ class MultiViewLoop:
         # only the multi-process CPU tests use it (gloo has no GPU), the product path is _local_view_grads.
         self.view_grad_fn = view_grad_fn
         self.cameras = cameras
+        # K [R|t] of all V views, float64 on the device: new_scene(points=None) triangulates the initial joints with them
+        from .triangulation import device_projection_matrices
+        self._proj = device_projection_matrices(cameras, dev)
         P = gaussians._xyz.shape[0]
         self.P = P
         Vl = len(self.local_ids)
@@ -302,10 +305,24 @@ class MultiViewLoop:
         heat-maps, iteration counter back to 0).  Everything is re-initialised in place -- parameters, Adam moments,
         step counters, V-slot buffer, heat-maps and their tile statistics keep their storage -- so the hipGraphs
         captured for the previous frame are replayed as they are.  Give either `poses_2d` (V,J,2) (the heat-maps are
-        generated from the re-initialised Gaussians like general_utils.py:175-304) or ready `heatmaps`."""
+        generated from the re-initialised Gaussians like general_utils.py:175-304) or ready `heatmaps`.
+        `points=None`: the initial joints are the DLT triangulation of `poses_2d` (triangulation.triangulate_sequence, on
+        the device, on the current stream; with `dropout` the dropped planes' detections stay out of it).  It needs all V
+        views' detections, so a view-sharded loop (world > 1) refuses it; a joint kept in fewer than two views has no
+        triangulation and starts as NaN."""
         from .heatmaps import generate_heatmaps
         gm = self.gm
-        gm.reset_from_points(points)
+        if points is not None:
+            gm.reset_from_points(points)
+        else:
+            if poses_2d is None:
+                raise ValueError("new_scene(points=None) triangulates the initial joints from poses_2d: give poses_2d "
+                                 "(ready heatmaps do not carry the detections)")
+            if self.world > 1:
+                raise ValueError("new_scene(points=None): a view-sharded loop (world > 1) sees only its own views' "
+                                 "detections; triangulate on one rank (triangulation.triangulate_sequence) and pass points")
+            if self._proj is None:
+                raise ValueError("new_scene(points=None): the cameras carry no K / R / T to build projection matrices from")
         with torch.no_grad():
             self.accumulated_grads.zero_()
             if self.device_tail:
@@ -325,6 +342,12 @@ class MultiViewLoop:
                     dist.broadcast(buf, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0,
                                    group=self.group)
                     drop = buf.to(device="cpu", dtype=torch.bool)
+            if points is None:
+                from .triangulation import triangulate_sequence
+                p2d = torch.as_tensor(poses_2d, device=self.device)
+                if p2d.dim() != 3 or tuple(p2d.shape[:2]) != (self.V, self.P):
+                    raise ValueError(f"poses_2d must be (V,J,2) = {(self.V, self.P, 2)}, got {tuple(p2d.shape)}")
+                gm.reset_from_points(triangulate_sequence(self._proj, p2d, valid=None if drop is None else ~drop))
             for grp in self.size_groups:
                 slots, vb, gt, stats, idx = grp
                 ids = [self.local_ids[k] for k in slots]
@@ -673,6 +696,17 @@ class MultiViewLoop:
         return self.gm._xyz.detach()
 
 
+def _sequence_inputs(points, poses_2d):
+    """optimize_sequence's (points or None, detections, N): tensors stay where they are, arrays become CPU tensors."""
+    p2d = poses_2d if torch.is_tensor(poses_2d) else torch.as_tensor(np.asarray(poses_2d))
+    if points is None:
+        return None, p2d, p2d.shape[0]
+    pts = points if torch.is_tensor(points) else torch.as_tensor(np.asarray(points))
+    if p2d.shape[0] != pts.shape[0]:
+        raise ValueError(f"{pts.shape[0]} frames of points, {p2d.shape[0]} of detections")
+    return pts, p2d, pts.shape[0]
+
+
 def _frame_criterion(early_stopping):
     """FrameBatchLoop's `early_stopping` -> None (off) or (window, tolerance) of the reference's criterion, which the frame
     batch runs per frame on the device; anything else is refused."""
@@ -767,6 +801,9 @@ class FrameBatchLoop:
         self._limb = (ctypes.c_int * 8)(*limbs) if self.lambda_consistency != 0.0 else None
         cams_all = [cameras[k % V] for k in range(F * V)]
         self._cams_all = cams_all
+        # K [R|t] per view, float64 on the device, built once: new_scenes(points=None) triangulates with them
+        from .triangulation import device_projection_matrices
+        self._proj = device_projection_matrices(cameras, dev)
         sizes = [(int(c.image_width), int(c.image_height)) for c in cams_all]
         # factored (default): the pseudo-GT stays in its separable form (rasterizer.HeatmapFactors) -- the fused step
         # evaluates the pixels it needs, the per-view loss constants come from the factors (sks_heatmap_totals), and no
@@ -813,15 +850,32 @@ class FrameBatchLoop:
         from the re-initialised Gaussians like general_utils.py:175-304, all frames in two launches per image size -- or
         ready `heatmaps` (F,V,C,H,W) / a list of F lists of V (C,H_v,W_v) planes.  `drop_masks`: optional (F,V,J) bool of
         dropped heat-map planes (heatmaps.draw_dropout per frame).  Everything is re-initialised in place, so captured
-        hipGraphs are replayed as they are."""
+        hipGraphs are replayed as they are.
+        `points=None`: the initial joints are the DLT triangulation of `poses_2d` (triangulation.triangulate_sequence),
+        written straight into `self.xyz` by one launch on the current stream, in front of the heat-map factors that read
+        them: detections already on the device never touch the host.  `drop_masks` are then also the DLT's
+        `valid = ~drop_masks` -- a dropped plane is a detection the caller does not trust --, and a joint kept in fewer than
+        two views has no triangulation: it starts as NaN.  Ready `heatmaps` carry no detections: refused."""
         from .heatmaps import generate_heatmaps, heatmap_factors
+        from .triangulation import triangulate_sequence
         F, V, P = self.F, self.V, self.P
         if self.factored and heatmaps is not None:
             raise ValueError("ready heat-map planes need FrameBatchLoop(..., factored=False)")
         with torch.no_grad():
-            pts = points if torch.is_tensor(points) else torch.as_tensor(np.asarray(points))
-            if tuple(pts.shape) != (F, P, 3):
-                raise ValueError(f"points must be (F,P,3) = {(F, P, 3)}, got {tuple(pts.shape)}")
+            if points is None:
+                if poses_2d is None:
+                    raise ValueError("new_scenes(points=None) triangulates the initial joints from poses_2d: give poses_2d "
+                                     "(ready heatmaps do not carry the detections)")
+                if self._proj is None:
+                    raise ValueError("new_scenes(points=None): the cameras carry no K / R / T to build projection matrices from")
+                p2d_dlt = torch.as_tensor(poses_2d, device=self.device)
+                if p2d_dlt.dim() != 4 or tuple(p2d_dlt.shape[:3]) != (F, V, P) or p2d_dlt.shape[3] < 2:
+                    raise ValueError(f"poses_2d must be (F,V,J,2) = {(F, V, P, 2)}, got {tuple(p2d_dlt.shape)}")
+                poses_2d = p2d_dlt[..., :2]
+            else:
+                pts = points if torch.is_tensor(points) else torch.as_tensor(np.asarray(points))
+                if tuple(pts.shape) != (F, P, 3):
+                    raise ValueError(f"points must be (F,P,3) = {(F, P, 3)}, got {tuple(pts.shape)}")
             if self._es is not None:
                 # a frame still running may yet write its flag from work enqueued before: let it drain first (once every
                 # frame has stopped, nothing writes a flag any more, and the next frames start at once)
@@ -829,7 +883,11 @@ class FrameBatchLoop:
                     torch.cuda.current_stream(self.device).synchronize()
                 self._es_flags_np[:] = 0
                 self._es_state.zero_()
-            self.xyz.copy_(pts.to(device=self.device, dtype=torch.float32))
+            if points is None:
+                keep = None if drop_masks is None else ~torch.as_tensor(drop_masks).to(device=self.device, dtype=torch.bool)
+                triangulate_sequence(self._proj, p2d_dlt, valid=None if keep is None else keep.reshape(F, V, P), out=self.xyz)
+            else:
+                self.xyz.copy_(pts.to(device=self.device, dtype=torch.float32))
             self.scaling.copy_(self._init[0].expand(F, P, 3))
             self.rotation.copy_(self._init[1].expand(F, P, 4))
             self.opacity.copy_(self._init[2].expand(F, P, 1))
@@ -953,26 +1011,34 @@ class FrameBatchLoop:
             self.step_group(parameters_untouched=chained)
             chained = True
 
-    def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25):
+    def _next_batch(self, pts, p2d, b, initial=None):
+        """new_scenes for the frames b .. b + F of a sequence (a short last batch is filled up by repeating its final
+        frame); `pts` None: triangulated from the detections.  `initial` (N,P,3): receives the batch's initial joints."""
+        N, F = p2d.shape[0], self.F
+        if b + F <= N:      # a full batch: views of the inputs, no gather
+            self.new_scenes(None if pts is None else pts[b:b + F], poses_2d=p2d[b:b + F])
+        else:
+            idx = [min(b + i, N - 1) for i in range(F)]
+            self.new_scenes(None if pts is None else pts[idx], poses_2d=p2d[idx])
+        if initial is not None:
+            initial[b:min(b + F, N)] = self.xyz[:min(F, N - b)]
+
+    def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, return_initial=False):
         """The reference's outer loop over the frames of a sequence (train.py:74-99) F frames at a time: `points`
         (N,P,3) initial joints and `poses_2d` (N,V,J,2) detections of N frames -> (N,P,3) optimised joints.  A last batch
         with fewer than F frames is filled up by repeating its final frame (frames are independent: the filler changes
-        nothing and is dropped)."""
-        pts = points if torch.is_tensor(points) else torch.as_tensor(np.asarray(points))
-        p2d = poses_2d if torch.is_tensor(poses_2d) else torch.as_tensor(np.asarray(poses_2d))
-        N, F = pts.shape[0], self.F
-        if p2d.shape[0] != N:
-            raise ValueError(f"{N} frames of points, {p2d.shape[0]} of detections")
+        nothing and is dropped).  `points=None`: every batch's initial joints are triangulated from its detections on
+        the device (new_scenes); `poses_2d` may be a device tensor and is then never copied to the host.
+        `return_initial=True`: returns (joints, initial joints), both (N,P,3) on the device."""
+        pts, p2d, N = _sequence_inputs(points, poses_2d)
+        F = self.F
         out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
+        initial = torch.empty_like(out) if return_initial else None
         for b in range(0, N, F):
-            if b + F <= N:
-                self.new_scenes(pts[b:b + F], poses_2d=p2d[b:b + F])
-            else:
-                idx = [min(b + i, N - 1) for i in range(F)]
-                self.new_scenes(pts[idx], poses_2d=p2d[idx])
+            self._next_batch(pts, p2d, b, initial)
             res = self.run(iterations, groups_per_graph)
             out[b:min(b + F, N)] = res[:min(F, N - b)]
-        return out
+        return (out, initial) if return_initial else out
 
 
 class FramePipeline:
@@ -995,37 +1061,35 @@ class FramePipeline:
         self.F, self.P = self.loops[0].F, self.loops[0].P
         self.stopped_at = None       # early stopping: (N,) int64 of the last optimize_sequence, 0 = ran to the end
 
-    def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, interleave=100):
+    def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, interleave=100,
+                          return_initial=False):
         """(N,P,3) initial joints + (N,V,J,2) detections -> (N,P,3) optimised joints (train.py:74-99 over the frames).
         The loops' graph launches are issued round-robin, `interleave` iterations at a time, so that every stream always
-        has work queued; a last batch with fewer than `frames` frames is padded by repeating its final frame."""
-        pts = points if torch.is_tensor(points) else torch.as_tensor(np.asarray(points))
-        p2d = poses_2d if torch.is_tensor(poses_2d) else torch.as_tensor(np.asarray(poses_2d))
-        N, F, S = pts.shape[0], self.F, len(self.loops)
-        if p2d.shape[0] != N:
-            raise ValueError(f"{N} frames of points, {p2d.shape[0]} of detections")
+        has work queued; a last batch with fewer than `frames` frames is padded by repeating its final frame.
+        `points=None`: every batch's initial joints are triangulated from its detections by one launch on the batch's own
+        stream (FrameBatchLoop.new_scenes), behind whatever the caller's stream did to `poses_2d`; detections given as a
+        device tensor are never copied to the host.  `return_initial=True`: returns (joints, initial joints)."""
+        pts, p2d, N = _sequence_inputs(points, poses_2d)
+        F, S = self.F, len(self.loops)
         out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
+        initial = torch.empty_like(out) if return_initial else None
         cur = torch.cuda.current_stream(self.device)
         starts = list(range(0, N, F))
         if self.loops[0]._es is not None:
             self.stopped_at = torch.zeros(N, dtype=torch.int64, device=self.device)
             for st in self.streams:
                 st.wait_stream(cur)
-            self._sequence_es(pts, p2d, out, starts, iterations, groups_per_graph, interleave)
+            self._sequence_es(pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial)
             for st in self.streams:
                 cur.wait_stream(st)
-            return out
+            return (out, initial) if return_initial else out
         for st in self.streams:
             st.wait_stream(cur)                      # inputs and `out` were produced on the caller's stream
         for w in range(0, len(starts), S):
             active = list(zip(self.loops, self.streams, starts[w:w + S]))
             for fb, st, b in active:
                 with torch.cuda.stream(st):
-                    if b + F <= N:      # a full batch: views of the inputs, no gather
-                        fb.new_scenes(pts[b:b + F], poses_2d=p2d[b:b + F])
-                    else:
-                        idx = [min(b + i, N - 1) for i in range(F)]
-                        fb.new_scenes(pts[idx], poses_2d=p2d[idx])
+                    fb._next_batch(pts, p2d, b, initial)
             for k in range(0, iterations, max(int(interleave), 1)):
                 for fb, st, b in active:
                     with torch.cuda.stream(st):
@@ -1035,13 +1099,13 @@ class FramePipeline:
                     out[b:min(b + F, N)] = fb.xyz[:min(F, N - b)]
         for st in self.streams:
             cur.wait_stream(st)
-        return out
+        return (out, initial) if return_initial else out
 
-    def _sequence_es(self, pts, p2d, out, starts, iterations, groups_per_graph, interleave):
+    def _sequence_es(self, pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial=None):
         """optimize_sequence with early stopping: every stream keeps its own batch and takes the next one as soon as its
         batch is done -- all frames stopped (seen in the pinned flags, without waiting) or `iterations` enqueued -- instead
         of waiting for the other streams' batches.  Results and stopping iterations are copied on the batch's stream."""
-        N, F = pts.shape[0], self.F
+        N, F = p2d.shape[0], self.F
         pending = iter(starts)
 
         def take(fb, st):
@@ -1049,11 +1113,7 @@ class FramePipeline:
             if b is None:
                 return None
             with torch.cuda.stream(st):
-                if b + F <= N:
-                    fb.new_scenes(pts[b:b + F], poses_2d=p2d[b:b + F])
-                else:
-                    idx = [min(b + i, N - 1) for i in range(F)]
-                    fb.new_scenes(pts[idx], poses_2d=p2d[idx])
+                fb._next_batch(pts, p2d, b, initial)
             return [fb, st, b, 0]
 
         step = max(int(interleave), 1)
