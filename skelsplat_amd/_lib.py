@@ -33,18 +33,37 @@ def SKS_BIN_GROUPS(n):
 
 _vp, _i, _u, _f, _sz = C.c_void_p, C.c_int, C.c_uint, C.c_float, C.c_size_t
 
+# The three entry points whose calls rasterizer.py records and replays: (parameter name, ctype) as in include/skelsplat_hip.h
+# (tests/test_cpu.py holds the tables to it).  A slot of a recorded argument block is addressed through FWD / BWD / FWD_BWD below.
+_CAMERAS = (("V", _i), ("P", _i), ("C", _i), ("W", _i), ("H", _i), ("viewmatrix", _vp), ("projmatrix", _vp),
+            ("tanfovx", _vp), ("tanfovy", _vp))
+_GAUSSIANS = (("means3D", _vp), ("features", _vp), ("opacities", _vp), ("scales", _vp), ("rotations", _vp),
+              ("cov3D_precomp", _vp), ("scale_modifier", _f), ("flags", _u))
+_UPSTREAM = (("dL_dout_color", _vp), ("dL_dout_invdepth", _vp), ("accum", _vp))
+_GRADS = (("dL_dmeans3D", _vp), ("dL_dmeans2D", _vp), ("dL_dopacity", _vp), ("dL_dscales", _vp), ("dL_drotations", _vp),
+          ("dL_dcov3D", _vp), ("dL_dfeatures", _vp), ("dL_dmeans3D_mean", _vp))
+_FORWARD_IO = (("out_color", _vp), ("out_invdepth", _vp), ("radii", _vp), ("geom", _vp), ("binning", _vp),
+               ("bin_capacity", _sz), ("num_rendered_dev", _vp))
+FORWARD_PARAMS = _CAMERAS + _GAUSSIANS + _FORWARD_IO + (("final_T", _vp), ("n_contrib", _vp), ("stream", _vp))
+BACKWARD_PARAMS = _CAMERAS + (("bg", _vp),) + _GAUSSIANS + (("radii", _vp), ("geom", _vp), ("binning", _vp), ("bin_capacity", _sz)) \
+    + _UPSTREAM + _GRADS + (("stream", _vp),)
+FORWARD_BACKWARD_PARAMS = _CAMERAS + _GAUSSIANS + _FORWARD_IO + (("bg", _vp),) + _UPSTREAM + _GRADS \
+    + (("stream", _vp), ("aux_stream", _vp), ("fb_flags", _u))
+
+FWD, BWD, FWD_BWD = ({name: i for i, (name, _) in enumerate(params)}      # parameter name -> slot
+                     for params in (FORWARD_PARAMS, BACKWARD_PARAMS, FORWARD_BACKWARD_PARAMS))
+# sks_forward_backward's block from the two calls' records, BY NAME: the forward record's slot if sks_forward has the name, else the
+# backward record's; None = in neither, the caller sets it per call.
+FWD_BWD_SOURCES = tuple(("fwd", FWD[n]) if n in FWD else ("bwd", BWD[n]) if n in BWD else None for n in FWD_BWD)
+
 # symbol -> (restype, argtypes); mirrors include/skelsplat_hip.h (tests check every declared symbol is exported)
 SIGNATURES = {
     "sks_last_error": (C.c_char_p, []),
     "sks_version": (_i, []),
     "sks_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
-    "sks_forward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _u,
-                         _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
-    "sks_backward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _u,
-                          _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sks_forward_backward": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _u,
-                                  _vp, _vp, _vp, _vp, _vp, _sz, _vp,
-                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u]),
+    "sks_forward": (_i, [ct for _, ct in FORWARD_PARAMS]),
+    "sks_backward": (_i, [ct for _, ct in BACKWARD_PARAMS]),
+    "sks_forward_backward": (_i, [ct for _, ct in FORWARD_BACKWARD_PARAMS]),
     "sks_mark_visible": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "sks_mean_views": (_i, [_i, _i, _vp, _i, _vp, _vp]),
     "sks_export_lists": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp]),

@@ -4,8 +4,10 @@ plus the batched multi-view entry points the MI355X loop uses.
 
 "DGR/" = submodules/diff-gaussian-rasterization-h36m/ of the reference.
 """
+from collections import namedtuple
 from typing import NamedTuple, Optional
 
+import operator
 import os
 import weakref
 
@@ -67,10 +69,9 @@ class Workspace:
 
     def __init__(self):
         self._t = {}
-        self._plans = {}     # "fwd" / "bwd" -> the last call's recorded C-ABI argument list (see _plan_key)
+        self._plans = {}     # "fwd" / "bwd" -> the last call's record (_FwdRecord / _BwdRecord)
         self._aux = {}
         self._pending_join = None     # device whose second stream still holds a forward_backward_views(join=False) backward
-        self._tuned = {}     # recorded forward's key -> the tuner's pick for it (tune())
 
     def aux_stream(self, dev_index):
         """The second stream forward_backward_views runs the backward on (created on first use, one per device)."""
@@ -101,7 +102,22 @@ class Workspace:
         whose step holds a collective wants every rank to issue the same number of steps) with device synchronisations in between
         (once, before a long loop); the candidates are interleaved round-robin.
         The pick also becomes the default of later Workspace recordings of the same shape.  Returns (best, {candidate: us})."""
-        return _workspace_tune(self, step_fn, TUNE_CANDIDATES if candidates is None else candidates, reps, rounds, confirm)
+        plan = self._plans.get("fwd")
+        if plan is None or torch.cuda.is_current_stream_capturing():
+            return None, {}
+        candidates = TUNE_CANDIDATES if candidates is None else candidates
+        args, dev_index = plan.args, plan.dev_index
+        base = args[_F_FLAGS] & ~_FILL_BITS
+
+        def set_bits(bits):
+            args[_F_FLAGS] = base | bits
+        times = _time_candidates(set_bits, step_fn, candidates, reps, rounds, dev_index)
+        best, med = _pick(times, candidates, set_bits, step_fn, reps, dev_index, confirm)
+        set_bits(_tune_flag_bits(best))
+        key = (dev_index, *(args[_lib.FWD[n]] for n in ("V", "P", "C", "W", "H")), "workspace")
+        _FILL_TUNE[key] = _tune_flag_bits(best)
+        _FILL_TUNE_LOG[key] = {tune_name(c): round(v, 2) for c, v in med.items()}
+        return best, med
 
     def settle(self):
         """A forward_backward_views(join=False) whose caller never joined: the next call through this workspace makes the join
@@ -128,12 +144,38 @@ def _sig(t):
     return (t.data_ptr(), t.shape)
 
 
-def _replay(fn, args, dev_index):
-    """Issue a recorded call on the CURRENT stream of the tensors' device.  The host side of a step matters here: the
-    H36M step is ~78 us of kernels, and building two ~30-argument ctypes calls from tensors (validation, data_ptr,
-    current_stream, device guard) was ~60 us of Python per step -- host-bound on a slow box.  A recorded call is one
-    tuple comparison and one ctypes call."""
-    args[-1] = torch._C._cuda_getCurrentRawStream(dev_index)
+# The records of replayed calls.  Their field ORDER is part of the surface: bench.py writes the flags word of the live list between
+# calls, `Workspace._plans["fwd"][2][_lib.FWD["flags"]]`.  key: _fwd_key / _bwd_key of the recorded call; keep: what the pointers in
+# `args` belong to; args: the live argument block (_lib.FORWARD_PARAMS / BACKWARD_PARAMS) the next replay launches with; result: what
+# every replay returns, (color, invdepth, radii, state) / the gradient dictionary; cap_check: None, or how a binned forward's arena is
+# checked (_replay_cap_prepare): counts = the synchronous check's pinned pair (_sync_counts), None when replays are lazy (_lazy_probe).
+_CapCheck = namedtuple("_CapCheck", "counts capacity shape_key")
+_FwdRecord = namedtuple("_FwdRecord", "key keep args dev_index result cap_check")      # Workspace._plans["fwd"]
+_BwdRecord = namedtuple("_BwdRecord", "key keep args dev_index result")                # Workspace._plans["bwd"]
+# An entry of the autograd path's `plans`: the validated block of a call whose tensors are fresh every call (a replay patches their
+# pointers into a copy).  shape: (V, P, C, H, W, gbytes, flags) of a forward, (V, P, C, has_scales, has_rotations) of a backward.
+_Block = namedtuple("_Block", "args dev_index dev shape")
+
+# Slots of the recorded blocks that are addressed after the recording: the layouts live in _lib, by parameter name.
+_F_V, _F_FLAGS, _F_COLOR, _F_INVDEPTH, _F_RADII, _F_GEOM, _F_NUM_RENDERED = (
+    _lib.FWD[n] for n in ("V", "flags", "out_color", "out_invdepth", "radii", "geom", "num_rendered_dev"))
+_B_RADII, _B_GEOM, _B_DL_COLOR, _B_DL_INVDEPTH = (_lib.BWD[n] for n in ("radii", "geom", "dL_dout_color", "dL_dout_invdepth"))
+_GRAD_SLOTS = tuple((k, _lib.BWD[n]) for k, n in (      # gradient dictionary key -> sks_backward's slot
+    ("means3D", "dL_dmeans3D"), ("means2D", "dL_dmeans2D"), ("opacities", "dL_dopacity"), ("scales", "dL_dscales"),
+    ("rotations", "dL_drotations"), ("cov3D", "dL_dcov3D"), ("features", "dL_dfeatures")))
+_FB_STREAM, _FB_AUX_STREAM, _FB_FLAGS = (_lib.FWD_BWD[n] for n in ("stream", "aux_stream", "fb_flags"))
+# sks_forward_backward's block as ONE gather (_lib.FWD_BWD_SOURCES) from forward block + backward block; slots no record has pick the
+# forward's stream slot: like `stream` itself they are set per call
+_FB_GATHER = operator.itemgetter(*(_lib.FWD["stream"] if src is None else src[1] + (len(_lib.FWD) if src[0] == "bwd" else 0)
+                                   for src in _lib.FWD_BWD_SOURCES))
+
+
+def _replay(fn, args, dev_index, stream_slot=-1):
+    """Issue a recorded call on the CURRENT stream of the tensors' device (`stream` is the last parameter of sks_forward and
+    sks_backward).  The host side of a step matters here: the H36M step is ~78 us of kernels, and building two ~30-argument ctypes
+    calls from tensors (validation, data_ptr, current_stream, device guard) was ~60 us of Python per step -- host-bound on a slow
+    box.  A recorded call is one tuple comparison and one ctypes call."""
+    args[stream_slot] = torch._C._cuda_getCurrentRawStream(dev_index)
     if torch._C._cuda_getDevice() == dev_index:
         return fn(*args)
     with torch.cuda.device(dev_index):
@@ -153,6 +195,23 @@ def _f32c(t, name):
     if t.dtype != torch.float32:
         raise RuntimeError(f"skelsplat_amd: `{name}` must be float32 (got {t.dtype})")
     return t.contiguous()
+
+
+def _f32c_params(means3D, features, opacities, scales, rotations, cov3D_precomp):
+    """The parameter tensors of a call as contiguous fp32 ROCm tensors (None = not provided)."""
+    return (_f32c(means3D, "means3D"), _f32c(features, "features"), _f32c(opacities, "opacities"), _f32c(scales, "scales"),
+            _f32c(rotations, "rotations"), _f32c(cov3D_precomp, "cov3D_precomp"))
+
+
+def _grad_dict(new, V, P, C, has_scales, has_rotations, want_features):
+    """The gradient dictionary of a backward: per-view (V,P,..) fp32 tensors from the allocator `new(name, *shape)`."""
+    return dict(means3D=new("m3", V, P, 3), means2D=new("m2", V, P, 3), opacities=new("op", V, P, 1), cov3D=new("cov", V, P, 6),
+                scales=new("sc", V, P, 3) if has_scales else None, rotations=new("rot", V, P, 4) if has_rotations else None,
+                features=new("feat", V, P, C) if want_features else None)
+
+
+def _fresh(fill, dev):      # _grad_dict's allocator of fresh tensors (fill: torch.empty / torch.zeros)
+    return lambda name, *shape: fill(shape, dtype=torch.float32, device=dev)
 
 
 _VIEW_CACHE = {}     # ViewBatch.from_settings
@@ -200,8 +259,10 @@ class ViewBatch:
         vm, pm = rs.viewmatrix, rs.projmatrix
         key = (vm.data_ptr(), vm._version, pm.data_ptr(), pm._version, rs.tanfovx, rs.tanfovy, rs.image_width, rs.image_height)
         hit = _VIEW_CACHE.get(key)
-        if hit is not None and hit[1]() is vm and hit[2]() is pm:
-            return hit[0]
+        if hit is not None:
+            vb, vm_ref, pm_ref = hit
+            if vm_ref() is vm and pm_ref() is pm:
+                return vb
         if len(_VIEW_CACHE) > 256:
             _VIEW_CACHE.clear()
         vb = cls(vm, pm, [rs.tanfovx], [rs.tanfovy], rs.image_width, rs.image_height)
@@ -215,9 +276,12 @@ class ForwardState:
     __slots__ = ("views", "P", "C", "flags", "scale_modifier", "geom", "binning", "bin_capacity", "radii",
                  "num_rendered_dev", "frames", "plan_key", "chunks")
 
-    def __init__(self):
-        self.frames = 1
-        self.plan_key = None
+    def __init__(self, views, P, C, flags, scale_modifier, radii, geom=None, binning=None, bin_capacity=0, num_rendered_dev=None,
+                 frames=1):
+        self.views, self.P, self.C, self.flags, self.scale_modifier = views, P, C, flags, float(scale_modifier)
+        self.geom, self.binning, self.bin_capacity, self.radii, self.num_rendered_dev = geom, binning, bin_capacity, radii, num_rendered_dev
+        self.frames = frames    # geometry_views(frames=F): F independent frames' Gaussians, stacked
+        self.plan_key = None    # the autograd path: key of the forward's _Block in `plans`
         self.chunks = None      # more than SKS_MAX_CHANNELS channels: [(view, c0, c1, feature chunk, ForwardState of that call)]
 
 
@@ -241,10 +305,12 @@ def forward_views(views: ViewBatch, means3D, features, opacities, scales, rotati
             and features.numel() // means3D.shape[0] > _lib.SKS_MAX_CHANNELS:
         return _forward_views_wide(views, means3D, features, opacities, scales, rotations, cov3D_precomp, scale_modifier, antialiasing,
                                    clamp01, debug, force_binned, bin_capacity, want_aux, tune_flags, check_capacity)
-    if plans is not None and workspace is None and not want_aux:
-        pkey = _fwd_key(views, means3D, features, opacities, scales, rotations, cov3D_precomp, scale_modifier, antialiasing,
-                        clamp01, debug, force_binned, bin_capacity, tune_flags, check_capacity)
-        hit = plans.get(pkey)
+    if not want_aux and (workspace is not None or plans is not None):
+        # the same call as a recorded one (same tensors, same switches)?  Then the validated argument list is replayed as is.
+        key = _fwd_key(views, means3D, features, opacities, scales, rotations, cov3D_precomp, scale_modifier, antialiasing,
+                       clamp01, debug, force_binned, bin_capacity, tune_flags, check_capacity)
+    if key is not None and workspace is None:
+        hit = plans.get(key)
         if hit is not None:
             args_t, dev_index, dev, (V, P, C, H, W, gbytes, flags) = hit
             color = torch.empty((V, C, H, W), dtype=torch.float32, device=dev)
@@ -252,29 +318,23 @@ def forward_views(views: ViewBatch, means3D, features, opacities, scales, rotati
             radii = torch.empty((V, P), dtype=torch.int32, device=dev)
             geom = torch.empty((gbytes,), dtype=torch.uint8, device=dev)
             args = list(args_t)
-            args[17], args[18], args[19], args[20] = color.data_ptr(), invdepth.data_ptr(), radii.data_ptr(), geom.data_ptr()
+            args[_F_COLOR], args[_F_INVDEPTH], args[_F_RADII], args[_F_GEOM] = color.data_ptr(), invdepth.data_ptr(), radii.data_ptr(), geom.data_ptr()
             _lib.check(_replay(lib.sks_forward, args, dev_index), "sks_forward")
-            st = ForwardState()
-            st.views, st.P, st.C, st.flags, st.scale_modifier = views, P, C, flags, float(scale_modifier)
-            st.geom, st.binning, st.bin_capacity, st.radii, st.num_rendered_dev = geom, None, 0, radii, None
-            st.plan_key = pkey
+            st = ForwardState(views, P, C, flags, scale_modifier, radii, geom)
+            st.plan_key = key
             return color, invdepth, radii, st
     if workspace is not None:
         workspace.settle()
-    if workspace is not None and not want_aux:
-        # the same call as last time (same tensors, same switches)?  Then the validated argument list is replayed as is.
-        key = _fwd_key(views, means3D, features, opacities, scales, rotations, cov3D_precomp, scale_modifier, antialiasing,
-                       clamp01, debug, force_binned, bin_capacity, tune_flags, check_capacity)
+    if key is not None and workspace is not None:
         plan = workspace._plans.get("fwd")
-        if plan is not None and plan[0] == key:
-            _, _views, args, dev_index, result, cap_check = plan
+        if plan is not None and plan.key == key:
             _replay_cap_prepare(workspace, plan, check_capacity)
-            rc = _replay(lib.sks_forward, args, dev_index)
+            rc = _replay(lib.sks_forward, plan.args, plan.dev_index)
             if rc != 0:
                 del workspace._plans["fwd"]
             _lib.check(rc, "sks_forward")
             if _replay_cap_finish(workspace, plan, check_capacity):
-                return result
+                return plan.result
             # (the binning arena overflowed: the validating path below grows it and redoes)
     if views.mixed:
         raise RuntimeError("the dense forward writes one (V,C,H,W) tensor: all views of the batch must share the image size")
@@ -284,22 +344,16 @@ def forward_views(views: ViewBatch, means3D, features, opacities, scales, rotati
     if means3D.shape[0] == 0:   # DGR/rasterize_points.cu:88: nothing is rasterised, the outputs stay zero
         dev, V, W, H = means3D.device, views.V, views.W, views.H
         C = int(features.shape[-1])
-        st = ForwardState()
-        st.views, st.P, st.C, st.flags, st.scale_modifier = views, 0, C, 0, float(scale_modifier)
-        st.geom = st.binning = st.num_rendered_dev = None
-        st.bin_capacity, st.radii = 0, torch.zeros((V, 0), dtype=torch.int32, device=dev)
+        st = ForwardState(views, 0, C, 0, scale_modifier, torch.zeros((V, 0), dtype=torch.int32, device=dev))
         out = (torch.zeros((V, C, H, W), device=dev), torch.zeros((V, 1, H, W), device=dev), st.radii, st)
         if want_aux:
             out += (torch.ones((V, H, W), device=dev), torch.zeros((V, H, W), dtype=torch.int32, device=dev))
         return out
-    means3D = _f32c(means3D, "means3D")
+    means3D, features, opacities, scales, rotations, cov3D_precomp = _f32c_params(means3D, features, opacities, scales, rotations, cov3D_precomp)
     dev = means3D.device
     P = means3D.shape[0]
-    features = _f32c(features, "features")
     feat2 = features.reshape(P, -1)
     C = feat2.shape[1]
-    opacities = _f32c(opacities, "opacities")
-    scales, rotations, cov3D_precomp = _f32c(scales, "scales"), _f32c(rotations, "rotations"), _f32c(cov3D_precomp, "cov3D_precomp")
     V, W, H = views.V, views.W, views.H
     flags = (_lib.SKS_ANTIALIASING if antialiasing else 0) | (_lib.SKS_CLAMP01 if clamp01 else 0) | \
             (_lib.SKS_DEBUG_SYNC if debug else 0) | (_lib.SKS_FORCE_BINNED if force_binned else 0) | int(tune_flags) | _ENV_TUNE
@@ -364,31 +418,29 @@ def forward_views(views: ViewBatch, means3D, features, opacities, scales, rotati
                 return forward_views(views, means3D, features, opacities, scales, rotations, cov3D_precomp, scale_modifier,
                                      antialiasing, clamp01, debug, force_binned, int(need * 1.25) + 1024, want_aux, tune_flags,
                                      check_capacity, workspace)
-    st = ForwardState()
-    st.views, st.P, st.C, st.flags, st.scale_modifier = views, P, C, flags, float(scale_modifier)
-    st.geom, st.binning, st.bin_capacity, st.radii = geom, binning, cap, radii
-    st.num_rendered_dev = nrend[0] if isinstance(nrend, tuple) else nrend
+    st = ForwardState(views, P, C, flags, scale_modifier, radii, geom, binning, cap, nrend[0] if isinstance(nrend, tuple) else nrend)
     if want_aux:
         return color, invdepth, radii, st, final_T, n_contrib
-    if plans is not None and workspace is None and not binned and P and all(sg is not False for sg in pkey[1:7]):
-        if len(plans) > 64:
-            plans.clear()
-        # (the block keeps the parameter tensors' pointers: `keep` holds the tensors so that the pointers stay theirs)
-        plans[pkey] = (list(args), dev.index, dev, (V, P, C, H, W, gbytes, flags))
-        plans[("keep", pkey)] = (views, means3D, feat2, opacities, scales, rotations, cov3D_precomp)
-        st.plan_key = pkey
-    if key is not None and all(sg is not False for sg in key[1:7]) and not torch.cuda.is_current_stream_capturing():
+    if key is None or not _recordable(key):
+        return color, invdepth, radii, st
+    if workspace is None:
+        if not binned and P:
+            if len(plans) > 64:
+                plans.clear()
+            # (the block keeps the parameter tensors' pointers: `keep` holds the tensors so that the pointers stay theirs)
+            plans[key] = _Block(list(args), dev.index, dev, (V, P, C, H, W, gbytes, flags))
+            plans[("keep", key)] = (views, means3D, feat2, opacities, scales, rotations, cov3D_precomp)
+            st.plan_key = key
+    elif not torch.cuda.is_current_stream_capturing():
         # (the tensors the pointers belong to stay alive in `keep`; the views object is held so that its id stays its own)
         keep = (means3D, feat2, opacities, scales, rotations, cov3D_precomp)
         cap_check = None
         if binned:
             # (the binning buffer needs no clearing between calls: every counter is written before it is read)
             args = list(args)
-            if check_capacity is True:
-                cap_check = (nrend, cap, cap_key)
-            elif check_capacity:
-                cap_check = (None, cap, cap_key)     # replays are lazy calls: each takes a probe buffer of the shape (_lazy_probe)
-        workspace._plans["fwd"] = (key, (views, keep), args, dev.index, (color, invdepth, radii, st), cap_check)
+            if check_capacity:      # (no counts: replays are lazy calls, each takes a probe buffer of the shape, _lazy_probe)
+                cap_check = _CapCheck(nrend if check_capacity is True else None, cap, cap_key)
+        workspace._plans["fwd"] = _FwdRecord(key, (views, keep), args, dev.index, (color, invdepth, radii, st), cap_check)
     return color, invdepth, radii, st
 
 
@@ -396,31 +448,32 @@ def _replay_cap_prepare(workspace, plan, check_capacity):
     """In front of a REPLAYED binned forward (forward_views, forward_backward_views): where this call's pair counts go.  Lazy modes:
     a pinned probe buffer of the shape (looking at earlier calls' counts first: raises when one of them overflowed its arena);
     synchronous check: the shape's pinned counts preset to "not written yet"."""
-    args, result, cap_check = plan[2], plan[4], plan[5]
+    args, cap_check = plan.args, plan.cap_check
     if cap_check is None:
         return
     if check_capacity is not True:
         try:
-            host = _lazy_probe(cap_check[2], cap_check[1])     # earlier calls' counts; a buffer for this call's (or None)
+            host = _lazy_probe(cap_check.shape_key, cap_check.capacity)     # earlier calls' counts; a buffer for this call's (or None)
         except RuntimeError:
             # the recorded call holds the overflowed arena: drop it, so that the next call takes the validating path
             # and allocates the grown one (`_BIN_CAP_HINT`)
             workspace._plans.pop("fwd", None)
             raise
-        args[23] = None if host is None else host.data_ptr()
-        result[3].num_rendered_dev = host
+        args[_F_NUM_RENDERED] = None if host is None else host.data_ptr()
+        _color, _invdepth, _radii, st = plan.result
+        st.num_rendered_dev = host
     else:
-        cap_check[0][1][:args[0]] = -1       # (the pinned counts of the synchronous check: "not written yet")
+        _host, view = cap_check.counts
+        view[:args[_F_V]] = -1       # (the pinned counts of the synchronous check: "not written yet")
 
 
 def _replay_cap_finish(workspace, plan, check_capacity):
     """Behind it: True = the call stands.  False (synchronous check only): its arena was too small -- the recorded call is dropped,
     the caller takes the validating path, which grows the arena and redoes the forward."""
-    args, dev_index, cap_check = plan[2], plan[3], plan[5]
+    cap_check = plan.cap_check
     if cap_check is None or check_capacity is not True:
         return True       # (lazy: the counts of this call are looked at when the next one comes in)
-    nr, pcap, ckey = cap_check
-    if _wait_counts(nr, args[0], dev_index) <= pcap:
+    if _wait_counts(cap_check.counts, plan.args[_F_V], plan.dev_index) <= cap_check.capacity:
         return True
     workspace._plans.pop("fwd", None)
     return False
@@ -446,10 +499,8 @@ def _forward_views_wide(views, means3D, features, opacities, scales, rotations, 
     color = torch.empty((V, C, H, W), dtype=torch.float32, device=dev)
     invdepth = torch.empty((V, 1, H, W), dtype=torch.float32, device=dev)
     radii = torch.empty((V, P), dtype=torch.int32, device=dev)
-    st = ForwardState()
-    st.views, st.P, st.C, st.scale_modifier, st.flags = views, P, C, float(scale_modifier), 0
-    st.geom = st.binning = st.num_rendered_dev = None
-    st.bin_capacity, st.radii, st.chunks = 0, radii, []
+    st = ForwardState(views, P, C, 0, scale_modifier, radii)
+    st.chunks = []
     for v in range(V):
         one = ViewBatch(views.viewmatrix[v:v + 1], views.projmatrix[v:v + 1], [views.tanfovx[v]], [views.tanfovy[v]], W, H)
         for c0 in range(0, C, M):
@@ -470,11 +521,8 @@ def _backward_views_wide(st, means3D, opacities, scales, rotations, cov3D_precom
     dev, V, P, C = means3D.device, st.views.V, st.P, st.C
     dL_dcolor = _f32c(dL_dcolor, "dL_dout_color").reshape(V, C, st.views.H, st.views.W)
     dL_dinvdepth = _f32c(dL_dinvdepth, "dL_dout_invdepth")
-    z = lambda *s_: torch.zeros(s_, dtype=torch.float32, device=dev)
-    out = dict(means3D=z(V, P, 3), means2D=z(V, P, 3), opacities=z(V, P, 1), cov3D=z(V, P, 6),
-               scales=z(V, P, 3) if scales is not None and scales.numel() else None,
-               rotations=z(V, P, 4) if rotations is not None and rotations.numel() else None,
-               features=z(V, P, C) if want_dfeatures else None)
+    out = _grad_dict(_fresh(torch.zeros, dev), V, P, C, scales is not None and scales.numel(),
+                     rotations is not None and rotations.numel(), want_dfeatures)
     bgC = _bg_channels(bg, C, dev)
     for v, c0, c1, fc, sub in st.chunks:
         g = backward_views(sub, means3D, fc, opacities, scales, rotations, cov3D_precomp, dL_dcolor[v:v + 1, c0:c1],
@@ -490,15 +538,21 @@ def _backward_views_wide(st, means3D, opacities, scales, rotations, cov3D_precom
 
 def _fwd_key(views, means3D, features, opacities, scales, rotations, cov3D_precomp, scale_modifier, antialiasing, clamp01, debug,
              force_binned, bin_capacity, tune_flags, check_capacity):
-    return (id(views), _sig(means3D), _sig(features), _sig(opacities), _sig(scales), _sig(rotations), _sig(cov3D_precomp),
+    return (id(views), (_sig(means3D), _sig(features), _sig(opacities), _sig(scales), _sig(rotations), _sig(cov3D_precomp)),
             scale_modifier, antialiasing, clamp01, debug, force_binned, bin_capacity, tune_flags, check_capacity)
 
 
 def _bwd_key(st, means3D, features, opacities, scales, rotations, cov3D_precomp, dL_dcolor, dL_dinvdepth, bg, want_dfeatures,
              tune_flags, want_mean, out_means3D, stream):
-    return (id(st), _sig(means3D), _sig(features), _sig(opacities), _sig(scales), _sig(rotations), _sig(cov3D_precomp),
-            _sig(dL_dcolor), _sig(dL_dinvdepth), None if bg is None else (id(bg), bg._version), want_dfeatures, tune_flags,
+    return (id(st), (_sig(means3D), _sig(features), _sig(opacities), _sig(scales), _sig(rotations), _sig(cov3D_precomp),
+                     _sig(dL_dcolor), _sig(dL_dinvdepth)), None if bg is None else (id(bg), bg._version), want_dfeatures, tune_flags,
             want_mean, None if out_means3D is None else out_means3D.data_ptr(), stream)   # (the partial-sum scratch is per stream)
+
+
+def _recordable(key):
+    """Every tensor of the call is one whose pointer a record may hold: a key's second element is the tuple of its tensors' _sig."""
+    _owner, sigs, *_switches = key
+    return all(sg is not False for sg in sigs)
 
 
 _SCRATCH_BYTES = {}
@@ -522,7 +576,8 @@ def _sync_counts(cap_key):
     if hit is None:
         host = torch.empty((cap_key[1] + 1,), dtype=torch.int32).pin_memory()
         hit = _SYNC_PROBE[cap_key] = (host, host.numpy())
-    hit[1][:] = -1
+    _host, view = hit
+    view[:] = -1
     return hit
 
 
@@ -534,7 +589,7 @@ def _wait_counts(probe, V, dev_index):
     running forward.  The check stays synchronous and exact (an arena that was too small is grown and the forward redone before
     anything is returned); what it no longer costs is the idle GPU between two calls (bench.py stress: default mode vs "auto")."""
     import time
-    view = probe[1]
+    _host, view = probe
     t0 = time.perf_counter()
     while int(view[:V].min()) < 0:
         if time.perf_counter() - t0 > 0.2:      # (counts that never arrive: wait for the stream, look once more)
@@ -611,19 +666,19 @@ def _bg_channels(bg, C, dev):
         return None
     key = (id(bg), C, str(dev))
     hit = _BG_CACHE.get(key)
-    if hit is not None and (hit[0]() is not bg or hit[1] != bg._version):
-        hit = None     # another tensor at a recycled id, or modified in place since
-    if hit is None:
-        if len(_BG_CACHE) > 64:
-            _BG_CACHE.clear()
-        bgC = None
-        if bool((bg != 0).any()):
-            bgC = torch.zeros(C, dtype=torch.float32, device=dev)
-            k = min(C, bg.numel())
-            bgC[:k] = bg.reshape(-1)[:k].to(device=dev, dtype=torch.float32)
-        hit = (weakref.ref(bg), bg._version, bgC)
-        _BG_CACHE[key] = hit
-    return hit[2]
+    if hit is not None:
+        bg_ref, version, bgC = hit
+        if bg_ref() is bg and version == bg._version:     # (else: another tensor at a recycled id, or modified in place since)
+            return bgC
+    if len(_BG_CACHE) > 64:
+        _BG_CACHE.clear()
+    bgC = None
+    if bool((bg != 0).any()):
+        bgC = torch.zeros(C, dtype=torch.float32, device=dev)
+        k = min(C, bg.numel())
+        bgC[:k] = bg.reshape(-1)[:k].to(device=dev, dtype=torch.float32)
+    _BG_CACHE[key] = (weakref.ref(bg), bg._version, bgC)
+    return bgC
 
 
 def backward_views(st: ForwardState, means3D, features, opacities, scales, rotations, cov3D_precomp, dL_dcolor,
@@ -634,8 +689,7 @@ def backward_views(st: ForwardState, means3D, features, opacities, scales, rotat
     `out_means3D`: a contiguous fp32 (V,P,3) tensor to receive "means3D" (a view-sharded caller passes the rows of its
     all_gather shard: no copy between the backward and the exchange)."""
     lib = _lib.load()
-    key = None
-    pkey = None
+    key = pkey = None
     if st.chunks is not None:
         if want_mean or out_means3D is not None:
             raise RuntimeError("want_mean / out_means3D are not available beyond SKS_MAX_CHANNELS channels")
@@ -649,15 +703,14 @@ def backward_views(st: ForwardState, means3D, features, opacities, scales, rotat
                 want_dfeatures, tune_flags, stream)
         hit = plans.get(pkey)
         if hit is not None:
-            args_t, dev_index, dev, (V, P, C), has_sr = hit
-            e = lambda *s_: torch.empty(s_, dtype=torch.float32, device=dev)
-            out = dict(means3D=e(V, P, 3), means2D=e(V, P, 3), opacities=e(V, P, 1), cov3D=e(V, P, 6),
-                       scales=e(V, P, 3) if has_sr[0] else None, rotations=e(V, P, 4) if has_sr[1] else None,
-                       features=e(V, P, C) if want_dfeatures else None)
+            args_t, dev_index, dev, shape = hit
+            out = _grad_dict(_fresh(torch.empty, dev), *shape, want_dfeatures)
             args = list(args_t)
-            args[18], args[19], args[22], args[23] = st.radii.data_ptr(), st.geom.data_ptr(), dL_dcolor.data_ptr(), _lib.ptr(dL_dinvdepth)
-            args[25], args[26], args[27] = out["means3D"].data_ptr(), out["means2D"].data_ptr(), out["opacities"].data_ptr()
-            args[28], args[29], args[30], args[31] = _lib.ptr(out["scales"]), _lib.ptr(out["rotations"]), out["cov3D"].data_ptr(), _lib.ptr(out["features"])
+            args[_B_RADII], args[_B_GEOM], args[_B_DL_COLOR], args[_B_DL_INVDEPTH] = \
+                st.radii.data_ptr(), st.geom.data_ptr(), dL_dcolor.data_ptr(), _lib.ptr(dL_dinvdepth)
+            for k, i in _GRAD_SLOTS:
+                g = out[k]
+                args[i] = None if g is None else g.data_ptr()
             rc = _replay(lib.sks_backward, args, dev_index)
             if rc != 0:
                 reset_scratch()
@@ -670,42 +723,29 @@ def backward_views(st: ForwardState, means3D, features, opacities, scales, rotat
         key = _bwd_key(st, means3D, features, opacities, scales, rotations, cov3D_precomp, dL_dcolor, dL_dinvdepth, bg,
                        want_dfeatures, tune_flags, want_mean, out_means3D, torch._C._cuda_getCurrentRawStream(st.geom.device.index))
         plan = workspace._plans.get("bwd")
-        if plan is not None and plan[0] == key:
-            _, _keep, args, dev_index, result = plan
-            rc = _replay(lib.sks_backward, args, dev_index)
+        if plan is not None and plan.key == key:
+            rc = _replay(lib.sks_backward, plan.args, plan.dev_index)
             if rc != 0:
                 reset_scratch()
                 del workspace._plans["bwd"]
             _lib.check(rc, "sks_backward")
-            return result
+            return plan.result
     if st.P == 0:
-        dev, V, C = means3D.device, st.views.V, st.C
-        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
-        empty = dict(means3D=z(V, 0, 3), means2D=z(V, 0, 3), opacities=z(V, 0, 1), cov3D=z(V, 0, 6), scales=z(V, 0, 3),
-                     rotations=z(V, 0, 4), features=z(V, 0, C) if want_dfeatures else None)
+        dev = means3D.device
+        empty = _grad_dict(_fresh(torch.zeros, dev), st.views.V, 0, st.C, True, True, want_dfeatures)
         if want_mean:
-            empty["means3D_mean"] = z(0, 3)
+            empty["means3D_mean"] = torch.zeros((0, 3), dtype=torch.float32, device=dev)
         return empty
-    means3D = _f32c(means3D, "means3D")
+    means3D, features, opacities, scales, rotations, cov3D_precomp = _f32c_params(means3D, features, opacities, scales, rotations, cov3D_precomp)
     dev = means3D.device
-    V, P, C = st.views.V, st.P, st.C
-    W, H = st.views.W, st.views.H
-    feat2 = _f32c(features, "features").reshape(P, -1)
-    opacities = _f32c(opacities, "opacities")
-    scales, rotations, cov3D_precomp = _f32c(scales, "scales"), _f32c(rotations, "rotations"), _f32c(cov3D_precomp, "cov3D_precomp")
-    dL_dcolor = _f32c(dL_dcolor, "dL_dout_color")
-    dL_dinvdepth = _f32c(dL_dinvdepth, "dL_dout_invdepth")
+    V, P, C, W, H = st.views.V, st.P, st.C, st.views.W, st.views.H
+    feat2 = features.reshape(P, -1)
+    dL_dcolor, dL_dinvdepth = _f32c(dL_dcolor, "dL_dout_color"), _f32c(dL_dinvdepth, "dL_dout_invdepth")
     if dL_dcolor.numel() != V * C * H * W:
         raise RuntimeError("dL_dout_color has the wrong number of elements")
     bgC = _bg_channels(bg, C, dev)
-    if workspace is None:
-        e = lambda name, *s: torch.empty(s, dtype=torch.float32, device=dev)
-    else:
-        e = lambda name, *s: workspace.get(("bwd", name), s, torch.float32, dev)
-    out = dict(means3D=e("m3", V, P, 3), means2D=e("m2", V, P, 3), opacities=e("op", V, P, 1), cov3D=e("cov", V, P, 6),
-               scales=e("sc", V, P, 3) if scales is not None else None,
-               rotations=e("rot", V, P, 4) if rotations is not None else None,
-               features=e("feat", V, P, C) if want_dfeatures else None)
+    e = _fresh(torch.empty, dev) if workspace is None else lambda name, *s: workspace.get(("bwd", name), s, torch.float32, dev)
+    out = _grad_dict(e, V, P, C, scales is not None, rotations is not None, want_dfeatures)
     if want_mean:
         out["means3D_mean"] = e("m3mean", P, 3)
     if out_means3D is not None:
@@ -727,11 +767,11 @@ def backward_views(st: ForwardState, means3D, features, opacities, scales, rotat
     if rc != 0:
         reset_scratch()
     _lib.check(rc, "sks_backward")
-    if key is not None and all(sg is not False for sg in key[1:9]) and not torch.cuda.is_current_stream_capturing():
+    if key is not None and _recordable(key) and not torch.cuda.is_current_stream_capturing():
         keep = (st, means3D, feat2, opacities, scales, rotations, cov3D_precomp, dL_dcolor, dL_dinvdepth, bg, bgC, accum)
-        workspace._plans["bwd"] = (key, keep, args, dev.index, out)
+        workspace._plans["bwd"] = _BwdRecord(key, keep, args, dev.index, out)
     if pkey is not None and st.binning is None:
-        plans[pkey] = (list(args), dev.index, dev, (V, P, C), (scales is not None, rotations is not None))
+        plans[pkey] = _Block(list(args), dev.index, dev, (V, P, C, scales is not None, rotations is not None))
         plans[("keep", pkey)] = (bg, bgC, accum)
     return out
 
@@ -759,29 +799,24 @@ def forward_backward_views(views: ViewBatch, means3D, features, opacities, scale
     workspace.settle()
     fplan, bplan = workspace._plans.get("fwd"), workspace._plans.get("bwd")
     if fplan is not None and bplan is not None:
-        dev_index = fplan[3]
+        dev_index = fplan.dev_index
         fkey = _fwd_key(views, means3D, features, opacities, scales, rotations, cov3D_precomp, scale_modifier, antialiasing, clamp01,
                         False, force_binned, bin_capacity, tune_flags, check_capacity)
-        if fplan[0] == fkey:
-            st = fplan[4][3]
+        if fplan.key == fkey:
+            _color, _invdepth, _radii, st = fplan.result
             bkey = _bwd_key(st, means3D, features, opacities, scales, rotations, cov3D_precomp, dL_dcolor, dL_dinvdepth, bg,
                             want_dfeatures, tune_flags, want_mean, out_means3D, torch._C._cuda_getCurrentRawStream(dev_index))
-            if bplan[0] == bkey:
+            if bplan.key == bkey:
                 aux = workspace.aux_stream(dev_index) if (overlap or not join) else None
                 # (a binned forward keeps its capacity check: the probe buffer / pinned counts go in front of the call, the
                 # synchronous check's wait behind it -- on the binned path the library runs the backward of a view group beside
                 # the forward of the next one, SKS_BIN_GROUPS)
                 _replay_cap_prepare(workspace, fplan, check_capacity)
-                fa, ba = fplan[2], bplan[2]
                 no_join = overlap and not join
-                args = fa[:24] + [ba[9], ba[22], ba[23], ba[24]] + ba[25:33] + [None, aux.cuda_stream if overlap else None,
-                                                                             _lib.SKS_FB_NO_JOIN if no_join else 0]
-                args[-3] = torch._C._cuda_getCurrentRawStream(dev_index)
-                if torch._C._cuda_getDevice() == dev_index:
-                    rc = lib.sks_forward_backward(*args)
-                else:
-                    with torch.cuda.device(dev_index):
-                        rc = lib.sks_forward_backward(*args)
+                # (rebuilt from the LIVE blocks on every call: Workspace.tune and callers change the forward record's flags between calls)
+                args = list(_FB_GATHER(fplan.args + bplan.args))
+                args[_FB_AUX_STREAM], args[_FB_FLAGS] = aux.cuda_stream if overlap else None, _lib.SKS_FB_NO_JOIN if no_join else 0
+                rc = _replay(lib.sks_forward_backward, args, dev_index, _FB_STREAM)
                 if rc != 0:
                     reset_scratch()
                     workspace._plans.pop("fwd", None), workspace._plans.pop("bwd", None)
@@ -791,7 +826,7 @@ def forward_backward_views(views: ViewBatch, means3D, features, opacities, scale
                 if not join and not overlap:     # (the gradients were produced on the current stream: aux must see them)
                     aux.wait_stream(torch.cuda.current_stream(dev_index))
                 if _replay_cap_finish(workspace, fplan, check_capacity):
-                    return fplan[4] + (bplan[4],)
+                    return fplan.result + (bplan.result,)
                 workspace.settle()     # the arena overflowed (synchronous check): the two calls below grow it and redo the step
     out = forward_views(views, means3D, features, opacities, scales, rotations, cov3D_precomp, scale_modifier, antialiasing, clamp01,
                         force_binned=force_binned, bin_capacity=bin_capacity, check_capacity=check_capacity,
@@ -874,32 +909,6 @@ def _pick(times, candidates, set_bits=None, step_fn=None, reps=8, dev_index=None
 
 
 TUNE_WARM = 12      # untimed calls in front of a tuner's measurement (_time_candidates)
-
-
-def _workspace_tune(workspace, step_fn, candidates=TUNE_CANDIDATES, reps=8, rounds=3, confirm=True):
-    """Workspace.tune (see there)."""
-    plan = workspace._plans.get("fwd")
-    if plan is None or torch.cuda.is_current_stream_capturing():
-        return None, {}
-    args, dev_index = plan[2], plan[3]
-    base = args[16] & ~_FILL_BITS
-
-    def set_bits(bits):
-        args[16] = base | bits
-    times = _time_candidates(set_bits, step_fn, candidates, reps, rounds, dev_index)
-    best, med = _pick(times, candidates, set_bits, step_fn, reps, dev_index, confirm)
-    set_bits(_tune_flag_bits(best))
-    V, P, C, W, H = args[0], args[1], args[2], args[3], args[4]
-    key = (dev_index, V, P, C, W, H, "workspace")
-    _FILL_TUNE[key] = _tune_flag_bits(best)
-    _FILL_TUNE_LOG[key] = {tune_name(c): round(v, 2) for c, v in med.items()}
-    workspace._tuned[plan[0]] = best
-    return best, med
-
-
-def autotune_fill_passes(workspace, step_fn, candidates=TUNE_CANDIDATES, reps=8, rounds=3):
-    """Former name of Workspace.tune (kept for callers of the round-5 API)."""
-    return _workspace_tune(workspace, step_fn, candidates, reps, rounds)
 
 
 def tune_forward(views, means3D, features, opacities, scales, rotations, cov3D_precomp, scale_modifier=1.0, antialiasing=False,
@@ -1283,7 +1292,7 @@ def geometry_views(views: ViewBatch, means3D, C, opacities, scales, rotations, c
     frames > 1: `views` holds frames x Vf views (frame-major) and the parameter tensors are stacked (frames, P, ..):
     view f*Vf + j renders frame f's Gaussians (see sks_loop_fused_step)."""
     lib = _lib.load()
-    means3D = _f32c(means3D, "means3D")
+    means3D, _, opacities, scales, rotations, cov3D_precomp = _f32c_params(means3D, None, opacities, scales, rotations, cov3D_precomp)
     dev = means3D.device
     frames = int(frames)
     if frames < 1 or views.V % frames:
@@ -1291,8 +1300,6 @@ def geometry_views(views: ViewBatch, means3D, C, opacities, scales, rotations, c
     if frames > 1 and (means3D.dim() != 3 or means3D.shape[0] != frames):
         raise ValueError(f"frames = {frames} needs parameters stacked (frames, P, ..); means3D is {tuple(means3D.shape)}")
     P = means3D.shape[-2]
-    opacities = _f32c(opacities, "opacities")
-    scales, rotations, cov3D_precomp = _f32c(scales, "scales"), _f32c(rotations, "rotations"), _f32c(cov3D_precomp, "cov3D_precomp")
     V, W, H = views.V, views.W, views.H
     flags = (_lib.SKS_ANTIALIASING if antialiasing else 0) | (_lib.SKS_RAW_PARAMS if raw_params else 0)
     gbytes, _, _ = _lib.scratch_bytes(V, max(P, 1), C, W, H, 0)
@@ -1307,11 +1314,7 @@ def geometry_views(views: ViewBatch, means3D, C, opacities, scales, rotations, c
                               _lib.ptr(cov3D_precomp), float(scale_modifier), flags, radii.data_ptr(), geom.data_ptr(),
                               views.wh, frames, torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, "sks_geometry")
-    st = ForwardState()
-    st.frames = frames
-    st.views, st.P, st.C, st.flags, st.scale_modifier = views, P, C, flags, float(scale_modifier)
-    st.geom, st.binning, st.bin_capacity, st.radii, st.num_rendered_dev = geom, None, 0, radii, None
-    return st
+    return ForwardState(views, P, C, flags, scale_modifier, radii, geom, frames=frames)
 
 
 def _check_heatmaps(views, C, stats):
@@ -1377,18 +1380,13 @@ def backward_fused_loss(st: ForwardState, stats: GtStats, means3D, features, opa
     """Render + clamp + masked-L2 + backward on the covered tiles only.  Returns (grads dict of (V,P,..) UNSCALED
     gradients, loss_sums (V,2) f64 = per-view {S, N}); the true gradient is grads / N_v, loss_v = S_v / N_v."""
     lib = _lib.load()
-    means3D = _f32c(means3D, "means3D")
+    means3D, features, opacities, scales, rotations, cov3D_precomp = _f32c_params(means3D, features, opacities, scales, rotations, cov3D_precomp)
     dev = means3D.device
-    V, P, C = st.views.V, st.P, st.C
-    W, H = st.views.W, st.views.H
+    V, P, C, W, H = st.views.V, st.P, st.C, st.views.W, st.views.H
     _check_heatmaps(st.views, C, stats)
-    feat2 = _f32c(features, "features").reshape(P, -1)
-    opacities = _f32c(opacities, "opacities")
-    scales, rotations, cov3D_precomp = _f32c(scales, "scales"), _f32c(rotations, "rotations"), _f32c(cov3D_precomp, "cov3D_precomp")
+    feat2 = features.reshape(P, -1)
     bgC = _bg_channels(bg, C, dev)
-    e = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
-    out = dict(means3D=e(V, P, 3), means2D=e(V, P, 3), opacities=e(V, P, 1), cov3D=e(V, P, 6),
-               scales=e(V, P, 3) if scales is not None else None, rotations=e(V, P, 4) if rotations is not None else None)
+    out = _grad_dict(_fresh(torch.empty, dev), V, P, C, scales is not None, rotations is not None, False)
     if sums_out is None:
         sums = torch.empty((V, 2), dtype=torch.float64, device=dev)
     else:

@@ -206,6 +206,34 @@ def test_library_exports_every_declared_symbol():
         _lib.scratch_bytes(4, 17, 64, 1000, 1000)                   # C > SKS_MAX_CHANNELS -> error string, not a crash
 
 
+def test_recorded_layouts_are_the_headers():
+    """The three entry points whose argument blocks rasterizer.py records and replays are addressed by parameter name through the
+    tables of skelsplat_amd._lib: the tables are the header's prototypes, name for name, type for type and in order; the one-call
+    block is assembled from the two records by name with exactly `aux_stream` and `fb_flags` left to the caller; and `flags` is
+    slot 16 of sks_forward, the position bench.py writes."""
+    import ctypes
+    from skelsplat_amd import _lib
+    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "skelsplat_hip.h")).read(), flags=re.S)     # (a comment holds ");")
+    scalars = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
+    for symbol, table in (("sks_forward", _lib.FORWARD_PARAMS), ("sks_backward", _lib.BACKWARD_PARAMS),
+                          ("sks_forward_backward", _lib.FORWARD_BACKWARD_PARAMS)):
+        proto = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % symbol, hdr).group(1)
+        declared = []
+        for param in proto.split(","):
+            ctype, name = re.fullmatch(r"\s*(.*?)(\w+)\s*", param, flags=re.S).groups()
+            declared.append((name, ctypes.c_void_p if "*" in ctype else scalars[ctype.strip()]))
+        assert declared == list(table), symbol
+        assert _lib.SIGNATURES[symbol] == (ctypes.c_int, [ct for _, ct in table])
+    assert len(_lib.FWD_BWD_SOURCES) == len(_lib.FORWARD_BACKWARD_PARAMS) == 39
+    assert [n for n, src in zip(_lib.FWD_BWD, _lib.FWD_BWD_SOURCES) if src is None] == ["aux_stream", "fb_flags"]
+    for name, src in zip(_lib.FWD_BWD, _lib.FWD_BWD_SOURCES):
+        if src is not None:
+            assert src == (("fwd", _lib.FWD[name]) if name in _lib.FWD else ("bwd", _lib.BWD[name])), name
+    assert [n for n in _lib.FWD if n not in _lib.FWD_BWD] == ["final_T", "n_contrib"]
+    assert _lib.FWD["flags"] == 16
+    assert _lib.FWD["stream"] == len(_lib.FWD) - 1 and _lib.BWD["stream"] == len(_lib.BWD) - 1      # (rasterizer._replay's default)
+
+
 def test_product_refuses_cpu_tensors_and_bad_arguments():
     from diff_gaussian_rasterization_h36m import GaussianRasterizationSettings, GaussianRasterizer
     import gaussian_renderer

@@ -1312,17 +1312,17 @@ def test_tuned_workspace_changes_no_bit_on_any_path(device):
         step(), step()
         best, med = ws.tune(step, reps=4, rounds=2)
         assert best in R.TUNE_CANDIDATES and set(med) == set(R.TUNE_CANDIDATES) and all(v > 0 for v in med.values())
-        flags = ws._plans["fwd"][2][16]
+        flags = ws._plans["fwd"].args[_lib.FWD["flags"]]
         assert (flags >> 8) & 0xff == best & 0xff and bool(flags & _lib.SKS_NO_NT_STORES) == bool(best & R.PLAIN_STORES)
         assert R._FILL_TUNE[(views.viewmatrix.device.index, 2, c.P, c.feat.shape[1], 1000, 96, "workspace")] == R._tune_flag_bits(best)
         for forced in (best, 1, 5, 7, R.PLAIN_STORES | 2, R.PLAIN_STORES | 4):     # (passes per block x store kind)
-            ws._plans["fwd"][2][16] = (flags & ~R._FILL_BITS) | R._tune_flag_bits(forced)
+            ws._plans["fwd"].args[_lib.FWD["flags"]] = (flags & ~R._FILL_BITS) | R._tune_flag_bits(forced)
             out = step()
             same(out, out[4], (form, forced), g0b if form == "binned_one_call" else None)
     # a Workspace recorded AFTER the measurement starts from the pick
     ws2 = R.Workspace()
     out = R.forward_backward_views(views, *args, dL, workspace=ws2)
-    assert ws2._plans["fwd"][2][16] & R._FILL_BITS == R._FILL_TUNE[(views.viewmatrix.device.index, 2, c.P, c.feat.shape[1], 1000, 96, "workspace")]
+    assert ws2._plans["fwd"].args[_lib.FWD["flags"]] & R._FILL_BITS == R._FILL_TUNE[(views.viewmatrix.device.index, 2, c.P, c.feat.shape[1], 1000, 96, "workspace")]
     same(out, out[4], "recorded after tuning")
     assert R.Workspace().tune(lambda: None) == (None, {})        # (nothing recorded: nothing to tune)
     # fresh outputs: an explicit measurement, and the autograd path's own on first sight of a shape

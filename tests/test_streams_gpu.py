@@ -350,12 +350,13 @@ _GROUPS_CHILD = textwrap.dedent("""
     torch.cuda.synchronize()
     same(g2, ref["g2"], True, "backward_views on the one call's state")
     # sks_backward through the state's recorded plan, dL swapped for dL2, into fresh tensors
-    a = list(ws._plans["bwd"][2])
+    a = list(ws._plans["bwd"].args)
     g3 = {k: torch.full_like(v, float("nan")) for k, v in ref["g2"].items() if v is not None}
-    a[22] = dL2.data_ptr()
-    for i, k in zip(range(25, 32), ("means3D", "means2D", "opacities", "scales", "rotations", "cov3D", "features")):
-        a[i] = g3[k].data_ptr()
-    a[32] = None
+    a[_lib.BWD["dL_dout_color"]] = dL2.data_ptr()
+    for k, name in (("means3D", "dL_dmeans3D"), ("means2D", "dL_dmeans2D"), ("opacities", "dL_dopacity"), ("scales", "dL_dscales"),
+                    ("rotations", "dL_drotations"), ("cov3D", "dL_dcov3D"), ("features", "dL_dfeatures")):
+        a[_lib.BWD[name]] = g3[k].data_ptr()
+    a[_lib.BWD["dL_dmeans3D_mean"]] = None
     _lib.check(R._replay(_lib.load().sks_backward, a, 0), "sks_backward")
     torch.cuda.synchronize()
     same(g3, ref["g2"], True, "sks_backward through the recorded plan")
