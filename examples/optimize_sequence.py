@@ -2,7 +2,9 @@
 """A whole synthetic SEQUENCE through the hot path, the way the reference's train.py walks a dataset (one frame after the
 other, train.py:74-99) -- but many frames per launch: noisy 2D detections of N frames -> DLT initial guesses -> 500
 iterations of the multi-view loop for every frame (loop.FramePipeline) -> MPJPE per frame.
-python examples/optimize_sequence.py [--frames 64] [--per-launch 16] [--streams 2] [--iters 500] [--init host|device]
+python examples/optimize_sequence.py [--frames 64] [--per-launch 16] [--streams 2] [--iters 500] [--init host|device] [--rigs R]
+--rigs R: the frames cycle through R jittered ring rigs (SyntheticScene seeds 0 .. R-1), as a dataset whose scenes bring their own
+cameras does; one rigs.RigBank holds them on the device and every batch names its frames' rigs (rig_ids).
 --init host (default): the DLT runs on the host, frame by frame, and its points are uploaded; --init device: the detections
 go to the device once and every batch is triangulated there (FramePipeline.optimize_sequence(None, ...)); the timed region
 runs from the detections to the joints either way."""
@@ -29,31 +31,41 @@ def main():
     ap.add_argument("--streams", type=int, default=2)
     ap.add_argument("--iters", type=int, default=500)
     ap.add_argument("--init", choices=("host", "device"), default="host")
+    ap.add_argument("--rigs", type=int, default=1)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     sc = SyntheticScene(args.dataset, n_views=args.views, seed=0, device=dev)
+    rigs = [sc.cameras] + [SyntheticScene(args.dataset, n_views=args.views, seed=r, device=dev).cameras for r in range(1, args.rigs)]
+    rig_of = [f % args.rigs for f in range(args.frames)]
     rng = np.random.default_rng(1)
     # a moving skeleton: the template drifts and wobbles from frame to frame; detections carry 3 px of noise
     gt = np.stack([sc.pose_3d_gt + np.array([8.0 * f, 3.0 * f, 0.0]) + rng.normal(0, 5.0, sc.pose_3d_gt.shape)
                    for f in range(args.frames)])
-    p2d = np.stack([np.stack([project_points(c, gt[f]) + rng.normal(0, 3.0, (sc.n_points, 2)) for c in sc.cameras])
+    p2d = np.stack([np.stack([project_points(c, gt[f]) + rng.normal(0, 3.0, (sc.n_points, 2)) for c in rigs[rig_of[f]]])
                     for f in range(args.frames)]).astype(np.float32)
-    Pm = triangulation.projection_matrices(sc.cameras)
+    Pm = [triangulation.projection_matrices(rig) for rig in rigs]
 
     def host_init():
-        return np.stack([triangulation.triangulate_poses(Pm, p2d[f])[:, :3] for f in range(args.frames)]).astype(np.float32)
+        return np.stack([triangulation.triangulate_poses(Pm[rig_of[f]], p2d[f])[:, :3] for f in range(args.frames)]).astype(np.float32)
 
     gm = GaussianModel().create_from_points(host_init()[0], sc.spatial_lr_scale, sc.n_joints, scene_type=args.dataset, device=dev)
     gm.training_setup()
-    pipe = FramePipeline(gm, sc.cameras, frames=args.per_launch, streams=args.streams, dataset=args.dataset,
-                         accumulation_steps=args.views)
+    if args.rigs > 1:
+        from skelsplat_amd.rigs import RigBank
+        pipe = FramePipeline(gm, rigs=RigBank(rigs, dev), frames=args.per_launch, streams=args.streams, dataset=args.dataset,
+                             accumulation_steps=args.views)
+        ids = dict(rig_ids=torch.tensor(rig_of, dtype=torch.int32, device=dev))
+    else:
+        pipe = FramePipeline(gm, sc.cameras, frames=args.per_launch, streams=args.streams, dataset=args.dataset,
+                             accumulation_steps=args.views)
+        ids = {}
     if args.init == "device":
         p2d_dev = torch.as_tensor(p2d, device=dev)
-        run = lambda: pipe.optimize_sequence(None, p2d_dev, iterations=args.iters, return_initial=True)
+        run = lambda: pipe.optimize_sequence(None, p2d_dev, iterations=args.iters, return_initial=True, **ids)
     else:
         def run():
             init = host_init()
-            return pipe.optimize_sequence(init, p2d, iterations=args.iters), init
+            return pipe.optimize_sequence(init, p2d, iterations=args.iters, **ids), init
     run()                                                             # captures the hipGraphs
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -65,7 +77,7 @@ def main():
     e0 = np.mean([io.mpjpe(init[f], gt[f]) for f in range(args.frames)])
     e1 = np.mean([io.mpjpe(pred[f], gt[f]) for f in range(args.frames)])
     print(f"{args.dataset} V={args.views} {sc.W}x{sc.H}: {args.frames} frames x {args.iters} iterations in {dt * 1e3:.1f} ms "
-          f"({args.frames / dt:.0f} frames/s, {args.per_launch} frames per launch on {args.streams} streams); "
+          f"({args.frames / dt:.0f} frames/s, {args.per_launch} frames per launch on {args.streams} streams, {args.rigs} rig(s)); "
           f"mean MPJPE {e0:.2f} mm (DLT on the {args.init}) -> {e1:.2f} mm")
 
 

@@ -420,6 +420,61 @@ int sks_loop_fused_step_es(int V, int P, int C, int W, int H, const float* viewm
                            int* es_state, int es_window, float es_tolerance, int* es_host_flags /*pinned HOST frames or NULL*/,
                            void* stream);
 
+/* Frame batches whose frames are seen by DIFFERENT camera rigs (since sks_version 14).  The entry points above take the per-view
+ * scalars (tanfovx / tanfovy / view_wh) and the LR schedule as HOST arrays and hand them to their kernels by value, so a captured
+ * hipGraph holds them; the *_dv twins below read them from DEVICE memory, so that the cameras of a batch can be exchanged under a
+ * captured graph by writing a few buffers.
+ *  views_dev: 4 x SKS_MAX_VIEWS words on the device -- float tanfovx[SKS_MAX_VIEWS], float tanfovy[SKS_MAX_VIEWS],
+ *      int W_v[SKS_MAX_VIEWS], int H_v[SKS_MAX_VIEWS] --, entries [0, V) valid, every size within [1, W] x [1, H];
+ *  lr_sched_dev: frames x 5 doubles on the device, row f = frame f's schedule as {log lr_init, log lr_final, delay_mult, delay_steps,
+ *      max_steps} -- sks_loop_adam_step's five numbers with the two logarithms (log 0 = -inf) already taken, on the host;
+ *  sks_rig_select: fills both -- and the view / projection rows and K [R|t] -- for a batch of `frames` frames from a bank of R
+ *      rigs, all device memory: rig_ids (frames) ints; bank_viewmatrix / bank_projmatrix (R,V,16); bank_tan (R,V,2) = {tanfovx,
+ *      tanfovy}; slot_wh (V,2) = {W_j, H_j} of view slot j (the same in every rig); bank_proj (R,V,3,4) doubles or NULL (with
+ *      proj NULL); bank_sched (R,5) doubles, rows as lr_sched_dev's.  Frame f receives rig rig_ids[f]: viewmatrix / projmatrix
+ *      rows [f*V, (f+1)*V), the same entries of views_dev, proj (frames,V,3,4) -- what sks_triangulate takes with rig_stride =
+ *      V * 12 -- and row f of lr_sched_dev.  One launch on `stream`, nothing synchronises.  An id outside [0, R) writes nothing
+ *      for its frame and stores 1 + f into *error_word (device or pinned host memory, zeroed by the caller; one of them when
+ *      several frames do);
+ *  sks_geometry_dv, sks_heatmap_factors_dv, sks_heatmap_totals_dv: as the entry points they are named after, views_dev in place
+ *      of tanfovx / tanfovy / view_wh;
+ *  sks_loop_fused_step_dv, sks_loop_fused_step_es_dv: views_dev in place of tanfovx / tanfovy, lr_sched_dev in place of lr_sched
+ *      (the tail workgroup of frame f reads row f).  view_wh stays a HOST argument with the same sizes as views_dev holds: the
+ *      compositing backward reads nothing but the sizes, which are fixed per view slot, and keeps them in its argument segment.
+ *  Results are bit-identical to the by-value entry points given the same numbers. */
+int sks_rig_select(int R, int V, int frames, const int* rig_ids, const float* bank_viewmatrix, const float* bank_projmatrix,
+                   const float* bank_tan, const int* slot_wh, const double* bank_proj, const double* bank_sched,
+                   float* viewmatrix, float* projmatrix, void* views_dev, double* proj, double* lr_sched_dev, int* error_word,
+                   void* stream);
+int sks_geometry_dv(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix, const void* views_dev,
+                    const float* means3D, const float* opacities, const float* scales, const float* rotations,
+                    const float* cov3D_precomp, float scale_modifier, unsigned flags, int* radii, void* geom, int frames,
+                    void* stream);
+int sks_heatmap_factors_dv(int V, int J, int W, int H, const float* means3D, const float* scales, const float* rotations,
+                           float scale_modifier, const float* poses_2d, const float* viewmatrix, const void* views_dev,
+                           float* row, float* col, float* cmin, float* den, int frames, void* stream);
+int sks_heatmap_totals_dv(int V, int J, int W, int H, const float* row, const float* col, const float* cmin, const float* den,
+                          const void* views_dev, double* gt_totals, void* stream);
+int sks_loop_fused_step_dv(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                           const void* views_dev, const float* features, float scale_modifier, unsigned flags, int* radii,
+                           void* geom, const float* gt, const double* gt_totals, void* accum, double* loss_sums, float* packed,
+                           float* slots, unsigned long long group_mask, int last_view, float* xyz, float* scaling,
+                           float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq, int* counters, int acc_steps,
+                           const double* lr_sched_dev, const double* lrs /*HOST 3*/, const double* adam /*HOST 3*/,
+                           float lambda_consistency, const int* limb /*HOST 8 or NULL*/,
+                           const int* view_wh /*HOST V x {W,H} or NULL*/, const size_t* gt_offsets /*HOST V or NULL*/, int frames,
+                           const float* const* hm_factors /*HOST 4 or NULL*/, void* stream);
+int sks_loop_fused_step_es_dv(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                              const void* views_dev, const float* features, float scale_modifier, unsigned flags, int* radii,
+                              void* geom, const float* gt, const double* gt_totals, void* accum, double* loss_sums,
+                              float* packed, float* slots, unsigned long long group_mask, int last_view, float* xyz,
+                              float* scaling, float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq, int* counters,
+                              int acc_steps, const double* lr_sched_dev, const double* lrs /*HOST 3*/,
+                              const double* adam /*HOST 3*/, float lambda_consistency, const int* limb /*HOST 8 or NULL*/,
+                              const int* view_wh /*HOST V x {W,H} or NULL*/, const size_t* gt_offsets /*HOST V or NULL*/,
+                              int frames, const float* const* hm_factors /*HOST 4 or NULL*/, int* es_state, int es_window,
+                              float es_tolerance, int* es_host_flags /*pinned HOST frames or NULL*/, void* stream);
+
 /* Measurement hook used by bench.py (no reference counterpart; state per HOST THREAD, like the error text): while enabled, the dominant kernel of sks_forward
  * (kind 0: forward compositor) and of sks_backward (kind 1: backward compositor) is bracketed by hipEvents recorded
  * on the caller's stream (the small path's kernels carry the pair on their own dispatch, hipExtLaunchKernelGGL).  The low 16

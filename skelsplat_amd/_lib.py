@@ -56,6 +56,35 @@ FWD, BWD, FWD_BWD = ({name: i for i, (name, _) in enumerate(params)}      # para
 # backward record's; None = in neither, the caller sets it per call.
 FWD_BWD_SOURCES = tuple(("fwd", FWD[n]) if n in FWD else ("bwd", BWD[n]) if n in BWD else None for n in FWD_BWD)
 
+# The entry points that read per-view scalars and the LR schedule from DEVICE memory (frame batches over a rig bank), in the same
+# style: (parameter name, ctype) as in include/skelsplat_hip.h (tests/test_rigs_cpu.py holds the tables to it).
+_ull = C.c_ulonglong
+_VIEWS_DV = (("viewmatrix", _vp), ("projmatrix", _vp), ("views_dev", _vp))
+RIG_SELECT_PARAMS = (("R", _i), ("V", _i), ("frames", _i), ("rig_ids", _vp), ("bank_viewmatrix", _vp), ("bank_projmatrix", _vp),
+                     ("bank_tan", _vp), ("slot_wh", _vp), ("bank_proj", _vp), ("bank_sched", _vp), ("viewmatrix", _vp),
+                     ("projmatrix", _vp), ("views_dev", _vp), ("proj", _vp), ("lr_sched_dev", _vp), ("error_word", _vp),
+                     ("stream", _vp))
+GEOMETRY_DV_PARAMS = (("V", _i), ("P", _i), ("C", _i), ("W", _i), ("H", _i)) + _VIEWS_DV + (
+    ("means3D", _vp), ("opacities", _vp), ("scales", _vp), ("rotations", _vp), ("cov3D_precomp", _vp), ("scale_modifier", _f),
+    ("flags", _u), ("radii", _vp), ("geom", _vp), ("frames", _i), ("stream", _vp))
+HEATMAP_FACTORS_DV_PARAMS = (("V", _i), ("J", _i), ("W", _i), ("H", _i), ("means3D", _vp), ("scales", _vp), ("rotations", _vp),
+                             ("scale_modifier", _f), ("poses_2d", _vp), ("viewmatrix", _vp), ("views_dev", _vp), ("row", _vp),
+                             ("col", _vp), ("cmin", _vp), ("den", _vp), ("frames", _i), ("stream", _vp))
+HEATMAP_TOTALS_DV_PARAMS = (("V", _i), ("J", _i), ("W", _i), ("H", _i), ("row", _vp), ("col", _vp), ("cmin", _vp), ("den", _vp),
+                            ("views_dev", _vp), ("gt_totals", _vp), ("stream", _vp))
+_STEP_DV = (("V", _i), ("P", _i), ("C", _i), ("W", _i), ("H", _i)) + _VIEWS_DV + (
+    ("features", _vp), ("scale_modifier", _f), ("flags", _u), ("radii", _vp), ("geom", _vp), ("gt", _vp), ("gt_totals", _vp),
+    ("accum", _vp), ("loss_sums", _vp), ("packed", _vp), ("slots", _vp), ("group_mask", _ull), ("last_view", _i), ("xyz", _vp),
+    ("scaling", _vp), ("rotation", _vp), ("opacity", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("counters", _vp),
+    ("acc_steps", _i), ("lr_sched_dev", _vp), ("lrs", _vp), ("adam", _vp), ("lambda_consistency", _f), ("limb", _vp),
+    ("view_wh", _vp), ("gt_offsets", _vp), ("frames", _i), ("hm_factors", _vp))
+LOOP_FUSED_STEP_DV_PARAMS = _STEP_DV + (("stream", _vp),)
+LOOP_FUSED_STEP_ES_DV_PARAMS = _STEP_DV + (("es_state", _vp), ("es_window", _i), ("es_tolerance", _f), ("es_host_flags", _vp),
+                                           ("stream", _vp))
+DV_PARAMS = {"sks_rig_select": RIG_SELECT_PARAMS, "sks_geometry_dv": GEOMETRY_DV_PARAMS,
+             "sks_heatmap_factors_dv": HEATMAP_FACTORS_DV_PARAMS, "sks_heatmap_totals_dv": HEATMAP_TOTALS_DV_PARAMS,
+             "sks_loop_fused_step_dv": LOOP_FUSED_STEP_DV_PARAMS, "sks_loop_fused_step_es_dv": LOOP_FUSED_STEP_ES_DV_PARAMS}
+
 # symbol -> (restype, argtypes); mirrors include/skelsplat_hip.h (tests check every declared symbol is exported)
 SIGNATURES = {
     "sks_last_error": (C.c_char_p, []),
@@ -97,6 +126,7 @@ SIGNATURES = {
                                     _vp, C.c_ulonglong, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp,
                                     _vp, _i, _vp, _vp, _i, _f, _vp, _vp]),
     "sks_triangulate": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    **{name: (_i, [ct for _, ct in params]) for name, params in DV_PARAMS.items()},
     "sks_prof_enable": (_i, [_i]),
     "sks_prof_spin": (_i, [C.c_double, _vp]),
     "sks_prof_read": (_i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),

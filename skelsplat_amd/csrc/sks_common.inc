@@ -102,6 +102,22 @@ struct ViewOff {
     unsigned long long off[SKS_MAX_VIEWS];
 };
 // host: fills both; view_wh (V x {W,H}) / plane_off (V) may be NULL = uniform W x H.  Returns false on a bad size.
+// The same record where it lives in DEVICE memory (the *_dv entry points: the table sks_rig_select fills, laid out as a ViewTan):
+// `vt.x[v]` reads alike from either, so the geometry code is written once and the kernels' _dv twins differ in this argument only.
+// A captured hipGraph then holds a pointer, not the cameras' scalars.  sched: the tail's per-frame LR schedule rows
+// (sks_loop_fused_step_dv's lr_sched_dev), nullptr elsewhere.
+struct ViewTanDev {
+    const float* x;
+    const float* y;
+    const int* w;
+    const int* h;
+    const double* sched;
+};
+inline ViewTanDev views_dev_from(const void* views_dev, const double* sched = nullptr)
+{
+    const ViewTan* t = (const ViewTan*)views_dev;
+    return ViewTanDev{ t->x, t->y, t->w, t->h, sched };   // (addresses only: nothing is read on the host)
+}
 inline bool fill_views(ViewTan& vt, ViewOff* vo, int V, int C, int W, int H, const float* tanfovx, const float* tanfovy,
                        const int* view_wh, const size_t* plane_off)
 {

@@ -173,8 +173,8 @@ __device__ __forceinline__ void geom_bwd_fetch(const GeomBwdArgs& a, int v, int 
 }
 
 // part 2: the reference's formulas; n_view = the view's mask count N_v (fused-loss mode, else unused)
-template <bool PRE = false>
-__device__ __forceinline__ void geom_bwd_finish(const GeomBwdArgs& a, const ViewTan& vt, int v, int idx, const float (&g)[NACC],
+template <bool PRE = false, class VT = ViewTan>
+__device__ __forceinline__ void geom_bwd_finish(const GeomBwdArgs& a, const VT& vt, int v, int idx, const float (&g)[NACC],
                                                 double n_view, const GeomBwdIn* pre = nullptr)
 {
     const size_t o = (size_t)v * a.P + idx;
@@ -541,8 +541,10 @@ __global__ void k_mean_views(int V, int P, const float* __restrict__ dmeans3D, f
 // exactly as k_loop_adam does for one scene: a cut inside the group shortens the step (views, winning view, iterations,
 // the LR schedule's iteration); a frame that stopped at an earlier launch leaves at once and writes nothing.
 // ------------------------------------------------------------------------------------------------------------
-template <bool ES = false>
-__global__ __launch_bounds__(256) void k_step_tail(GeomBwdArgs ga, ViewTan vt, sksloop::AdamArgs aa, int V, Geom g, int* radii)
+// VT = ViewTan: the per-view scalars by value.  VT = ViewTanDev (sks_loop_fused_step_dv): they are read from the device table, and
+// frame f's LR schedule is row f of vt.sched instead of the one schedule in `aa`.
+template <bool ES = false, class VT = ViewTan>
+__global__ __launch_bounds__(256) void k_step_tail(GeomBwdArgs ga, VT vt, sksloop::AdamArgs aa, int V, Geom g, int* radii)
 {
     __shared__ float s_xyz[256 * 3];
     __shared__ float s_hyp[6];
@@ -559,6 +561,15 @@ __global__ __launch_bounds__(256) void k_step_tail(GeomBwdArgs ga, ViewTan vt, s
         aa.grads += (size_t)vb * P * 11; aa.slots += (size_t)vb * P * 3;
         aa.xyz += (size_t)f * P * 3; aa.scaling += (size_t)f * P * 3; aa.rotation += (size_t)f * P * 4; aa.opacity += (size_t)f * P;
         aa.m += (size_t)f * P * 11; aa.vv += (size_t)f * P * 11; aa.counters += 2 * f;
+    }
+    if constexpr (std::is_same<VT, ViewTanDev>::value) {
+        // the frame's own schedule (frames of different rigs: lr = position_lr x that rig's extent), {log lr_init, log lr_final,
+        // delay_mult, delay_steps, max_steps}: the logarithms were taken on the host, as fill_adam_args takes them
+        const double* r = vt.sched + 5 * (size_t)f;
+        aa.log_lr_init = r[0]; aa.log_lr_final = r[1]; aa.lr_delay_mult = r[2];
+        aa.lr_delay_steps = (int)r[3]; aa.lr_max_steps = (int)r[4];
+        aa.lr_init = r[0] == -INFINITY ? 0.0 : 1.0;      // (read only by the "schedule switched off" test: both end points zero)
+        aa.lr_final = r[1] == -INFINITY ? 0.0 : 1.0;
     }
     if constexpr (ES) {
         aa.es_state += (size_t)f * (2 + 2 * aa.es_window);

@@ -4,7 +4,8 @@
 // geometry forward: preprocessCUDA, DGR/cuda_rasterizer/forward.cu:153-273 (+ in_frustum auxiliary.h:151-176)
 // ------------------------------------------------------------------------------------------------------------
 // one (view, Gaussian) pair; returns the tile rect (all zero when culled or !live)
-__device__ __forceinline__ uint4 geom_fwd_one(int P, const ViewTan& vt, const float* __restrict__ vms,
+template <class VT>
+__device__ __forceinline__ uint4 geom_fwd_one(int P, const VT& vt, const float* __restrict__ vms,
                                               const float* __restrict__ pms, const float* __restrict__ means,
                                               const float* __restrict__ opac, const float* __restrict__ scales,
                                               const float* __restrict__ rots, const float* __restrict__ cov3Dp,
@@ -157,6 +158,27 @@ __global__ __launch_bounds__(SKS_GEOM_COVER_THREADS > 256 ? SKS_GEOM_COVER_THREA
         uint32_t* out = g.cover + ((size_t)v * (cover_planes ? C + 1 : 1) + (cover_planes ? pz : 0)) * pw;
         for (int i = threadIdx.x; i < pw; i += blockDim.x) out[i] = s_cov[i];
     }
+}
+
+// sks_geometry_dv: the geometry pass of the fused-loss path (no cover rows, no binning) with the per-view scalars read from the
+// device table
+__global__ __launch_bounds__(256) void k_geom_fwd_dv(int P, ViewTanDev vt, const float* __restrict__ vms, const float* __restrict__ pms,
+                                                      const float* __restrict__ means, const float* __restrict__ opac,
+                                                      const float* __restrict__ scales, const float* __restrict__ rots,
+                                                      const float* __restrict__ cov3Dp, float smod, unsigned flags, Geom g,
+                                                      int* __restrict__ radii, int vf)
+{
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int v = blockIdx.y;
+    if (vf > 0) {   // (frames batched: as k_geom_fwd)
+        const int fr = v / vf;
+        means += (size_t)fr * P * 3;
+        opac += (size_t)fr * P;
+        if (scales) scales += (size_t)fr * P * 3;
+        if (rots) rots += (size_t)fr * P * 4;
+        if (cov3Dp) cov3Dp += (size_t)fr * P * 6;
+    }
+    geom_fwd_one(P, vt, vms, pms, means, opac, scales, rots, cov3Dp, smod, flags, g, radii, v, idx, idx < P);
 }
 
 __global__ void k_mark_visible(int P, const float* __restrict__ means, const float* __restrict__ V,

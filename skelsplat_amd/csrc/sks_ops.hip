@@ -386,6 +386,18 @@ struct HmTan {
     int w[SKS_MAX_VIEWS], h[SKS_MAX_VIEWS];   // per-view image size (<= the W, H strides of row / col)
 };
 
+struct HmTanDev {   // the same scalars in device memory (the *_dv entry points: the ViewTan table sks_rig_select fills)
+    const float* x;
+    const float* y;
+    const int* w;
+    const int* h;
+};
+inline HmTanDev hm_tan_dev(const void* views_dev)
+{
+    const HmTan* t = (const HmTan*)views_dev;     // (same layout as the rasterizer's ViewTan; addresses only)
+    return HmTanDev{ t->x, t->y, t->w, t->h };
+}
+
 __device__ __forceinline__ double block_sum_d(double v, double* s_red)
 {
     v = wave_sum_d(v);
@@ -439,10 +451,12 @@ __device__ __forceinline__ float block_minmax(float v, bool want_max, float* s_r
                     : fminf(fminf(s_red[0], s_red[1]), fminf(s_red[2], s_red[3]));
 }
 
+// (TAN = HmTan: the per-view scalars by value; HmTanDev, sks_heatmap_factors_dv: read from the device table)
+template <class TAN = HmTan>
 __global__ __launch_bounds__(256) void k_heatmap_factors(int J, int W, int H, const float* __restrict__ means,
                                                           const float* __restrict__ scales, const float* __restrict__ rots,
                                                           float scale_modifier, const float* __restrict__ poses_2d,
-                                                          const float* __restrict__ viewmatrix, HmTan tan,
+                                                          const float* __restrict__ viewmatrix, TAN tan,
                                                           float* __restrict__ row, float* __restrict__ col,
                                                           float* __restrict__ cmin, float* __restrict__ den, int vf)
 {
@@ -514,7 +528,8 @@ __global__ __launch_bounds__(256) void k_heatmap_factors(int J, int W, int H, co
 // integers (exact in any order), the sums are accumulated in fp64 like k_heatmaps' own and combined across blocks in
 // fixed point (order-independent: reproducible bit for bit).
 // ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_heatmap_totals(int J, int Ws, int Hs, HmTan sz, const float* __restrict__ row,
+template <class TAN = HmTan>
+__global__ __launch_bounds__(256) void k_heatmap_totals(int J, int Ws, int Hs, TAN sz, const float* __restrict__ row,
                                                          const float* __restrict__ col, const float* __restrict__ cmin,
                                                          const float* __restrict__ den, double* __restrict__ totals)
 {
@@ -555,6 +570,41 @@ __global__ __launch_bounds__(256) void k_heatmap_totals(int J, int Ws, int Hs, H
         if (Sb != 0.0) atomicAdd(reinterpret_cast<unsigned long long*>(&totals[2 * v]), (unsigned long long)llrint(Sb * 4294967296.0));
         if (Nb != 0.0) atomicAdd(&totals[2 * v + 1], Nb);   // (all-zero workgroups send nothing: see k_heatmaps)
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// sks_rig_select: frame f of a batch is seen by rig rig_ids[f] of a bank of R rigs (V cameras each, the same image size per
+// view slot in every rig).  One workgroup per frame copies that rig's rows into the batch's persistent buffers: view and
+// projection rows, the ViewTan table the *_dv kernels read (tan from the bank, sizes per slot), K [R|t] for the triangulation
+// and the LR schedule row.  An id outside [0, R) writes nothing for its frame and reports 1 + the frame through `err`.
+// ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_rig_select(int R, int V, const int* __restrict__ rig_ids,
+                                                     const float* __restrict__ b_vm, const float* __restrict__ b_pm,
+                                                     const float* __restrict__ b_tan, const int* __restrict__ slot_wh,
+                                                     const double* __restrict__ b_proj, const double* __restrict__ b_sched,
+                                                     float* __restrict__ vm, float* __restrict__ pm, HmTan* __restrict__ views,
+                                                     double* __restrict__ proj, double* __restrict__ sched, int* __restrict__ err)
+{
+    const int f = blockIdx.x, t = threadIdx.x;
+    const int r = rig_ids[f];
+    if (r < 0 || r >= R) {
+        if (t == 0) *err = f + 1;     // (a plain store, as the early-stopping flags: `err` may be pinned host memory)
+        return;
+    }
+    const size_t src = (size_t)r * V, dst = (size_t)f * V;
+    for (int i = t; i < V * 16; i += 256) {
+        vm[dst * 16 + i] = b_vm[src * 16 + i];
+        pm[dst * 16 + i] = b_pm[src * 16 + i];
+    }
+    if (t < V) {
+        views->x[dst + t] = b_tan[(src + t) * 2];
+        views->y[dst + t] = b_tan[(src + t) * 2 + 1];
+        views->w[dst + t] = slot_wh[2 * t];
+        views->h[dst + t] = slot_wh[2 * t + 1];
+    }
+    if (proj)
+        for (int i = t; i < V * 12; i += 256) proj[dst * 12 + i] = b_proj[src * 12 + i];
+    if (t < 5) sched[5 * (size_t)f + t] = b_sched[5 * (size_t)r + t];
 }
 
 __global__ void k_heatmap_totals_finish(int V, double* __restrict__ totals)
@@ -675,7 +725,7 @@ int sks_heatmap_factors(int V, int J, int W, int H, const float* means3D, const 
         if (tan.w[v] < 1 || tan.w[v] > W || tan.h[v] < 1 || tan.h[v] > H)
             return fail2(-1, "heatmap factors: every view's size must be within [1, W] x [1, H]");
     }
-    hipLaunchKernelGGL(k_heatmap_factors, dim3(J, V), dim3(256), 0, (hipStream_t)stream, J, W, H, means3D, scales, rotations,
+    hipLaunchKernelGGL(k_heatmap_factors<HmTan>, dim3(J, V), dim3(256), 0, (hipStream_t)stream, J, W, H, means3D, scales, rotations,
                        scale_modifier, poses_2d, viewmatrix, tan, row, col, cmin, den, frames > 1 ? V / frames : 0);
     HIP_TRY2(hipGetLastError());
     return 0;
@@ -694,9 +744,54 @@ int sks_heatmap_totals(int V, int J, int W, int H, const float* row, const float
             return fail2(-1, "heatmap totals: every view's size must be within [1, W] x [1, H]");
     }
     HIP_TRY2(hipMemsetAsync(gt_totals, 0, (size_t)V * 2 * sizeof(double), (hipStream_t)stream));
-    hipLaunchKernelGGL(k_heatmap_totals, dim3((H + 15) / 16, J, V), dim3(256), 0, (hipStream_t)stream, J, W, H, sz, row, col, cmin,
+    hipLaunchKernelGGL(k_heatmap_totals<HmTan>, dim3((H + 15) / 16, J, V), dim3(256), 0, (hipStream_t)stream, J, W, H, sz, row, col, cmin,
                        den, gt_totals);
     hipLaunchKernelGGL(k_heatmap_totals_finish, dim3((V + 63) / 64), dim3(64), 0, (hipStream_t)stream, V, gt_totals);
+    HIP_TRY2(hipGetLastError());
+    return 0;
+}
+
+int sks_heatmap_factors_dv(int V, int J, int W, int H, const float* means3D, const float* scales, const float* rotations,
+                           float scale_modifier, const float* poses_2d, const float* viewmatrix, const void* views_dev,
+                           float* row, float* col, float* cmin, float* den, int frames, void* stream)
+{
+    if (V < 1 || V > SKS_MAX_VIEWS || J < 1 || W < 1 || H < 1) return fail2(-1, "heatmap factors: bad shape");
+    if (frames < 1 || V % frames) return fail2(-1, "heatmap factors: frames must divide the number of views");
+    if (!means3D || !scales || !rotations || !poses_2d || !viewmatrix || !views_dev || !row || !col || !cmin || !den)
+        return fail2(-2, "heatmap factors: missing pointer");
+    hipLaunchKernelGGL(k_heatmap_factors<HmTanDev>, dim3(J, V), dim3(256), 0, (hipStream_t)stream, J, W, H, means3D, scales, rotations,
+                       scale_modifier, poses_2d, viewmatrix, hm_tan_dev(views_dev), row, col, cmin, den,
+                       frames > 1 ? V / frames : 0);
+    HIP_TRY2(hipGetLastError());
+    return 0;
+}
+
+int sks_heatmap_totals_dv(int V, int J, int W, int H, const float* row, const float* col, const float* cmin, const float* den,
+                          const void* views_dev, double* gt_totals, void* stream)
+{
+    if (V < 1 || V > SKS_MAX_VIEWS || J < 1 || W < 1 || H < 1) return fail2(-1, "heatmap totals: bad shape");
+    if (!row || !col || !cmin || !den || !views_dev || !gt_totals) return fail2(-2, "heatmap totals: missing pointer");
+    HIP_TRY2(hipMemsetAsync(gt_totals, 0, (size_t)V * 2 * sizeof(double), (hipStream_t)stream));
+    hipLaunchKernelGGL(k_heatmap_totals<HmTanDev>, dim3((H + 15) / 16, J, V), dim3(256), 0, (hipStream_t)stream, J, W, H,
+                       hm_tan_dev(views_dev), row, col, cmin, den, gt_totals);
+    hipLaunchKernelGGL(k_heatmap_totals_finish, dim3((V + 63) / 64), dim3(64), 0, (hipStream_t)stream, V, gt_totals);
+    HIP_TRY2(hipGetLastError());
+    return 0;
+}
+
+int sks_rig_select(int R, int V, int frames, const int* rig_ids, const float* bank_viewmatrix, const float* bank_projmatrix,
+                   const float* bank_tan, const int* slot_wh, const double* bank_proj, const double* bank_sched,
+                   float* viewmatrix, float* projmatrix, void* views_dev, double* proj, double* lr_sched_dev, int* error_word,
+                   void* stream)
+{
+    if (R < 1 || V < 1 || frames < 1 || (long long)frames * V > SKS_MAX_VIEWS)
+        return fail2(-1, "rig_select: needs R >= 1 and 1 <= frames x V <= SKS_MAX_VIEWS");
+    if (!rig_ids || !bank_viewmatrix || !bank_projmatrix || !bank_tan || !slot_wh || !bank_sched || !viewmatrix || !projmatrix ||
+        !views_dev || !lr_sched_dev || !error_word || (proj != nullptr) != (bank_proj != nullptr))
+        return fail2(-2, "rig_select: missing pointer (bank_proj and proj go together)");
+    hipLaunchKernelGGL(k_rig_select, dim3(frames), dim3(256), 0, (hipStream_t)stream, R, V, rig_ids, bank_viewmatrix,
+                       bank_projmatrix, bank_tan, slot_wh, bank_proj, bank_sched, viewmatrix, projmatrix, (HmTan*)views_dev, proj,
+                       lr_sched_dev, error_word);
     HIP_TRY2(hipGetLastError());
     return 0;
 }

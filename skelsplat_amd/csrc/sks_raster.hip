@@ -27,6 +27,7 @@
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/skelsplat_hip.h"
 #include "sks_math.h"
@@ -278,7 +279,7 @@ void sks_set_error_(const char* msg)  // used by the other translation units of 
 {
     snprintf(g_err, sizeof(g_err), "%s", msg);
 }
-int sks_version(void) { return 13; }
+int sks_version(void) { return 14; }
 
 int sks_scratch_bytes(int V, int P, int C, int W, int H, size_t bin_capacity, size_t* geom, size_t* binning, size_t* accum)
 {
@@ -742,8 +743,31 @@ int sks_geometry(int V, int P, int C, int W, int H, const float* viewmatrix, con
     return 0;
 }
 
+int sks_geometry_dv(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix, const void* views_dev,
+                    const float* means3D, const float* opacities, const float* scales, const float* rotations,
+                    const float* cov3D_precomp, float scale_modifier, unsigned flags, int* radii, void* geom, int frames,
+                    void* stream)
+{
+    if (int rc = check_common(V, P, C, W, H)) return rc;
+    if (P < 1) return fail(-1, "P must be positive");
+    if (frames < 1 || V % frames) return fail(-1, "frames must divide the number of views (V = %d, frames = %d)", V, frames);
+    if (!viewmatrix || !projmatrix || !views_dev || !means3D || !opacities || !radii || !geom)
+        return fail(-2, "missing required pointer");
+    if (!cov3D_precomp && (!scales || !rotations)) return fail(-2, "need scales+rotations or cov3D_precomp");
+    hipStream_t st = (hipStream_t)stream;
+    Geom g = geom_from(geom, V, P, W, H);
+    g.cover = nullptr;
+    hipLaunchKernelGGL(k_geom_fwd_dv, dim3((P + 255) / 256, V), dim3(256), 0, st, P, views_dev_from(views_dev), viewmatrix,
+                       projmatrix, means3D, opacities, scales, rotations, cov3D_precomp, scale_modifier, flags, g, radii,
+                       frames > 1 ? V / frames : 0);
+    STAGE_CHECK("geometry");
+    return 0;
+}
+
 // sks_loop_fused_step and (es_state != nullptr) sks_loop_fused_step_es: the same two launches, the latter in the early-stopping
-// instantiations of both kernels
+// instantiations of both kernels.  views_dev != nullptr (the _dv entries): the tail reads the per-view scalars from that device
+// table and frame f's LR schedule from row f of lr_sched_dev; the compositing backward reads only the views' SIZES, which stay
+// in its argument segment (view_wh: fixed per view slot)
 static int loop_fused_step_impl(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
                                 const float* tanfovx, const float* tanfovy, const float* features, float scale_modifier,
                                 unsigned flags, int* radii, void* geom, const float* gt, const double* gt_totals, void* accum,
@@ -752,10 +776,14 @@ static int loop_fused_step_impl(int V, int P, int C, int W, int H, const float* 
                                 int* counters, int acc_steps, const double* lr_sched, const double* lrs, const double* adam,
                                 float lambda_consistency, const int* limb, const int* view_wh, const size_t* gt_offsets,
                                 int frames, const float* const* hm_factors, int* es_state, int es_window, float es_tolerance,
-                                int* es_host_flags, void* stream)
+                                int* es_host_flags, void* stream, const void* views_dev = nullptr,
+                                const double* lr_sched_dev = nullptr)
 {
     if (int rc = check_common(V, P, C, W, H)) return rc;
     if (P < 1 || P > 64) return fail(-1, "fused step needs 1 <= P <= 64 (got %d)", P);
+    static const float no_tan[SKS_MAX_VIEWS] = {};                  // _dv: the by-value record carries the sizes only
+    static const double no_sched[5] = { 1.0, 1.0, 1.0, 0.0, 1.0 };  // _dv: every frame's schedule is read in the kernel
+    if (views_dev) { tanfovx = tanfovy = no_tan; lr_sched = no_sched; }
     if (frames < 1 || V % frames) return fail(-1, "frames must divide the number of views (V = %d, frames = %d)", V, frames);
     const int Vf = V / frames;   // views of one frame: the optimiser's V (slots, group mask, last_view are per frame)
     if (!viewmatrix || !projmatrix || !tanfovx || !tanfovy || !features || !radii || !geom || (!gt && !hm_factors) || !gt_totals ||
@@ -792,7 +820,11 @@ static int loop_fused_step_impl(int V, int P, int C, int W, int H, const float* 
     GeomBwdArgs ga{ P, C, W, H, flags, viewmatrix, projmatrix, xyz, opacity, scaling, rotation, nullptr, scale_modifier, radii,
                     (const float*)accum, BWD_SPLITS, gt_totals, loss_sums, packed, nullptr, nullptr, nullptr, nullptr, nullptr,
                     nullptr, nullptr };
-    if (es) hipLaunchKernelGGL(k_step_tail<true>, dim3(frames), dim3(256), 0, st, ga, vt, aa, Vf, g, radii);
+    if (views_dev) {
+        const ViewTanDev vd = views_dev_from(views_dev, lr_sched_dev);
+        if (es) hipLaunchKernelGGL((k_step_tail<true, ViewTanDev>), dim3(frames), dim3(256), 0, st, ga, vd, aa, Vf, g, radii);
+        else hipLaunchKernelGGL((k_step_tail<false, ViewTanDev>), dim3(frames), dim3(256), 0, st, ga, vd, aa, Vf, g, radii);
+    } else if (es) hipLaunchKernelGGL(k_step_tail<true>, dim3(frames), dim3(256), 0, st, ga, vt, aa, Vf, g, radii);
     else hipLaunchKernelGGL(k_step_tail<false>, dim3(frames), dim3(256), 0, st, ga, vt, aa, Vf, g, radii);
     STAGE_CHECK("step tail");
     return 0;
@@ -833,6 +865,45 @@ int sks_loop_fused_step_es(int V, int P, int C, int W, int H, const float* viewm
                                 rotation, opacity, exp_avg, exp_avg_sq, counters, acc_steps, lr_sched, lrs, adam,
                                 lambda_consistency, limb, view_wh, gt_offsets, frames, hm_factors, es_state, es_window,
                                 es_tolerance, es_host_flags, stream);
+}
+
+int sks_loop_fused_step_dv(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                           const void* views_dev, const float* features, float scale_modifier, unsigned flags, int* radii,
+                           void* geom, const float* gt, const double* gt_totals, void* accum, double* loss_sums, float* packed,
+                           float* slots, unsigned long long group_mask, int last_view, float* xyz, float* scaling,
+                           float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq, int* counters, int acc_steps,
+                           const double* lr_sched_dev, const double* lrs, const double* adam, float lambda_consistency,
+                           const int* limb, const int* view_wh, const size_t* gt_offsets, int frames,
+                           const float* const* hm_factors, void* stream)
+{
+    if (!views_dev || !lr_sched_dev) return fail(-2, "loop_fused_step_dv: views_dev and lr_sched_dev are required");
+    return loop_fused_step_impl(V, P, C, W, H, viewmatrix, projmatrix, nullptr, nullptr, features, scale_modifier, flags, radii,
+                                geom, gt, gt_totals, accum, loss_sums, packed, slots, group_mask, last_view, xyz, scaling,
+                                rotation, opacity, exp_avg, exp_avg_sq, counters, acc_steps, nullptr, lrs, adam,
+                                lambda_consistency, limb, view_wh, gt_offsets, frames, hm_factors, nullptr, 0, 0.0f, nullptr,
+                                stream, views_dev, lr_sched_dev);
+}
+
+int sks_loop_fused_step_es_dv(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                              const void* views_dev, const float* features, float scale_modifier, unsigned flags, int* radii,
+                              void* geom, const float* gt, const double* gt_totals, void* accum, double* loss_sums,
+                              float* packed, float* slots, unsigned long long group_mask, int last_view, float* xyz,
+                              float* scaling, float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq, int* counters,
+                              int acc_steps, const double* lr_sched_dev, const double* lrs, const double* adam,
+                              float lambda_consistency, const int* limb, const int* view_wh, const size_t* gt_offsets,
+                              int frames, const float* const* hm_factors, int* es_state, int es_window, float es_tolerance,
+                              int* es_host_flags, void* stream)
+{
+    if (!views_dev || !lr_sched_dev) return fail(-2, "loop_fused_step_es_dv: views_dev and lr_sched_dev are required");
+    if (!es_state)
+        return fail(-2, "loop_fused_step_es_dv: es_state is required (sks_loop_fused_step_dv is the step without a criterion)");
+    if (es_window < 1 || es_window > sksloop::ES_MAX_WINDOW)
+        return fail(-1, "loop_fused_step_es_dv: window %d out of range [1, %d]", es_window, sksloop::ES_MAX_WINDOW);
+    return loop_fused_step_impl(V, P, C, W, H, viewmatrix, projmatrix, nullptr, nullptr, features, scale_modifier, flags, radii,
+                                geom, gt, gt_totals, accum, loss_sums, packed, slots, group_mask, last_view, xyz, scaling,
+                                rotation, opacity, exp_avg, exp_avg_sq, counters, acc_steps, nullptr, lrs, adam,
+                                lambda_consistency, limb, view_wh, gt_offsets, frames, hm_factors, es_state, es_window,
+                                es_tolerance, es_host_flags, stream, views_dev, lr_sched_dev);
 }
 
 int sks_prof_spin(double microseconds, void* stream)

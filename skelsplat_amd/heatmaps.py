@@ -64,11 +64,17 @@ def heatmap_factors(means, scaling, rotation_raw, poses_2d, cameras, scaling_mod
         cmin = torch.empty((V, J), dtype=torch.float32, device=dev)
         den = torch.empty((V, J), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        rc = _lib.load().sks_heatmap_factors(V, J, W, H, means.data_ptr(), scaling.data_ptr(), rotation_raw.data_ptr(),
-                                             float(scaling_modifier), p2d.data_ptr(), views.viewmatrix.data_ptr(),
-                                             views.tanfovx, views.tanfovy, row.data_ptr(), col.data_ptr(),
-                                             cmin.data_ptr(), den.data_ptr(), frames, views.wh,
-                                             torch.cuda.current_stream(dev).cuda_stream)
+        if views.table is not None:     # (a frame batch over a rig bank: the per-view scalars live on the device)
+            rc = _lib.load().sks_heatmap_factors_dv(V, J, W, H, means.data_ptr(), scaling.data_ptr(), rotation_raw.data_ptr(),
+                                                    float(scaling_modifier), p2d.data_ptr(), views.viewmatrix.data_ptr(),
+                                                    views.table.data_ptr(), row.data_ptr(), col.data_ptr(), cmin.data_ptr(),
+                                                    den.data_ptr(), frames, torch.cuda.current_stream(dev).cuda_stream)
+        else:
+            rc = _lib.load().sks_heatmap_factors(V, J, W, H, means.data_ptr(), scaling.data_ptr(), rotation_raw.data_ptr(),
+                                                 float(scaling_modifier), p2d.data_ptr(), views.viewmatrix.data_ptr(),
+                                                 views.tanfovx, views.tanfovy, row.data_ptr(), col.data_ptr(),
+                                                 cmin.data_ptr(), den.data_ptr(), frames, views.wh,
+                                                 torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, "sks_heatmap_factors")
     if drop_mask is not None:
         dm = torch.as_tensor(drop_mask, dtype=torch.bool).to(row.device)
@@ -107,6 +113,13 @@ def generate_heatmaps(means, scaling, rotation_raw, poses_2d, cameras, scaling_m
         drop_mask = draw_dropout(len(cameras), means.shape[-2])
     row, col, cmin, den = heatmap_factors(means, scaling, rotation_raw, poses_2d, cameras, scaling_modifier, views=views,
                                           frames=frames, drop_mask=drop_mask)
+    return heatmap_planes(row, col, cmin, den, out=out, totals=totals)
+
+
+def heatmap_planes(row, col, cmin, den, out=None, totals=None):
+    """The (V,J,H,W) planes of heat-maps given in separable form (heatmap_factors' contiguous row (V,J,H), col (V,J,W), cmin,
+    den (V,J)), by the streaming kernel sks_heatmaps; `out` / `totals` as for generate_heatmaps."""
+    from . import _lib
     V, J, H = row.shape
     W = col.shape[2]
     if out is None:

@@ -109,7 +109,7 @@ class MultiViewLoop:
     def __init__(self, gaussians, cameras, heatmaps, dataset="h36m", accumulation_steps=4, lambda_consistency=1e-5,
                  bg=None, antialiasing=False, loss_grad=None, group=None, view_grad_fn=None, device_tail=None,
                  use_graph=False, sparse=None, fused_tail=None, shard_views=True, graph_collectives=None,
-                 early_stopping="no_stopping"):
+                 early_stopping="no_stopping", rigs=None):
         import os
         self.gm = gaussians
         self.dataset = dataset
@@ -121,6 +121,13 @@ class MultiViewLoop:
         sharded = bool(shard_views) and dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size(group) if sharded else 1
         self.rank = dist.get_rank(group) if sharded else 0
+        if rigs is not None:
+            # a rig bank selects cameras per FRAME of a batch; this loop runs one frame on one list of cameras
+            if self.world > 1:
+                raise ValueError("a rig bank on a view-sharded loop (world > 1): every rank holds only its own views' rows; "
+                                 "rigs per frame need all views on one GPU (FrameBatchLoop / FramePipeline with rigs=)")
+            raise ValueError("MultiViewLoop runs one frame on one rig (cameras=); a rig bank goes to "
+                             "FrameBatchLoop(gaussians, rigs=bank, frames=F) -- frames=1 for one frame at a time")
         # the exchange step runs whenever views are sharded over a process group -- also a group of ONE rank, which is how
         # the single-GPU tests drive the very code path 8 GPUs take (RCCL all_gather included)
         self.exchange = sharded
@@ -707,6 +714,21 @@ def _sequence_inputs(points, poses_2d):
     return pts, p2d, pts.shape[0]
 
 
+def _sequence_rig_ids(sel, rig_ids, N):
+    """optimize_sequence's `rig_ids` -> None or an (N,) integer tensor on the device: host ids are validated against the bank
+    and uploaded once per sequence; a device tensor is taken as it is (the gather kernel checks its bounds)."""
+    if rig_ids is None:
+        return None
+    if sel is None:
+        raise ValueError("rig_ids needs a rig bank: FrameBatchLoop / FramePipeline(gaussians, rigs=RigBank(rigs, device), ...)")
+    if torch.is_tensor(rig_ids) and rig_ids.device.type != "cpu":
+        if rig_ids.dim() != 1 or rig_ids.shape[0] != N or rig_ids.is_floating_point():
+            raise ValueError(f"rig_ids must be ({N},) integers, got {tuple(rig_ids.shape)} {rig_ids.dtype}")
+        return rig_ids
+    from .rigs import validate_rig_ids
+    return torch.as_tensor(validate_rig_ids(rig_ids, sel.bank.R, N), dtype=torch.int32).to(sel.ids.device)
+
+
 def _frame_criterion(early_stopping):
     """FrameBatchLoop's `early_stopping` -> None (off) or (window, tolerance) of the reference's criterion, which the frame
     batch runs per frame on the device; anything else is refused."""
@@ -729,7 +751,8 @@ def _frame_criterion(early_stopping):
 
 
 class FrameBatchLoop:
-    """F independent frames seen by the SAME cameras, optimised side by side in the sparse fused step.
+    """F independent frames, optimised side by side in the sparse fused step -- seen by the SAME cameras (`cameras=`), or each
+    by one rig of a bank (`rigs=` a rigs.RigBank; then `new_scenes(..., rig_ids=)` names every frame's rig).
 
     The reference optimises one frame after the other (train.py:74-99: a fresh GaussianModel and fresh heat-maps per
     scene, nothing carried over), and one 17-Gaussian skeleton keeps only a fraction of an MI355X busy: the fused
@@ -747,11 +770,26 @@ class FrameBatchLoop:
     (sks_loop_fused_step_es): each frame stops at its own iteration, exactly as a MultiViewLoop running it alone with the
     same criterion, and a stopped frame's workgroups leave at once from then on.  `stopped_at` reads each frame's stopping
     iteration from pinned memory without waiting; `counters[f, 0]` is frame f's own iteration, while `iteration` stays the
-    number of iterations enqueued.  Host-side criteria (any other callable) read every loss back: MultiViewLoop runs those."""
+    number of iterations enqueued.  Host-side criteria (any other callable) read every loss back: MultiViewLoop runs those.
 
-    def __init__(self, gaussians, cameras, frames, dataset="h36m", accumulation_steps=4, lambda_consistency=1e-5,
-                 antialiasing=False, use_graph=False, factored=True, early_stopping="no_stopping"):
+    `rigs`: a RigBank on the parameters' device, instead of `cameras`.  The view and projection rows, the per-view scalars, the
+    DLT's projection matrices and the learning-rate schedule of the batch are then persistent DEVICE buffers which
+    `new_scenes(rig_ids=)` refills by one gather launch (sks_rig_select), and the step reads them through the library's *_dv
+    entry points -- nothing of a rig is baked into a captured graph, so `_graph` / `_multi` are replayed as they are for a batch
+    with other rigs.  `gaussians.opt_cfg` supplies every hyper-parameter except the spatial scale of the xyz learning rate,
+    which is each frame's own rig's `cameras_extent` (build the bank with the same `opt`).  A frame's trajectory is bit-identical
+    to FrameBatchLoop(cameras=that rig) running it alone.  The image size of a view slot stays fixed across rigs."""
+
+    def __init__(self, gaussians, cameras=None, frames=None, dataset="h36m", accumulation_steps=4, lambda_consistency=1e-5,
+                 antialiasing=False, use_graph=False, factored=True, early_stopping="no_stopping", rigs=None):
         import ctypes
+        if (cameras is None) == (rigs is None):
+            raise ValueError("FrameBatchLoop takes either cameras= (one rig for all frames) or rigs= (a RigBank)")
+        if frames is None:
+            raise ValueError("FrameBatchLoop needs frames=F")
+        if rigs is not None:
+            rigs.to(gaussians._xyz.device)      # (uploaded once; free when the bank already lives there)
+            cameras = rigs.rigs[0]      # (sizes and counts; every row a kernel reads comes from the bank, per batch)
         gm = gaussians
         self.gm = gm
         self.dataset = dataset
@@ -801,6 +839,15 @@ class FrameBatchLoop:
         self._limb = (ctypes.c_int * 8)(*limbs) if self.lambda_consistency != 0.0 else None
         cams_all = [cameras[k % V] for k in range(F * V)]
         self._cams_all = cams_all
+
+        def views_of(slots, allow_mixed=False):
+            if rigs is None:
+                return R.ViewBatch.from_cameras([cams_all[k] for k in slots], allow_mixed=allow_mixed)
+            # rows of the bank's rig 0 in buffers of the loop's own (filled per batch by sks_rig_select)
+            j = [k % V for k in slots]
+            sz = [rigs.sizes[i] for i in j]
+            return R.ViewBatch(rigs.viewmatrix_dev[0, j].clone(), rigs.projmatrix_dev[0, j].clone(), rigs.tan[0, j, 0].tolist(),
+                               rigs.tan[0, j, 1].tolist(), max(s[0] for s in sz), max(s[1] for s in sz), sz)
         # K [R|t] per view, float64 on the device, built once: new_scenes(points=None) triangulates with them
         from .triangulation import device_projection_matrices
         self._proj = device_projection_matrices(cameras, dev)
@@ -811,7 +858,7 @@ class FrameBatchLoop:
         self.factored = bool(factored)
         self.hset, self.size_groups, self.factors = None, [], None
         if self.factored:
-            self.views_all = R.ViewBatch.from_cameras(cams_all, allow_mixed=True)
+            self.views_all = views_of(range(F * V), allow_mixed=True)
             self.factors = R.HeatmapFactors(F * V, self.C, self.views_all.W, self.views_all.H, dev)
             st = R.GtStats()
             st.gt, st.tile_S, st.tile_N = None, None, None
@@ -823,19 +870,28 @@ class FrameBatchLoop:
             self.hset = R.HeatmapSet(sizes, self.C, dev)
             # [slots (frame-major), ViewBatch of them, (Vg,C,H,W) planes, GtStats, slot index tensor]
             for key, slots in self.hset.groups.items():
-                vb = R.ViewBatch.from_cameras([cams_all[k] for k in slots])
+                vb = views_of(slots)
                 gt = self.hset.group(key)
                 gt.zero_()
                 self.size_groups.append([slots, vb, gt, R.gt_tile_stats(gt), torch.tensor(slots, dtype=torch.long, device=dev)])
             if len(self.size_groups) == 1:
                 self.views_all, self.stats_all = self.size_groups[0][1], self.size_groups[0][3]
             else:
-                self.views_all = R.ViewBatch.from_cameras(cams_all, allow_mixed=True)
+                self.views_all = views_of(range(F * V), allow_mixed=True)
                 st = R.GtStats()
                 st.gt, st.tile_S, st.tile_N = self.hset.flat, None, None
                 st.totals = torch.zeros((F * V, 2), dtype=torch.float64, device=dev)
                 st.offsets = self.hset.offsets
                 self.stats_all = st
+        self.rigs, self._sel, self._hf_all = rigs, None, None
+        if rigs is not None:
+            from .rigs import RigSelection
+            self._sel = RigSelection(rigs, F, self.views_all.viewmatrix, self.views_all.projmatrix)
+            self.views_all.table = self._sel.table
+            self._sched, self._proj = self._sel.sched, self._sel.proj      # per frame, on the device
+            self._sel.select([0] * F)
+            if not self.factored:   # the factors of ALL views in one launch; the planes are written from them per image size
+                self._hf_all = R.HeatmapFactors(F * V, self.C, self.views_all.W, self.views_all.H, dev)
         with torch.no_grad():
             self._fstate = R.geometry_views(self.views_all, self.xyz, self.C, self.opacity, self.scaling, self.rotation, None,
                                             antialiasing=antialiasing, raw_params=True, frames=F)
@@ -845,7 +901,7 @@ class FrameBatchLoop:
         self.iteration = 0
         self.last_losses = None
 
-    def new_scenes(self, points, poses_2d=None, heatmaps=None, drop_masks=None):
+    def new_scenes(self, points, poses_2d=None, heatmaps=None, drop_masks=None, rig_ids=None):
         """The next F frames: `points` (F,P,3) initial joints; either `poses_2d` (F,V,J,2) -- the heat-maps are generated
         from the re-initialised Gaussians like general_utils.py:175-304, all frames in two launches per image size -- or
         ready `heatmaps` (F,V,C,H,W) / a list of F lists of V (C,H_v,W_v) planes.  `drop_masks`: optional (F,V,J) bool of
@@ -855,13 +911,24 @@ class FrameBatchLoop:
         written straight into `self.xyz` by one launch on the current stream, in front of the heat-map factors that read
         them: detections already on the device never touch the host.  `drop_masks` are then also the DLT's
         `valid = ~drop_masks` -- a dropped plane is a detection the caller does not trust --, and a joint kept in fewer than
-        two views has no triangulation: it starts as NaN.  Ready `heatmaps` carry no detections: refused."""
-        from .heatmaps import generate_heatmaps, heatmap_factors
+        two views has no triangulation: it starts as NaN.  Ready `heatmaps` carry no detections: refused.
+        `rig_ids` (F,) ints, host or device (a loop over a rig bank): frame f is seen by rig rig_ids[f] -- one gather launch on
+        the current stream fills the batch's camera rows, per-view scalars, projection matrices and schedule rows in place, in
+        front of the triangulation and the heat-map factors that read them.  Host ids are validated here; ids in a device
+        tensor are bounds-checked by the kernel, which skips a frame whose id is outside the bank (it keeps the cameras its
+        slot had) and raises an error word that `check_rigs()` reports.  None: the frames keep the rigs they have."""
+        from .heatmaps import generate_heatmaps, heatmap_factors, heatmap_planes
         from .triangulation import triangulate_sequence
         F, V, P = self.F, self.V, self.P
         if self.factored and heatmaps is not None:
             raise ValueError("ready heat-map planes need FrameBatchLoop(..., factored=False)")
+        if rig_ids is not None and self._sel is None:
+            raise ValueError("rig_ids needs a rig bank: FrameBatchLoop(gaussians, rigs=RigBank(rigs, device), frames=F)")
         with torch.no_grad():
+            if self._sel is not None:
+                self._sel.check()       # (an id a device tensor of an earlier batch held outside the bank; never waits)
+                if rig_ids is not None:
+                    self._sel.select(rig_ids)
             if points is None:
                 if poses_2d is None:
                     raise ValueError("new_scenes(points=None) triangulates the initial joints from poses_2d: give poses_2d "
@@ -902,11 +969,18 @@ class FrameBatchLoop:
                 heatmap_factors(self.xyz, torch.exp(self.scaling), self.rotation, p2d_all, self._cams_all,
                                 views=self.views_all, frames=F, out=self.factors, drop_mask=drop_all)
                 self.factors.totals(self.views_all, self.stats_all.totals)
+            if self._hf_all is not None and heatmaps is None:
+                heatmap_factors(self.xyz, torch.exp(self.scaling), self.rotation, p2d_all, self._cams_all,
+                                views=self.views_all, frames=F, out=self._hf_all, drop_mask=drop_all)
             for slots, vb, gt, stats, idx in self.size_groups:
                 if heatmaps is not None:
                     for i, k in enumerate(slots):
                         gt[i].copy_(heatmaps[k // V][k % V])
                     R.gt_tile_stats(gt, out=stats)
+                elif self._hf_all is not None:
+                    hf = self._hf_all       # (a view's factors do not depend on which views share its launch)
+                    heatmap_planes(hf.row[idx][:, :, :vb.H].contiguous(), hf.col[idx][:, :, :vb.W].contiguous(), hf.cmin[idx],
+                                   hf.den[idx], out=gt, totals=stats.totals)
                 else:
                     generate_heatmaps(self.xyz, torch.exp(self.scaling), self.rotation, p2d_all[idx],
                                       [self.cameras[k % V] for k in slots], out=gt, views=vb, totals=stats.totals,
@@ -982,7 +1056,15 @@ class FrameBatchLoop:
         self._enqueue(iterations, groups_per_graph)
         if self._es is not None:
             torch.cuda.current_stream(self.device).synchronize()
+            self.check_rigs()
         return self.xyz
+
+    def check_rigs(self):
+        """A loop over a rig bank: raises if a `rig_ids` device tensor named a rig outside the bank (that frame was skipped by
+        the gather and ran with the cameras its slot held before).  Reads a pinned word and never waits: final once the
+        stream has been synchronised, which run() with early stopping does itself."""
+        if self._sel is not None:
+            self._sel.check()
 
     def _enqueue(self, iterations, groups_per_graph):
         """run() without its final synchronisation (FramePipeline drives several loops with it)."""
@@ -1011,33 +1093,39 @@ class FrameBatchLoop:
             self.step_group(parameters_untouched=chained)
             chained = True
 
-    def _next_batch(self, pts, p2d, b, initial=None):
+    def _next_batch(self, pts, p2d, b, initial=None, rig_ids=None):
         """new_scenes for the frames b .. b + F of a sequence (a short last batch is filled up by repeating its final
-        frame); `pts` None: triangulated from the detections.  `initial` (N,P,3): receives the batch's initial joints."""
+        frame, rig included); `pts` None: triangulated from the detections.  `initial` (N,P,3): receives the batch's initial
+        joints.  `rig_ids`: None or the sequence's (N,) ids as _sequence_rig_ids left them."""
         N, F = p2d.shape[0], self.F
         if b + F <= N:      # a full batch: views of the inputs, no gather
-            self.new_scenes(None if pts is None else pts[b:b + F], poses_2d=p2d[b:b + F])
+            self.new_scenes(None if pts is None else pts[b:b + F], poses_2d=p2d[b:b + F],
+                            rig_ids=None if rig_ids is None else rig_ids[b:b + F])
         else:
             idx = [min(b + i, N - 1) for i in range(F)]
-            self.new_scenes(None if pts is None else pts[idx], poses_2d=p2d[idx])
+            self.new_scenes(None if pts is None else pts[idx], poses_2d=p2d[idx],
+                            rig_ids=None if rig_ids is None else rig_ids[idx])
         if initial is not None:
             initial[b:min(b + F, N)] = self.xyz[:min(F, N - b)]
 
-    def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, return_initial=False):
+    def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, return_initial=False, rig_ids=None):
         """The reference's outer loop over the frames of a sequence (train.py:74-99) F frames at a time: `points`
         (N,P,3) initial joints and `poses_2d` (N,V,J,2) detections of N frames -> (N,P,3) optimised joints.  A last batch
         with fewer than F frames is filled up by repeating its final frame (frames are independent: the filler changes
         nothing and is dropped).  `points=None`: every batch's initial joints are triangulated from its detections on
         the device (new_scenes); `poses_2d` may be a device tensor and is then never copied to the host.
-        `return_initial=True`: returns (joints, initial joints), both (N,P,3) on the device."""
+        `return_initial=True`: returns (joints, initial joints), both (N,P,3) on the device.
+        `rig_ids` (N,) ints, host or device (a loop over a rig bank): the rig of every frame, see new_scenes."""
         pts, p2d, N = _sequence_inputs(points, poses_2d)
+        ids = _sequence_rig_ids(self._sel, rig_ids, N)
         F = self.F
         out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
         initial = torch.empty_like(out) if return_initial else None
         for b in range(0, N, F):
-            self._next_batch(pts, p2d, b, initial)
+            self._next_batch(pts, p2d, b, initial, ids)
             res = self.run(iterations, groups_per_graph)
             out[b:min(b + F, N)] = res[:min(F, N - b)]
+        self.check_rigs()
         return (out, initial) if return_initial else out
 
 
@@ -1053,7 +1141,7 @@ class FramePipeline:
     `early_stopping` (as FrameBatchLoop's) goes to every loop; then a stream whose batch has stopped entirely takes the next
     batch at once, and `stopped_at` holds the last sequence's stopping iterations."""
 
-    def __init__(self, gaussians, cameras, frames=16, streams=2, **kw):
+    def __init__(self, gaussians, cameras=None, frames=16, streams=2, **kw):
         kw.setdefault("use_graph", True)
         self.loops = [FrameBatchLoop(gaussians, cameras, frames, **kw) for _ in range(int(streams))]
         self.device = self.loops[0].device
@@ -1062,14 +1150,17 @@ class FramePipeline:
         self.stopped_at = None       # early stopping: (N,) int64 of the last optimize_sequence, 0 = ran to the end
 
     def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, interleave=100,
-                          return_initial=False):
+                          return_initial=False, rig_ids=None):
         """(N,P,3) initial joints + (N,V,J,2) detections -> (N,P,3) optimised joints (train.py:74-99 over the frames).
         The loops' graph launches are issued round-robin, `interleave` iterations at a time, so that every stream always
         has work queued; a last batch with fewer than `frames` frames is padded by repeating its final frame.
         `points=None`: every batch's initial joints are triangulated from its detections by one launch on the batch's own
         stream (FrameBatchLoop.new_scenes), behind whatever the caller's stream did to `poses_2d`; detections given as a
-        device tensor are never copied to the host.  `return_initial=True`: returns (joints, initial joints)."""
+        device tensor are never copied to the host.  `return_initial=True`: returns (joints, initial joints).
+        `rig_ids` (N,) ints, host or device (loops over a rig bank, `rigs=`): the rig of every frame, see
+        FrameBatchLoop.new_scenes; check_rigs() reports an id a device tensor held outside the bank."""
         pts, p2d, N = _sequence_inputs(points, poses_2d)
+        ids = _sequence_rig_ids(self.loops[0]._sel, rig_ids, N)     # (uploaded on the caller's stream, which every stream waits for)
         F, S = self.F, len(self.loops)
         out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
         initial = torch.empty_like(out) if return_initial else None
@@ -1079,9 +1170,10 @@ class FramePipeline:
             self.stopped_at = torch.zeros(N, dtype=torch.int64, device=self.device)
             for st in self.streams:
                 st.wait_stream(cur)
-            self._sequence_es(pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial)
+            self._sequence_es(pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial, ids)
             for st in self.streams:
                 cur.wait_stream(st)
+            self.check_rigs()
             return (out, initial) if return_initial else out
         for st in self.streams:
             st.wait_stream(cur)                      # inputs and `out` were produced on the caller's stream
@@ -1089,7 +1181,7 @@ class FramePipeline:
             active = list(zip(self.loops, self.streams, starts[w:w + S]))
             for fb, st, b in active:
                 with torch.cuda.stream(st):
-                    fb._next_batch(pts, p2d, b, initial)
+                    fb._next_batch(pts, p2d, b, initial, ids)
             for k in range(0, iterations, max(int(interleave), 1)):
                 for fb, st, b in active:
                     with torch.cuda.stream(st):
@@ -1099,9 +1191,15 @@ class FramePipeline:
                     out[b:min(b + F, N)] = fb.xyz[:min(F, N - b)]
         for st in self.streams:
             cur.wait_stream(st)
+        self.check_rigs()
         return (out, initial) if return_initial else out
 
-    def _sequence_es(self, pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial=None):
+    def check_rigs(self):
+        """FrameBatchLoop.check_rigs of every loop (never waits: final once the device has been synchronised)."""
+        for fb in self.loops:
+            fb.check_rigs()
+
+    def _sequence_es(self, pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial=None, rig_ids=None):
         """optimize_sequence with early stopping: every stream keeps its own batch and takes the next one as soon as its
         batch is done -- all frames stopped (seen in the pinned flags, without waiting) or `iterations` enqueued -- instead
         of waiting for the other streams' batches.  Results and stopping iterations are copied on the batch's stream."""
@@ -1113,7 +1211,7 @@ class FramePipeline:
             if b is None:
                 return None
             with torch.cuda.stream(st):
-                fb._next_batch(pts, p2d, b, initial)
+                fb._next_batch(pts, p2d, b, initial, rig_ids)
             return [fb, st, b, 0]
 
         step = max(int(interleave), 1)

@@ -221,7 +221,10 @@ class ViewBatch:
     """V cameras packed for one launch sequence.  The dense entry points (sks_forward / sks_backward write and read
     (V,C,H,W) tensors) need one image size; the sparse fused-loss path writes nothing dense and takes a batch whose
     views differ in size (`sizes`: per-view (W, H); H36M mixes 1000- and 1002-wide sensors, dataset_readers.py:68-80):
-    then W, H are the largest and `wh` is the HOST array the C ABI's `view_wh` argument wants."""
+    then W, H are the largest and `wh` is the HOST array the C ABI's `view_wh` argument wants.
+    `table`: None, or (a frame batch over a rigs.RigBank) the device-resident ViewTan table sks_rig_select fills together with
+    the rows of `viewmatrix` / `projmatrix`: geometry_views, loop_fused_step, heatmap_factors and HeatmapFactors.totals then go
+    through the library's *_dv entry points, which read the per-view scalars from it instead of from the host arrays."""
 
     def __init__(self, viewmatrices, projmatrices, tanfovx, tanfovy, W, H, sizes=None):
         import ctypes
@@ -238,17 +241,25 @@ class ViewBatch:
         assert len(self.sizes) == self.V
         self.mixed = any(sz != (self.W, self.H) for sz in self.sizes)
         self.wh = (ctypes.c_int * (2 * self.V))(*[x for sz in self.sizes for x in sz]) if self.mixed else None
+        self.table = None
+
+    @staticmethod
+    def camera_rows(cams):
+        """What a batch of these cameras holds, on the device the cameras live on (host cameras: host rows, rigs.RigBank builds
+        its bank from them): viewmatrix, projmatrix (V,16), tanfovx, tanfovy (lists of V), sizes [(W_v, H_v)]."""
+        import math
+        sizes = [(int(c.image_width), int(c.image_height)) for c in cams]
+        vm = torch.stack([c.world_view_transform.reshape(16) for c in cams])
+        pm = torch.stack([c.full_proj_transform.reshape(16) for c in cams])
+        return vm, pm, [math.tan(c.FoVx * 0.5) for c in cams], [math.tan(c.FoVy * 0.5) for c in cams], sizes
 
     @classmethod
     def from_cameras(cls, cams, allow_mixed=False):
-        import math
-        sizes = [(int(c.image_width), int(c.image_height)) for c in cams]
+        vm, pm, tanx, tany, sizes = cls.camera_rows(cams)
         W, H = max(s[0] for s in sizes), max(s[1] for s in sizes)
         if not allow_mixed and any(sz != (W, H) for sz in sizes):
             raise RuntimeError("all views of a batch must share the image size")
-        vm = torch.stack([c.world_view_transform.reshape(16) for c in cams])
-        pm = torch.stack([c.full_proj_transform.reshape(16) for c in cams])
-        return cls(vm, pm, [math.tan(c.FoVx * 0.5) for c in cams], [math.tan(c.FoVy * 0.5) for c in cams], W, H, sizes)
+        return cls(vm, pm, tanx, tany, W, H, sizes)
 
     @classmethod
     def from_settings(cls, rs):
@@ -1200,9 +1211,14 @@ class HeatmapFactors:
             raise ValueError("HeatmapFactors.totals: `out` must be a contiguous fp64 (V,2) tensor")
         dev = self.row.device
         with torch.cuda.device(dev):
-            rc = lib.sks_heatmap_totals(self.V, self.J, self.W, self.H, self.row.data_ptr(), self.col.data_ptr(),
-                                        self.cmin.data_ptr(), self.den.data_ptr(), views.wh, out.data_ptr(),
-                                        torch.cuda.current_stream(dev).cuda_stream)
+            if views.table is not None:
+                rc = lib.sks_heatmap_totals_dv(self.V, self.J, self.W, self.H, self.row.data_ptr(), self.col.data_ptr(),
+                                               self.cmin.data_ptr(), self.den.data_ptr(), views.table.data_ptr(), out.data_ptr(),
+                                               torch.cuda.current_stream(dev).cuda_stream)
+            else:
+                rc = lib.sks_heatmap_totals(self.V, self.J, self.W, self.H, self.row.data_ptr(), self.col.data_ptr(),
+                                            self.cmin.data_ptr(), self.den.data_ptr(), views.wh, out.data_ptr(),
+                                            torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(rc, "sks_heatmap_totals")
         return out
 
@@ -1309,6 +1325,13 @@ def geometry_views(views: ViewBatch, means3D, C, opacities, scales, rotations, c
         radii = torch.empty((V, P), dtype=torch.int32, device=dev)
         geom = torch.empty(gbytes, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
+        if views.table is not None:
+            rc = lib.sks_geometry_dv(V, P, C, W, H, views.viewmatrix.data_ptr(), views.projmatrix.data_ptr(),
+                                     views.table.data_ptr(), _lib.ptr(means3D), _lib.ptr(opacities), _lib.ptr(scales),
+                                     _lib.ptr(rotations), _lib.ptr(cov3D_precomp), float(scale_modifier), flags,
+                                     radii.data_ptr(), geom.data_ptr(), frames, torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(rc, "sks_geometry_dv")
+            return ForwardState(views, P, C, flags, scale_modifier, radii, geom, frames=frames)
         rc = lib.sks_geometry(V, P, C, W, H, views.viewmatrix.data_ptr(), views.projmatrix.data_ptr(), views.tanfovx,
                               views.tanfovy, _lib.ptr(means3D), _lib.ptr(opacities), _lib.ptr(scales), _lib.ptr(rotations),
                               _lib.ptr(cov3D_precomp), float(scale_modifier), flags, radii.data_ptr(), geom.data_ptr(),
@@ -1343,7 +1366,9 @@ def loop_fused_step(st: ForwardState, stats: GtStats, features, packed, sums, sl
     updated ones.  lr_sched / lrs / adam / limb: ctypes arrays as for sks_loop_adam_step.  A state made with
     geometry_views(frames=F) steps F independent frames at once (stacked parameter / moment / slot / counter tensors).
     es_state: (F, 2 + 2 * es_window) int32 device tensor -> sks_loop_fused_step_es, the reference's opt_early_stopping per
-    frame on the device (es_flags: (F,) pinned int32 host tensor that receives each frame's stopping iteration, or None)."""
+    frame on the device (es_flags: (F,) pinned int32 host tensor that receives each frame's stopping iteration, or None).
+    Views with a device `table` (a frame batch over a rig bank): `lr_sched` is the (frames,5) float64 DEVICE tensor of per-frame
+    schedule rows and the step goes through sks_loop_fused_step_dv / _es_dv."""
     lib = _lib.load()
     dev = xyz.device
     V, P, C = st.views.V, st.P, st.C
@@ -1352,8 +1377,21 @@ def loop_fused_step(st: ForwardState, stats: GtStats, features, packed, sums, sl
     feat2 = _f32c(features, "features").reshape(P, -1)
     stream = torch.cuda.current_stream(dev).cuda_stream
     accum = _accum(dev, stream, V, P, C)
-    args = (V, P, C, W, H, st.views.viewmatrix.data_ptr(), st.views.projmatrix.data_ptr(), st.views.tanfovx,
-            st.views.tanfovy, feat2.data_ptr(), st.scale_modifier, st.flags, st.radii.data_ptr(), st.geom.data_ptr(),
+    dv = st.views.table is not None
+    if dv != torch.is_tensor(lr_sched):
+        raise ValueError("lr_sched: a (frames,5) device tensor with views that carry a device table, the HOST array otherwise")
+    if dv:
+        if lr_sched.dtype != torch.float64 or tuple(lr_sched.shape) != (st.frames, 5) or not lr_sched.is_contiguous() \
+                or lr_sched.device != dev:
+            raise ValueError(f"lr_sched must be a contiguous float64 ({st.frames}, 5) tensor on {dev}")
+        cams = (st.views.table.data_ptr(),)
+        lr_sched = lr_sched.data_ptr()
+    else:
+        cams = (st.views.tanfovx, st.views.tanfovy)
+    step, step_es = ((lib.sks_loop_fused_step_dv, lib.sks_loop_fused_step_es_dv) if dv
+                     else (lib.sks_loop_fused_step, lib.sks_loop_fused_step_es))
+    args = (V, P, C, W, H, st.views.viewmatrix.data_ptr(), st.views.projmatrix.data_ptr(), *cams,
+            feat2.data_ptr(), st.scale_modifier, st.flags, st.radii.data_ptr(), st.geom.data_ptr(),
             _lib.ptr(stats.gt), stats.totals.data_ptr(), accum.data_ptr(), sums.data_ptr(), packed.data_ptr(),
             slots.data_ptr(), group_mask, last_view, xyz.data_ptr(), scaling.data_ptr(), rotation.data_ptr(),
             opacity.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), counters.data_ptr(), acc_steps, lr_sched, lrs,
@@ -1361,7 +1399,7 @@ def loop_fused_step(st: ForwardState, stats: GtStats, features, packed, sums, sl
             None if stats.factors is None else stats.factors.ptrs)
     if es_state is None:
         with torch.cuda.device(dev):
-            rc = lib.sks_loop_fused_step(*args, stream)
+            rc = step(*args, stream)
         _lib.check(rc, "sks_loop_fused_step")
         return
     if es_state.dtype != torch.int32 or not es_state.is_contiguous() or es_state.device != dev \
@@ -1370,8 +1408,8 @@ def loop_fused_step(st: ForwardState, stats: GtStats, features, packed, sums, sl
     if es_flags is not None and (es_flags.dtype != torch.int32 or es_flags.numel() != st.frames or es_flags.device.type != "cpu"):
         raise ValueError(f"es_flags must be a pinned int32 host tensor of {st.frames} ints")
     with torch.cuda.device(dev):
-        rc = lib.sks_loop_fused_step_es(*args, es_state.data_ptr(), int(es_window), float(es_tolerance),
-                                        None if es_flags is None else es_flags.data_ptr(), stream)
+        rc = step_es(*args, es_state.data_ptr(), int(es_window), float(es_tolerance),
+                     None if es_flags is None else es_flags.data_ptr(), stream)
     _lib.check(rc, "sks_loop_fused_step_es")
 
 

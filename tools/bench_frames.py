@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """Frames per second of the H36M training loop (4 views @ 1000x1000, 500 iterations per frame, heat-map generation
 included) when F independent frames share the launches (loop.FrameBatchLoop), against one frame at a time
-(loop.MultiViewLoop.new_scene + run, hipGraphs in both).  Usage: bench_frames.py [F ...]"""
+(loop.MultiViewLoop.new_scene + run, hipGraphs in both).  Usage: bench_frames.py [F ...]
+
+bench_frames.py --rigs R [--reps N] [--frames F] [--streams S]: frames seen by different camera rigs (rigs.RigBank).  A
+sequence of S x F x 4 frames through FramePipeline (S streams of F frames, graphs on), N interleaved repetitions of
+  one_rig      FramePipeline(cameras=rig 0): the path that takes the per-view scalars by value;
+  bank_equal   FramePipeline(rigs=bank), every frame on rig 0;
+  bank_cycle   FramePipeline(rigs=bank), frame f on rig f % R;
+  naive        what a caller had to do before: per batch, the cameras of the batch's rig rebuilt on the host (Camera objects, a
+               new FrameBatchLoop with its ViewBatch) and the graphs captured again (one rig per batch: frames are taken rig by rig);
+and the host cost of building one rig's Cameras alone.  Prints one line per case: median frames/s, min, max."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -10,6 +19,88 @@ from skelsplat_amd.loop import MultiViewLoop, FrameBatchLoop
 from skelsplat_amd.scene import SyntheticScene, GaussianModel
 
 dev = torch.device("cuda", 0)
+
+
+def bench_rigs(argv):
+    import argparse, statistics
+    from skelsplat_amd.loop import FramePipeline
+    from skelsplat_amd.rigs import RigBank
+    from skelsplat_amd.scene import Camera
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rigs", type=int, required=True)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--streams", type=int, default=2)
+    ap.add_argument("--cases", default="one_rig,bank_equal,bank_cycle,naive")
+    a = ap.parse_args(argv)
+    iters = int(os.environ.get("ITERS", "500"))
+    R_, F, S = a.rigs, a.frames, a.streams
+    N = S * F * 4
+    scenes = [SyntheticScene("h36m", n_views=4, seed=r, device=dev) for r in range(R_)]
+    rigs = [sc.cameras for sc in scenes]
+    bank = RigBank(rigs, dev)
+    rng = np.random.default_rng(1)
+    cyc = [f % R_ for f in range(N)]
+
+    def frames_for(ids):
+        return (np.stack([scenes[r].pose_3d_init + rng.normal(0, 10.0, (17, 3)) for r in ids]).astype(np.float32),
+                np.stack([scenes[r].poses_2d + rng.normal(0, 2.0, (4, 17, 2)) for r in ids]).astype(np.float32))
+
+    def model(r=0):
+        gm = GaussianModel().create_from_points(scenes[r].pose_3d_init, scenes[r].spatial_lr_scale, 17, device=dev)
+        gm.training_setup()
+        return gm
+
+    data = {"one_rig": frames_for([0] * N), "bank_equal": frames_for([0] * N), "bank_cycle": frames_for(cyc),
+            "naive": frames_for(sorted(cyc))}
+    pipes = {"one_rig": FramePipeline(model(), rigs[0], frames=F, streams=S, dataset="h36m"),
+             "bank_equal": FramePipeline(model(), rigs=bank, frames=F, streams=S, dataset="h36m"),
+             "bank_cycle": FramePipeline(model(), rigs=bank, frames=F, streams=S, dataset="h36m")}
+    ids_dev = {"bank_equal": torch.zeros(N, dtype=torch.int32, device=dev), "bank_cycle": torch.tensor(cyc, dtype=torch.int32, device=dev)}
+
+    def run_case(name):
+        pts, p2d = data[name]
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        if name == "naive":
+            # one rig per batch: the rig's cameras are rebuilt from R / T / K, a loop is built around them, its graphs are captured
+            order = sorted(cyc)
+            for b in range(0, N, F):
+                src = rigs[order[b]]
+                cams = [Camera(c.uid, c.R, c.T, c.K, c.image_width, c.image_height, device=dev) for c in src]
+                fb = FrameBatchLoop(model(order[b]), cams, F, dataset="h36m", use_graph=True)
+                fb.new_scenes(pts[b:b + F], poses_2d=p2d[b:b + F])
+                fb.run(iters)
+        elif name == "one_rig":
+            pipes[name].optimize_sequence(pts, p2d, iterations=iters)
+        else:
+            pipes[name].optimize_sequence(pts, p2d, iterations=iters, rig_ids=ids_dev[name])
+        torch.cuda.synchronize()
+        return N / (time.perf_counter() - t0)
+
+    cases = [c for c in a.cases.split(",") if c]
+    for c in cases:
+        if c != "naive":
+            run_case(c)         # warm-up: allocations, graph capture
+    rates = {c: [] for c in cases}
+    for rep in range(a.reps):   # interleaved: one repetition of every case after the other
+        for c in cases:
+            rates[c].append(run_case(c))
+    for c in cases:
+        v = rates[c]
+        print(f"rigs={R_} {c:11s}: median {statistics.median(v):7.0f} frames/s  min {min(v):7.0f}  max {max(v):7.0f}  "
+              f"({S} streams x {F} frames, {N} frames, {iters} iterations, {a.reps} interleaved repetitions)  all: "
+              + " ".join(f"{x:.0f}" for x in v))
+    t0 = time.perf_counter()
+    for _ in range(20):
+        [Camera(c.uid, c.R, c.T, c.K, c.image_width, c.image_height, device=dev) for c in rigs[0]]
+    torch.cuda.synchronize()
+    print(f"host: building one rig's 4 Cameras (uploads included) {(time.perf_counter() - t0) / 20 * 1e3:.3f} ms, "
+          f"{F} x 4 per batch of distinct rigs {(time.perf_counter() - t0) / 20 * F * 1e3:.2f} ms")
+
+
+if "--rigs" in sys.argv:
+    bench_rigs(sys.argv[1:])
+    sys.exit(0)
 Fs = [int(a) for a in sys.argv[1:]] or [1, 2, 4, 8, 16]
 ITERS = int(os.environ.get("ITERS", "500"))
 FACTORED = os.environ.get("FACTORED", "1") == "1"   # heat-maps as separable factors (no planes) or as planes
