@@ -45,7 +45,7 @@ extern "C" {
                                  default) streams past the 256 MB Infinity Cache at the rate HBM takes writes; plain stores may
                                  stay in it: faster where a call rewrites the same ~cache-sized output step after step and
                                  nothing runs beside it (H36M: 46.5 -> 38-41 us), 40 % slower on outputs many times the cache.
-                                 No result bit depends on it (rasterizer.autotune_fill_passes times both) */
+                                 No result bit depends on it (rasterizer.tune_forward / Workspace.tune time the fill configurations) */
 
 /* tuning: bits 8..15 of `flags` = 4 KB passes per fill block of the fused forward (0 = automatic) */
 #define SKS_RAW_PARAMS   32u   /* opacities / scales / rotations are the LEAF parameters (_opacity logits, _scaling

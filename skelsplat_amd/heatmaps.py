@@ -37,7 +37,7 @@ def heatmap_factors(means, scaling, rotation_raw, poses_2d, cameras, scaling_mod
     ever written); only then may the cameras differ in size (rows / columns keep the largest view's strides).
     `drop_mask` (V,J) bool: planes without an impulse (see generate_heatmaps)."""
     from . import _lib
-    from .rasterizer import ViewBatch, _f32c
+    from ._base import ViewBatch, _f32c
     dev = means.device
     V = len(cameras)
     frames = int(frames)

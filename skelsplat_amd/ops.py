@@ -2,7 +2,7 @@
 import torch
 
 from . import _lib
-from .rasterizer import _need_gpu
+from ._base import _need_gpu
 
 
 def _chk(t, name):

@@ -16,6 +16,7 @@ import math
 import numpy as np
 import torch
 
+from ._base import ViewBatch
 from .scene import OptimizationParams, cameras_extent
 from .triangulation import projection_matrices
 
@@ -60,7 +61,6 @@ class RigBank:
     wh_dev (V,2) int32."""
 
     def __init__(self, rigs, device=None, opt=OptimizationParams):
-        from .rasterizer import ViewBatch
         rigs = [list(r) for r in rigs]
         if not rigs or not rigs[0]:
             raise ValueError("RigBank needs at least one rig of at least one camera")
