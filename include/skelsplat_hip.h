@@ -209,7 +209,10 @@ int sks_heatmaps(int V, int J, int W, int H, const float* row, const float* col,
                  float* out, double* gt_totals, void* stream);
 /* The factors themselves, one launch (general_utils.py:189-289): lambda1/lambda2 of each joint's Gaussian in each view
  * by the reference's own transcription of the EWA projection, the scipy-'reflect' truncated (4 sigma) 1-D responses of
- * the 255 impulse at the truncated 2D detection, and the min-max constants.  means3D (J,3), scales (J,3) activated,
+ * the 255 impulse at the truncated 2D detection, and the min-max constants.  Reflection rule: on an axis of n samples the
+ * impulse at p has the images p + 2nk and -1 - p + 2nk for every integer k, and every image within the truncation radius
+ * floor(4 sigma + 0.5) of a sample counts -- the impulse and one mirror per side while radius <= n, further bounces on a
+ * coarse image or under a wide Gaussian (any radius is exact; the cost grows with radius / n).  means3D (J,3), scales (J,3) activated,
  * rotations (J,4) raw quaternions, poses_2d (V,J,2) pixel (x, y), viewmatrix (V,16) as for sks_forward,
  * tanfovx/tanfovy HOST arrays of V. */
 int sks_heatmap_factors(int V, int J, int W, int H, const float* means3D, const float* scales, const float* rotations,

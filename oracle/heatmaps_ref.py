@@ -88,9 +88,12 @@ def _impulse_response_1d(pos, sigma, n, device):
         d = idx - src
         return torch.exp(-0.5 * d * d / (sig * sig)) * (d.abs() <= radius)
 
-    # 'reflect' extension (d c b a | a b c d | d c b a): mirrors of p about -0.5 and n-0.5 (one bounce each side
-    # is enough while radius < n, which holds for every realistic sigma)
+    # 'reflect' extension (d c b a | a b c d | d c b a | ...): the images of p are p + 2nk and -1 - p + 2nk for every
+    # integer k.  The impulse and its mirrors about -0.5 and n - 0.5 first; the k-th further pair of bounces starts
+    # 2nk - (n - 1) samples from the axis, so it only counts once radius > n (a coarse image or a wide Gaussian)
     out = tap(p) + tap(-1.0 - p) + tap(2.0 * n - 1.0 - p)
+    for k in range(1, (rmax + n - 1) // (2 * n) + 1):
+        out = out + tap(p + 2.0 * n * k) + tap(p - 2.0 * n * k) + tap(-1.0 - p - 2.0 * n * k) + tap(2.0 * n - 1.0 - p + 2.0 * n * k)
     return (out / norm).to(torch.float32)
 
 

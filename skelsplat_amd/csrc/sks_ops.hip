@@ -420,7 +420,12 @@ __device__ __forceinline__ void impulse_response(int n, int p, float sigma_f, fl
         part += exp(-0.5 * jj * jj / ss);
     }
     const double norm = 1.0 + 2.0 * block_sum_d(part, s_red);
-    const double src[3] = { (double)p, -1.0 - (double)p, 2.0 * n - 1.0 - (double)p };   // the impulse and its mirrors
+    // 'reflect' extension (d c b a | a b c d | d c b a | ...): the images of the impulse are p + 2nk and -1 - p + 2nk for every
+    // integer k.  The impulse and its two nearest mirrors first; an image of a further bounce is at least n + 1 samples from
+    // the axis, so those only count once radius > n (a coarse image or a wide Gaussian) and a smaller radius adds nothing.
+    const double src[3] = { (double)p, -1.0 - (double)p, 2.0 * n - 1.0 - (double)p };
+    const double period = 2.0 * n;
+    const double bounces = floor((radius + (double)(n - 1)) / period);   // the k-th pair of bounces starts 2nk - (n-1) away
     vmin = FLT_MAX;
     vmax = -FLT_MAX;
     for (int i = threadIdx.x; i < n; i += 256) {
@@ -429,6 +434,14 @@ __device__ __forceinline__ void impulse_response(int n, int p, float sigma_f, fl
         for (int m = 0; m < 3; m++) {
             const double d = (double)i - src[m];
             if (fabs(d) <= radius) acc += exp(-0.5 * d * d / ss);
+        }
+        for (double k = 1.0; k <= bounces; k += 1.0) {
+            const double far[4] = { src[0] + period * k, src[0] - period * k, src[1] - period * k, src[2] + period * k };
+#pragma unroll
+            for (int m = 0; m < 4; m++) {
+                const double d = (double)i - far[m];
+                if (fabs(d) <= radius) acc += exp(-0.5 * d * d / ss);
+            }
         }
         const float v = scale * (float)(acc / norm);
         out[i] = v;

@@ -188,6 +188,32 @@ def test_heatmaps_match_scipy_gaussian_filter():
             util.assert_close(f"heatmap v{v} j{j}", hm[v, j].numpy(), ref, rtol=1e-4, atol_scale=1e-6)
 
 
+def test_heatmaps_match_scipy_gaussian_filter_at_any_radius():
+    """... and on coarse images under wide Gaussians, where the truncation radius floor(4 sigma + 0.5) passes the axis length n
+    and scipy's `reflect` extension bounces the impulse more than once (images p + 2nk and -1 - p + 2nk for every k): radius
+    0, 1, n - 1, n, n + 1, about 3n and about 10n per axis, the impulse at 0, n - 1 and in the middle, against
+    scipy.ndimage.gaussian_filter itself."""
+    from scipy.ndimage import gaussian_filter
+    from oracle import heatmaps_ref as heatmaps
+    worst_three = 0.0
+    for H, W in ((16, 16), (24, 40), (1, 130)):
+        rows = sorted({0, 1, H - 1, H, H + 1, 3 * H, 10 * H})
+        cols = sorted({0, 1, W - 1, W, W + 1, 3 * W, 10 * W})
+        for k in range(max(len(rows), len(cols))):
+            ry, rx = rows[k % len(rows)], cols[(k + 2) % len(cols)]
+            sy, sx = ((ry + 0.25) / 4.0 if ry else 0.1), ((rx + 0.25) / 4.0 if rx else 0.1)
+            y, x = (0, H - 1, H // 2)[k % 3], (W - 1, W // 2, 0)[k % 3]
+            img = np.zeros((H, W), np.float64)
+            img[y, x] = 255.0
+            ref = gaussian_filter(img, sigma=[sy, sx])
+            t = lambda v: torch.tensor([v], dtype=torch.float64)
+            row = 255.0 * heatmaps._impulse_response_1d(torch.tensor([y]), t(sy), H, "cpu")[0].double()
+            col = heatmaps._impulse_response_1d(torch.tensor([x]), t(sx), W, "cpu")[0].double()
+            got = (row[:, None] * col[None, :]).numpy()
+            util.assert_close(f"{W}x{H} radius ({ry},{rx})", got, ref, rtol=1e-6, atol_scale=1e-7)
+    assert int(4.0 * ((10 * 130 + 0.25) / 4.0) + 0.5) == 1300
+
+
 # ------------------------------------------------------------------------------------------------ C ABI surface
 def test_library_exports_every_declared_symbol():
     hdr = open(os.path.join(ROOT, "include", "skelsplat_hip.h")).read()
