@@ -3,6 +3,8 @@ sizes that are not multiples of the tile, 1-3 views, 1-40 skeletons at random pi
 hundred), one-hot or dense features, opacities below 1, clamp, antialiasing, a background, with and without the inverse-depth and the
 feature gradient.  Forward bit for bit (colour, inverse depth, contributor counts, final T, tile lists), gradients at the tests'
 tolerance."""
+import types
+
 import numpy as np
 import torch
 
@@ -14,12 +16,9 @@ GR = (("means3D", "dL_dmeans3D"), ("means2D", "dL_dmeans2D"), ("opacities", "dL_
       ("rotations", "dL_drotations"), ("cov3D", "dL_dcov3D"), ("features", "dL_dcolors"))
 
 
-def run_case(seed, dev, small_path_too=False, stats=None):
-    """Raises AssertionError (its text names the case) when anything differs.  (check_capacity=True: the raw entry point's default
-    sizes the binning arena once per shape and checks later calls lazily -- two random scenes of one shape would trip it.)
-    `stats`: a dict that receives, per gradient, the largest excess over rtol in units of 2^-24 x sum|terms| (util.bound_excess:
-    what tools/fuzz_bound_calib.py calibrates util.BOUND_KAPPA with)."""
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a is not None else None
+def raster_scene(seed):
+    """The scene and switches of run_case's case `seed`, drawn without a device (tests/test_ref_cpu.py runs the same cases through
+    the CPU oracle and the compiled reference): -> a namespace with c (the Case), W, H, nv, kw, aa, clamp, use_bg, use_inv, use_feat, smod, precomp, extreme."""
     rng = np.random.default_rng(seed)
     W, H = int(rng.integers(40, 260)), int(rng.integers(40, 200))
     if seed % 8 == 0:    # wide and flat: the row-aligned fill mode (W % 32 == 0, >= 90 % of a 1024-pixel chunk) and its neighbours
@@ -48,6 +47,19 @@ def run_case(seed, dev, small_path_too=False, stats=None):
         m = pick(0.03); c.opac[m] = 1.0 / 255.0
         c.feat = c.feat.copy()
         m = pick(0.06); c.feat[m] = 0.0                                                                      # no colour at all: only inverse depth
+    return types.SimpleNamespace(c=c, W=W, H=H, nv=nv, kw=kw, aa=aa, clamp=clamp, use_bg=use_bg, use_inv=use_inv, use_feat=use_feat,
+                                 smod=smod, precomp=precomp, extreme=extreme)
+
+
+def run_case(seed, dev, small_path_too=False, stats=None):
+    """Raises AssertionError (its text names the case) when anything differs.  (check_capacity=True: the raw entry point's default
+    sizes the binning arena once per shape and checks later calls lazily -- two random scenes of one shape would trip it.)
+    `stats`: a dict that receives, per gradient, the largest excess over rtol in units of 2^-24 x sum|terms| (util.bound_excess:
+    what tools/fuzz_bound_calib.py calibrates util.BOUND_KAPPA with)."""
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a is not None else None
+    s = raster_scene(seed)
+    c, W, H, nv, kw, aa, clamp, extreme = s.c, s.W, s.H, s.nv, s.kw, s.aa, s.clamp, s.extreme
+    use_bg, use_inv, use_feat, smod, precomp = s.use_bg, s.use_inv, s.use_feat, s.smod, s.precomp
     views = R.ViewBatch.from_cameras([cam.to(dev) for cam in c.cams])
     cov = None
     if precomp:
@@ -123,12 +135,10 @@ def run_case(seed, dev, small_path_too=False, stats=None):
         raise AssertionError(f"{tag} -> {str(e)[:300]}") from None
 
 
-def run_one_call_case(seed, dev):
-    """sks_forward_backward (the backward on a second stream beside the forward, joined or not) against sks_forward + sks_backward on a
-    random small-path scene: image, inverse depth, radii and every gradient BIT FOR BIT, over several calls on one Workspace with
-    the parameters changing in place in between, any switch combination, 1-6 views, odd image sizes; every third seed with more
-    than SKS_MAX_CHANNELS channels (the generic path: two calls under the hood, same bits)."""
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a is not None else None
+def one_call_scene(seed):
+    """The scene and switches of run_one_call_case's case `seed`, drawn without a device:
+    -> a namespace with c (the Case), W, H, nv, aa, clamp, use_bg, use_inv, use_feat, want_mean, feat (the features: the Case's, or
+    33-71 channels wide) and rng (the generator as the draws left it: run_one_call_case goes on drawing from it)."""
     rng = np.random.default_rng(seed)
     W, H = int(rng.integers(40, 300)), int(rng.integers(40, 220))
     if seed % 6 == 0:
@@ -143,6 +153,19 @@ def run_one_call_case(seed, dev):
         Cw = int(rng.integers(33, 72))
         feat = (rng.random((c.P, Cw)) * (rng.random((c.P, Cw)) < 0.4)).astype(np.float32)
         want_mean = False
+    return types.SimpleNamespace(rng=rng, c=c, W=W, H=H, nv=nv, aa=aa, clamp=clamp, use_bg=use_bg, use_inv=use_inv, use_feat=use_feat,
+                                 want_mean=want_mean, feat=feat)
+
+
+def run_one_call_case(seed, dev):
+    """sks_forward_backward (the backward on a second stream beside the forward, joined or not) against sks_forward + sks_backward on a
+    random small-path scene: image, inverse depth, radii and every gradient BIT FOR BIT, over several calls on one Workspace with
+    the parameters changing in place in between, any switch combination, 1-6 views, odd image sizes; every third seed with more
+    than SKS_MAX_CHANNELS channels (the generic path: two calls under the hood, same bits)."""
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a is not None else None
+    s = one_call_scene(seed)
+    rng, c, W, H, nv, aa, clamp, feat = s.rng, s.c, s.W, s.H, s.nv, s.aa, s.clamp, s.feat
+    use_bg, use_inv, use_feat, want_mean = s.use_bg, s.use_inv, s.use_feat, s.want_mean
     C = feat.shape[1]
     tag = f"one-call seed {seed}: {W}x{H} V={nv} P={c.P} C={C} aa={aa} clamp={clamp} bg={use_bg} inv={use_inv} feat={use_feat} mean={want_mean}"
     try:
@@ -173,6 +196,22 @@ def run_one_call_case(seed, dev):
         raise AssertionError(f"{tag} -> {str(e)[:300]}") from None
 
 
+def fused_loss_scene(seed, dev):
+    """The scene and model of run_fused_loss_case's case `seed` on device `dev` ("cpu" works: tests/test_ref_cpu.py):
+    -> a namespace with sc (the scene), gm (the GaussianModel), dataset, W, H, nv, scaling, hscale, fxm, shift."""
+    from skelsplat_amd.scene import SyntheticScene, GaussianModel
+    rng = np.random.default_rng(seed)
+    dataset = str(rng.choice(["h36m", "panoptic", "occlusion-person"]))
+    W, H = int(rng.integers(48, 300)), int(rng.integers(48, 220))
+    nv = int(rng.integers(1, 6))
+    scaling, hscale = float(rng.uniform(2.6, 4.6)), float(rng.uniform(0.7, 1.6))
+    fxm, shift = float(rng.uniform(0.7, 1.8)), float(rng.uniform(0.0, 60.0))
+    sc = SyntheticScene(dataset, n_views=nv, seed=seed, W=W, H=H, ring=2500.0, fx=1145.0 * (W / 1000) * fxm, device=dev)
+    init = sc.pose_3d_init + rng.normal(0.0, shift, sc.pose_3d_init.shape)
+    gm = GaussianModel().create_from_points(init, sc.spatial_lr_scale, sc.n_joints, scaling=scaling, scene_type=dataset, device=dev)
+    return types.SimpleNamespace(sc=sc, gm=gm, dataset=dataset, W=W, H=H, nv=nv, scaling=scaling, hscale=hscale, fxm=fxm, shift=shift)
+
+
 def run_fused_loss_case(seed, dev):
     """The production loop's step -- sks_geometry + sks_backward_fused_loss: no image, no dense gradient, the pseudo-GT as planes
     or as separable factors -- against the dense device path sks_forward(clamp) -> sks_masked_l2 -> sks_backward on a random
@@ -180,17 +219,10 @@ def run_fused_loss_case(seed, dev):
     from skelsplat_amd.ops import masked_l2
     from skelsplat_amd.scene import SyntheticScene, GaussianModel
     from skelsplat_amd.heatmaps import generate_heatmaps, heatmap_factors
-    rng = np.random.default_rng(seed)
-    dataset = str(rng.choice(["h36m", "panoptic", "occlusion-person"]))
-    W, H = int(rng.integers(48, 300)), int(rng.integers(48, 220))
-    nv = int(rng.integers(1, 6))
-    scaling, hscale = float(rng.uniform(2.6, 4.6)), float(rng.uniform(0.7, 1.6))
-    fxm, shift = float(rng.uniform(0.7, 1.8)), float(rng.uniform(0.0, 60.0))
+    s = fused_loss_scene(seed, dev)
+    sc, gm, dataset, W, H, nv, scaling, hscale, fxm, shift = s.sc, s.gm, s.dataset, s.W, s.H, s.nv, s.scaling, s.hscale, s.fxm, s.shift
     tag = f"fused-loss seed {seed}: {dataset} {W}x{H} V={nv} scaling={scaling:.2f} heat x{hscale:.2f} fx x{fxm:.2f} shift {shift:.0f} mm"
     try:
-        sc = SyntheticScene(dataset, n_views=nv, seed=seed, W=W, H=H, ring=2500.0, fx=1145.0 * (W / 1000) * fxm, device=dev)
-        init = sc.pose_3d_init + rng.normal(0.0, shift, sc.pose_3d_init.shape)
-        gm = GaussianModel().create_from_points(init, sc.spatial_lr_scale, sc.n_joints, scaling=scaling, scene_type=dataset, device=dev)
         gt3d = torch.tensor(sc.pose_3d_gt, device=dev).float()
         p2d = torch.tensor(sc.poses_2d, device=dev)
         hm = generate_heatmaps(gt3d, gm.get_scaling.detach() * hscale, gm._rotation.detach(), p2d, sc.cameras)
