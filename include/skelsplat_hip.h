@@ -197,6 +197,25 @@ int sks_masked_l2(int V, size_t n_per_view, const float* render, const float* gt
 int sks_masked_l2_loss(int V, size_t n_per_view, const float* render, const float* gt, float* dL_unscaled, double* sums,
                        float* loss /* V */, float* scale /* V */, int mean, void* stream);
 
+/* The 2D keypoint read out of heat-map planes (utils/loss_utils.py:41-64 `softargmax2d`, which the reference's keypoint criteria
+ * l2 / l2_sqrt / huber / cauchy call with beta = 100 on the render).  img: `planes` contiguous (H, W) planes (V * C of them), 4-byte
+ * aligned.  Per plane, p = softmax(beta * img) over its H * W pixels:
+ *   xy[plane] = {sum p * col, sum p * row} in pixels (the reference's [result_c, result_r]);
+ *   stats[plane] = SKS_SOFTARGMAX_STATS floats {m = max img, 1 / sum exp(beta (img - m)), E[col], E[row], and what the floats of
+ *   E[col], E[row] miss of the fp64 expectations}: what the backward needs instead of a saved softmax (col - E[col] cancels
+ *   where p is largest, so the backward takes the expectations as float pairs).
+ * sks_softargmax_fwd: one read of img in two launches (per-chunk partial quadruples into `scratch`, then one wave per plane merges
+ *   them in a fixed order): no atomics, bit-identical from run to run.  scratch: sks_softargmax_scratch_bytes(planes, W, H) bytes,
+ *   8-byte aligned, contents irrelevant on entry (0 is returned, with the error text set, for sizes the calls below reject).
+ * sks_softargmax_bwd: dL_dimg = beta p (dL_dxy[plane][0] (col - E[col]) + dL_dxy[plane][1] (row - E[row])), one read of img and
+ *   one write of dL_dimg (planes x H x W, every element written). */
+#define SKS_SOFTARGMAX_STATS 6
+size_t sks_softargmax_scratch_bytes(int planes, int W, int H);
+int sks_softargmax_fwd(int planes, int W, int H, float beta, const float* img, float* xy /* planes x 2 */,
+                       float* stats /* planes x SKS_SOFTARGMAX_STATS */, void* scratch, size_t scratch_bytes, void* stream);
+int sks_softargmax_bwd(int planes, int W, int H, float beta, const float* img, const float* stats /* planes x SKS_SOFTARGMAX_STATS */,
+                       const float* dL_dxy /* planes x 2 */, float* dL_dimg, void* stream);
+
 /* Pseudo-GT heat-maps of a scene (utils/general_utils.py:175-304 generate_heatmaps + normalize_heatmaps).  The
  * reference filters one 255 impulse per joint plane with cupyx gaussian_filter (V*J full-resolution calls) and
  * min-max normalises each plane; the filtered impulse is separable, so a plane is

@@ -24,6 +24,7 @@ SKS_RAW_GRADS = 128
 SKS_FB_NO_JOIN = 1
 SKS_BIN_GROUPS_SHIFT = 16
 SKS_SSIM_SCRATCH_BYTES = 64 * 8
+SKS_SOFTARGMAX_STATS = 6
 
 
 def SKS_BIN_GROUPS(n):
@@ -105,6 +106,9 @@ SIGNATURES = {
     "sks_knn3_meandist2": (_i, [_i, _vp, _vp, _vp]),
     "sks_knn3_scratch_bytes": (_sz, [_i]),
     "sks_knn3_meandist2_grid": (_i, [_i, _vp, _vp, _vp, _sz, _vp]),
+    "sks_softargmax_scratch_bytes": (_sz, [_i, _i, _i]),
+    "sks_softargmax_fwd": (_i, [_i, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sks_softargmax_bwd": (_i, [_i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "sks_heatmaps": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sks_heatmap_factors": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "sks_heatmap_totals": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
