@@ -73,15 +73,29 @@ HEATMAP_FACTORS_DV_PARAMS = (("V", _i), ("J", _i), ("W", _i), ("H", _i), ("means
                              ("col", _vp), ("cmin", _vp), ("den", _vp), ("frames", _i), ("stream", _vp))
 HEATMAP_TOTALS_DV_PARAMS = (("V", _i), ("J", _i), ("W", _i), ("H", _i), ("row", _vp), ("col", _vp), ("cmin", _vp), ("den", _vp),
                             ("views_dev", _vp), ("gt_totals", _vp), ("stream", _vp))
-_STEP_DV = (("V", _i), ("P", _i), ("C", _i), ("W", _i), ("H", _i)) + _VIEWS_DV + (
-    ("features", _vp), ("scale_modifier", _f), ("flags", _u), ("radii", _vp), ("geom", _vp), ("gt", _vp), ("gt_totals", _vp),
-    ("accum", _vp), ("loss_sums", _vp), ("packed", _vp), ("slots", _vp), ("group_mask", _ull), ("last_view", _i), ("xyz", _vp),
-    ("scaling", _vp), ("rotation", _vp), ("opacity", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("counters", _vp),
-    ("acc_steps", _i), ("lr_sched_dev", _vp), ("lrs", _vp), ("adam", _vp), ("lambda_consistency", _f), ("limb", _vp),
-    ("view_wh", _vp), ("gt_offsets", _vp), ("frames", _i), ("hm_factors", _vp))
+# The optimiser block of the loop's step entry points (sks_loop_adam_step*, sks_loop_fused_step*): one run of every prototype, which
+# loop.py fills from one place per loop; the early-stopping entries append _ES and their host flag(s).  tests/test_cpu.py holds the
+# tables to the header.
+OPTIMISER_PARAMS = (("slots", _vp), ("group_mask", _ull), ("last_view", _i), ("xyz", _vp), ("scaling", _vp), ("rotation", _vp),
+                    ("opacity", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("counters", _vp), ("acc_steps", _i),
+                    ("lr_sched", _vp), ("lrs", _vp), ("adam", _vp), ("lambda_consistency", _f), ("limb", _vp))
+OPTIMISER_DV_PARAMS = tuple(("lr_sched_dev", ct) if name == "lr_sched" else (name, ct) for name, ct in OPTIMISER_PARAMS)
+_ES = (("es_state", _vp), ("es_window", _i), ("es_tolerance", _f))
+ES_PARAMS, ES_FRAMES_PARAMS = _ES + (("es_host_flag", _vp),), _ES + (("es_host_flags", _vp),)
+_ADAM_STEP = (("V", _i), ("P", _i), ("grads", _vp)) + OPTIMISER_PARAMS + (("shard_world", _i),)
+_STEP_RENDER = (("features", _vp), ("scale_modifier", _f), ("flags", _u), ("radii", _vp), ("geom", _vp), ("gt", _vp),
+                ("gt_totals", _vp), ("accum", _vp), ("loss_sums", _vp), ("packed", _vp))
+_STEP_HEATMAPS = (("view_wh", _vp), ("gt_offsets", _vp), ("frames", _i), ("hm_factors", _vp))
+_STEP = _CAMERAS + _STEP_RENDER + OPTIMISER_PARAMS + _STEP_HEATMAPS
+_STEP_DV = (("V", _i), ("P", _i), ("C", _i), ("W", _i), ("H", _i)) + _VIEWS_DV + _STEP_RENDER + OPTIMISER_DV_PARAMS + _STEP_HEATMAPS
+LOOP_ADAM_STEP_PARAMS = _ADAM_STEP + (("stream", _vp),)
+LOOP_ADAM_STEP_ES_PARAMS = _ADAM_STEP + (("loss_sums", _vp),) + ES_PARAMS + (("stream", _vp),)
+LOOP_FUSED_STEP_PARAMS = _STEP + (("stream", _vp),)
+LOOP_FUSED_STEP_ES_PARAMS = _STEP + ES_FRAMES_PARAMS + (("stream", _vp),)
 LOOP_FUSED_STEP_DV_PARAMS = _STEP_DV + (("stream", _vp),)
-LOOP_FUSED_STEP_ES_DV_PARAMS = _STEP_DV + (("es_state", _vp), ("es_window", _i), ("es_tolerance", _f), ("es_host_flags", _vp),
-                                           ("stream", _vp))
+LOOP_FUSED_STEP_ES_DV_PARAMS = _STEP_DV + ES_FRAMES_PARAMS + (("stream", _vp),)
+STEP_PARAMS = {"sks_loop_adam_step": LOOP_ADAM_STEP_PARAMS, "sks_loop_adam_step_es": LOOP_ADAM_STEP_ES_PARAMS,
+               "sks_loop_fused_step": LOOP_FUSED_STEP_PARAMS, "sks_loop_fused_step_es": LOOP_FUSED_STEP_ES_PARAMS}
 DV_PARAMS = {"sks_rig_select": RIG_SELECT_PARAMS, "sks_geometry_dv": GEOMETRY_DV_PARAMS,
              "sks_heatmap_factors_dv": HEATMAP_FACTORS_DV_PARAMS, "sks_heatmap_totals_dv": HEATMAP_TOTALS_DV_PARAMS,
              "sks_loop_fused_step_dv": LOOP_FUSED_STEP_DV_PARAMS, "sks_loop_fused_step_es_dv": LOOP_FUSED_STEP_ES_DV_PARAMS}
@@ -117,20 +131,10 @@ SIGNATURES = {
     "sks_backward_fused_loss": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _u,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sks_loop_pack_grads": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sks_loop_adam_step": (_i, [_i, _i, _vp, _vp, C.c_ulonglong, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp,
-                                _f, _vp, _i, _vp]),
-    "sks_loop_adam_step_es": (_i, [_i, _i, _vp, _vp, C.c_ulonglong, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp,
-                                   _f, _vp, _i, _vp, _vp, _i, _f, _vp, _vp]),
     "sks_loop_shard_floats": (_sz, [_i, _i, _i]),
     "sks_adam_multi": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp]),
-    "sks_loop_fused_step": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                 _vp, C.c_ulonglong, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp,
-                                 _i, _vp, _vp]),
-    "sks_loop_fused_step_es": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                    _vp, C.c_ulonglong, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp,
-                                    _vp, _i, _vp, _vp, _i, _f, _vp, _vp]),
     "sks_triangulate": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    **{name: (_i, [ct for _, ct in params]) for name, params in DV_PARAMS.items()},
+    **{name: (_i, [ct for _, ct in params]) for name, params in {**STEP_PARAMS, **DV_PARAMS}.items()},
     "sks_prof_enable": (_i, [_i]),
     "sks_prof_spin": (_i, [C.c_double, _vp]),
     "sks_prof_read": (_i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),

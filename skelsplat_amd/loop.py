@@ -12,12 +12,16 @@ single all_gather of the (V_local, P, 11) per-view parameter gradients over RCCL
 on every rank, so the mean uses the reference's summation order and every rank takes the identical Adam step
 (no parameter broadcast).  Nothing in the group synchronises with the host.
 """
+import ctypes
+import os
+
 import numpy as np
 
 import torch
 import torch.distributed as dist
 
 from . import rasterizer as R
+from ._group import next_group
 from .scene import DATASETS
 
 
@@ -92,7 +96,58 @@ class NotStopping:
 early_stopping_strategy = {"opt_early_stopping": OptEarlyStopping, "no_stopping": NotStopping}   # utils/__init__.py:31-34
 
 
-class MultiViewLoop:
+def _optimiser_arrays(cfg, dataset, lambda_consistency):
+    """The HOST arrays of the optimiser block (`_sched`, `_lrs`, `_adam`, `_limb`) from a GaussianModel's opt_cfg."""
+    sched = (ctypes.c_double * 5)(cfg["lr_init"], cfg["lr_final"], cfg["lr_delay_mult"],
+                                  float(cfg["lr_delay_steps"]), float(cfg["lr_max_steps"]))
+    lrs = (ctypes.c_double * 3)(cfg["lr_scaling"], cfg["lr_rotation"], cfg["lr_opacity"])
+    adam = (ctypes.c_double * 3)(cfg["betas"][0], cfg["betas"][1], cfg["eps"])
+    limbs = [i for pair in DATASETS[dataset]["limbs"] for i in pair]
+    return sched, lrs, adam, (ctypes.c_int * 8)(*limbs) if lambda_consistency != 0.0 else None
+
+
+class _GroupLoop:
+    """What MultiViewLoop and FrameBatchLoop share: run()'s groups, captured several to a hipGraph (`_enqueue`).  It calls the loop's
+    own `step_group()`, `_device_group(group_mask, last_view, n_iters)` and `_all_stopped()`, and `_after_replay()` after every replay.
+    Each loop also has `_optimiser_block(group_mask, last_view, n_iters)`: _lib.OPTIMISER_PARAMS of one group, tensors as tensors."""
+
+    def _after_replay(self):
+        pass
+
+    def _enqueue(self, iterations, groups_per_graph, graphs=True):
+        """run() without its final synchronisation (FramePipeline drives several loops with it).  With use_graph, while every group
+        is the same one (all views, acc_steps iterations), G = `groups_per_graph` of them are ONE hipGraph: an eager group warms
+        allocations and counts as a real step, G groups are captured, and the graph is replayed while G groups remain."""
+        # The eager group and every replay start by refreshing the geometry from the parameters: nobody has said that they were
+        # left untouched (new_scene(s), eager steps, a caller's write between two runs that capture).
+        if graphs and self.use_graph and self.acc_steps % self.V == 0 and self.iteration % self.acc_steps == 0:
+            key = next_group(self.iteration, self.acc_steps, self.V).key
+            remaining = (iterations - self.iteration) // self.acc_steps
+            G = min(int(groups_per_graph), remaining)
+            if G > 1:
+                if self._multi is None or self._multi[0] != (key, G):
+                    self._geom_valid = False
+                    self._device_group(*key)
+                    self.iteration += self.acc_steps
+                    remaining -= 1
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph):
+                        self._geom_valid = False
+                        for _ in range(G):
+                            self._device_group(*key)
+                    self._multi = ((key, G), graph)
+                while remaining >= G and not self._all_stopped():
+                    self._multi[1].replay()
+                    self.iteration += G * self.acc_steps
+                    remaining -= G
+                    self._after_replay()
+        chained = False       # (between a run's own consecutive groups nobody else touches the parameters)
+        while self.iteration < iterations and not self._all_stopped():
+            self.step_group(parameters_untouched=chained)
+            chained = True
+
+
+class MultiViewLoop(_GroupLoop):
     """One scene.  `heatmaps`: (V,C,H,W) pseudo-GT on this rank's device, or a list of V (C,H_v,W_v) tensors when the
     cameras differ in size (only the local views are read).
     `loss_grad`: callable (render, gt) -> (dL_unscaled, per-view loss, per-view scale); default: the fused HIP kernel
@@ -110,7 +165,6 @@ class MultiViewLoop:
                  bg=None, antialiasing=False, loss_grad=None, group=None, view_grad_fn=None, device_tail=None,
                  use_graph=False, sparse=None, fused_tail=None, shard_views=True, graph_collectives=None,
                  early_stopping="no_stopping", rigs=None):
-        import os
         self.gm = gaussians
         self.dataset = dataset
         self.V = len(cameras)
@@ -143,32 +197,7 @@ class MultiViewLoop:
         self._proj = device_projection_matrices(cameras, dev)
         P = gaussians._xyz.shape[0]
         self.P = P
-        Vl = len(self.local_ids)
-        # Local heat-maps live in ONE flat buffer (rasterizer.HeatmapSet): views of one size are adjacent -- a (Vg,C,H,W)
-        # tensor for the dense entry points -- and the sparse fused step addresses all of them, whatever their sizes,
-        # through per-view offsets in a single launch (H36M mixes 1000x1000 and 1002x1000 sensors, quirk Q11).
-        sizes = [(int(cameras[v].image_width), int(cameras[v].image_height)) for v in self.local_ids]
-        if torch.is_tensor(heatmaps) and heatmaps.dim() == 4 and Vl == self.V and heatmaps.is_contiguous() \
-                and heatmaps.dtype == torch.float32 and len(set(sizes)) == 1:
-            self.hset = R.HeatmapSet.adopt(heatmaps)            # all views local, one size: no copy
-        elif Vl:
-            C_hm = int(heatmaps[self.local_ids[0]].shape[0])
-            self.hset = R.HeatmapSet(sizes, C_hm, heatmaps[self.local_ids[0]].device)
-            for k, v in enumerate(self.local_ids):
-                self.hset.planes[k].copy_(heatmaps[v])
-        else:
-            self.hset = None
-        # size groups: local slots per image size, each one batched launch sequence of the DENSE path (and of the
-        # per-frame heat-map generation); entries: [slots, ViewBatch, gt (Vg,C,H,W), GtStats or None, slot index tensor]
-        self.size_groups = []
-        if self.hset is not None:
-            for key, slots in self.hset.groups.items():
-                vb = (R.ViewBatch.from_cameras([cameras[self.local_ids[k]] for k in slots]) if view_grad_fn is None else None)
-                idx = torch.tensor(slots, dtype=torch.long, device=dev)
-                self.size_groups.append([slots, vb, self.hset.group(key), None, idx])
-        single = len(self.size_groups) == 1
-        self.gt = self.size_groups[0][2] if single else None   # single-size convenience (tests, view_grad_fn)
-        self.views = self.size_groups[0][1] if single else None
+        self._init_heatmaps(heatmaps)
         self.bg = bg
         default_loss = loss_grad is None
         if loss_grad is None and view_grad_fn is None:
@@ -204,77 +233,18 @@ class MultiViewLoop:
         if graph_collectives is None:
             graph_collectives = os.environ.get("SKS_GRAPH_COLLECTIVES") == "1"
         self.use_graph = bool(use_graph) and self.device_tail and (not self.exchange or bool(graph_collectives))
-        self._graph = None
-        self._graphs = {}
+        self._graphs = {}            # step_group's: (group key, chained) -> graph of one group
+        self._multi = None           # run()'s: ((group key, G), graph of G groups)
+        self._rows = None            # the exchange on the host's word: row of view v in a gathered table (_gathered_rows)
         # sparse fused step: render + clamp + masked-L2 + backward only on the tiles some Gaussian rect covers, using
         # per-view statistics of the constant heat-maps (sks_gt_tile_stats); no dense image / gradient is ever written
         if sparse is None:
             sparse = self.device_tail and P <= 64
         self.sparse = bool(sparse) and self.device_tail and P <= 64
-        self.views_all = None        # sparse path: ALL local views in one batch (sizes may differ)
-        self.stats_all = None
-        if self.sparse and Vl:
-            for grp in self.size_groups:
-                grp[3] = R.gt_tile_stats(grp[2])
-            if single:
-                self.views_all, self.stats_all = self.size_groups[0][1], self.size_groups[0][3]
-            else:
-                self.views_all = R.ViewBatch.from_cameras([cameras[v] for v in self.local_ids], allow_mixed=True)
-                st = R.GtStats()
-                st.gt, st.tile_S, st.tile_N = self.hset.flat, None, None
-                st.totals = torch.empty((Vl, 2), dtype=torch.float64, device=dev)
-                st.offsets = self.hset.offsets
-                self.stats_all = st
-                self._merge_totals()
+        self._init_sparse_stats()
         if self.device_tail:
-            import ctypes
-            cfg = gaussians.opt_cfg
-            self._sched = (ctypes.c_double * 5)(cfg["lr_init"], cfg["lr_final"], cfg["lr_delay_mult"],
-                                                float(cfg["lr_delay_steps"]), float(cfg["lr_max_steps"]))
-            self._lrs = (ctypes.c_double * 3)(cfg["lr_scaling"], cfg["lr_rotation"], cfg["lr_opacity"])
-            self._adam = (ctypes.c_double * 3)(cfg["betas"][0], cfg["betas"][1], cfg["eps"])
-            limbs = [i for pair in DATASETS[dataset]["limbs"] for i in pair]
-            self._limb = (ctypes.c_int * 8)(*limbs) if self.lambda_consistency != 0.0 else None
-            self.exp_avg = torch.zeros((P, 11), device=dev)
-            self.exp_avg_sq = torch.zeros((P, 11), device=dev)
-            self.counters = torch.zeros(2, dtype=torch.int32, device=dev)
-            # persistent buffers of the group (allocated here, never inside a graph capture): this rank's packed
-            # raw-parameter gradients -- with the exchange padded to vmax rows, the pad rows stay zero for ever -- and what
-            # all_gather_into_tensor leaves, which sks_loop_adam_step reads in place (rank-major layout, `shard_world`)
-            self._es_state = self._es_flag = None
-            if self._es_device:
-                w = self.early_stopping.window_size
-                self._es_state = torch.zeros(2 + 2 * w, dtype=torch.int32, device=dev)
-                self._es_flag = torch.zeros(1, dtype=torch.int32).pin_memory()
-                self._es_flag_np = self._es_flag.numpy()
-            if self.exchange and self._es_device:
-                # a rank's block = its vmax x P x 11 gradient rows (padded to an even float count) + its views' {S, N} doubles:
-                # gradients and losses cross in ONE all_gather, every rank runs the same criterion (sks_loop_shard_floats)
-                from . import _lib
-                nfl = int(_lib.load().sks_loop_shard_floats(self.V, P, self.world))
-                tail = nfl - 4 * self.vmax
-                self._shard_flat = torch.zeros(nfl, device=dev)
-                self._shard = self._shard_flat[:self.vmax * P * 11].view(self.vmax, P, 11)
-                self._sums = self._shard_flat[tail:].view(torch.float64).view(self.vmax, 2)
-                self._allg = torch.empty(self.world * nfl, device=dev)
-            else:
-                self._shard_flat = None
-                self._shard = torch.zeros((self.vmax if self.exchange else max(Vl, 1), P, 11), device=dev)
-                self._allg = torch.empty((self.world * self.vmax, P, 11), device=dev) if self.exchange else None
-                self._sums = torch.zeros((max(Vl, 1), 2), dtype=torch.float64, device=dev)
-            self._sums_all = (torch.zeros((self.world * self.vmax, 2), dtype=torch.float64, device=dev)
-                              if self.exchange and self._stopping and not self._es_device else None)
-            self._direct = None
-            if self.exchange:
-                # RCCL builds its communicator on the first collective: do that here, eagerly, never inside a graph
-                # capture or a timed step (the gathered rows are overwritten by every group)
-                dist.all_gather_into_tensor(self._allg, self._shard if self._shard_flat is None else self._shard_flat, group=self.group)
-                # ... and, when asked for (SKS_RCCL_DIRECT=1), a communicator of our own, so that the group's one all_gather is
-                # enqueued on the stream its neighbours run on (torch's process group runs it on an internal stream: two event
-                # hand-overs, ~7 us of the GPU timeline per step at world 1); None by default and when the backend is not RCCL
-                if dev.type == "cuda":
-                    from .rccl_direct import DirectGather
-                    self._direct = DirectGather.create(dev, self.group)
+            self._init_device_tail()
+            self._init_exchange_buffers()
         # (without the device tail -- a custom loss_grad / view_grad_fn -- the criterion is a host decision per group: the views'
         # losses ride in the gradients' all_gather as one more column, every rank feeds the same numbers in iteration order)
         # the dense step renders into fresh tensors every group: its forward's fill configuration is measured once per image size
@@ -285,21 +255,121 @@ class MultiViewLoop:
                 for slots, vb, gt, _, idx in self.size_groups:
                     R.tune_forward(vb, gaussians._xyz.detach(), feats, gaussians.get_opacity.detach(), gaussians.get_scaling.detach(),
                                    gaussians.get_rotation.detach(), None, antialiasing=self.antialiasing, clamp01=True)
+        self._init_fused_tail(fused_tail)
+
+    # -- the constructor's steps, in the order they run ------------------------------------------------------------
+    def _init_heatmaps(self, heatmaps):
+        """Heat-map layout and size groups."""
+        # Local heat-maps live in ONE flat buffer (rasterizer.HeatmapSet): views of one size are adjacent -- a (Vg,C,H,W)
+        # tensor for the dense entry points -- and the sparse fused step addresses all of them, whatever their sizes,
+        # through per-view offsets in a single launch (H36M mixes 1000x1000 and 1002x1000 sensors, quirk Q11).
+        cameras, Vl = self.cameras, len(self.local_ids)
+        sizes = [(int(cameras[v].image_width), int(cameras[v].image_height)) for v in self.local_ids]
+        if torch.is_tensor(heatmaps) and heatmaps.dim() == 4 and Vl == self.V and heatmaps.is_contiguous() \
+                and heatmaps.dtype == torch.float32 and len(set(sizes)) == 1:
+            self.hset = R.HeatmapSet.adopt(heatmaps)            # all views local, one size: no copy
+        elif Vl:
+            C_hm = int(heatmaps[self.local_ids[0]].shape[0])
+            self.hset = R.HeatmapSet(sizes, C_hm, heatmaps[self.local_ids[0]].device)
+            for k, v in enumerate(self.local_ids):
+                self.hset.planes[k].copy_(heatmaps[v])
+        else:
+            self.hset = None
+        # size groups: local slots per image size, each one batched launch sequence of the DENSE path (and of the
+        # per-frame heat-map generation); entries: [slots, ViewBatch, gt (Vg,C,H,W), GtStats or None, slot index tensor]
+        self.size_groups = []
+        if self.hset is not None:
+            for key, slots in self.hset.groups.items():
+                vb = (R.ViewBatch.from_cameras([cameras[self.local_ids[k]] for k in slots]) if self.view_grad_fn is None else None)
+                idx = torch.tensor(slots, dtype=torch.long, device=self.device)
+                self.size_groups.append([slots, vb, self.hset.group(key), None, idx])
+        single = len(self.size_groups) == 1
+        self.gt = self.size_groups[0][2] if single else None   # single-size convenience (tests, view_grad_fn)
+        self.views = self.size_groups[0][1] if single else None
+
+    def _init_sparse_stats(self):
+        """Sparse path: the heat-maps' statistics per size group, and ALL local views in one batch (sizes may differ)."""
+        self.views_all = self.stats_all = None
+        if self.sparse and self.local_ids:
+            for grp in self.size_groups:
+                grp[3] = R.gt_tile_stats(grp[2])
+            if len(self.size_groups) == 1:
+                self.views_all, self.stats_all = self.size_groups[0][1], self.size_groups[0][3]
+            else:
+                self.views_all = R.ViewBatch.from_cameras([self.cameras[v] for v in self.local_ids], allow_mixed=True)
+                self.stats_all = R.GtStats.of_set(self.hset)
+                self._merge_totals()
+
+    def _init_device_tail(self):
+        """The optimiser's state on the device (sks_loop_adam_step), and the criterion's when it runs there."""
+        P, dev = self.P, self.device
+        self._sched, self._lrs, self._adam, self._limb = _optimiser_arrays(self.gm.opt_cfg, self.dataset, self.lambda_consistency)
+        self.exp_avg = torch.zeros((P, 11), device=dev)
+        self.exp_avg_sq = torch.zeros((P, 11), device=dev)
+        self.counters = torch.zeros(2, dtype=torch.int32, device=dev)
+        self._es_state = self._es_flag = None
+        if self._es_device:
+            w = self.early_stopping.window_size
+            self._es_state = torch.zeros(2 + 2 * w, dtype=torch.int32, device=dev)
+            self._es_flag = torch.zeros(1, dtype=torch.int32).pin_memory()
+            self._es_flag_np = self._es_flag.numpy()
+
+    def _init_exchange_buffers(self):
+        """The group's gradient and loss buffers, and the exchange's."""
+        # persistent buffers of the group (allocated here, never inside a graph capture): this rank's packed
+        # raw-parameter gradients -- with the exchange padded to vmax rows, the pad rows stay zero for ever -- and what
+        # all_gather_into_tensor leaves, which sks_loop_adam_step reads in place (rank-major layout, `shard_world`)
+        P, dev, Vl = self.P, self.device, len(self.local_ids)
+        if self.exchange and self._es_device:
+            # a rank's block = its vmax x P x 11 gradient rows (padded to an even float count) + its views' {S, N} doubles:
+            # gradients and losses cross in ONE all_gather, every rank runs the same criterion (sks_loop_shard_floats)
+            from . import _lib
+            nfl = int(_lib.load().sks_loop_shard_floats(self.V, P, self.world))
+            tail = nfl - 4 * self.vmax
+            self._shard_flat = torch.zeros(nfl, device=dev)
+            self._shard = self._shard_flat[:self.vmax * P * 11].view(self.vmax, P, 11)
+            self._sums = self._shard_flat[tail:].view(torch.float64).view(self.vmax, 2)
+            self._allg = torch.empty(self.world * nfl, device=dev)
+        else:
+            self._shard_flat = None
+            self._shard = torch.zeros((self.vmax if self.exchange else max(Vl, 1), P, 11), device=dev)
+            self._allg = torch.empty((self.world * self.vmax, P, 11), device=dev) if self.exchange else None
+            self._sums = torch.zeros((max(Vl, 1), 2), dtype=torch.float64, device=dev)
+        self._sums_all = (torch.zeros((self.world * self.vmax, 2), dtype=torch.float64, device=dev)
+                          if self.exchange and self._stopping and not self._es_device else None)
+        self._direct = None
+        if self.exchange:
+            # RCCL builds its communicator on the first collective: do that here, eagerly, never inside a graph
+            # capture or a timed step (the gathered rows are overwritten by every group)
+            dist.all_gather_into_tensor(self._allg, self._shard if self._shard_flat is None else self._shard_flat, group=self.group)
+            # ... and, when asked for (SKS_RCCL_DIRECT=1), a communicator of our own, so that the group's one all_gather is
+            # enqueued on the stream its neighbours run on (torch's process group runs it on an internal stream: two event
+            # hand-overs, ~7 us of the GPU timeline per step at world 1); None by default and when the backend is not RCCL
+            if dev.type == "cuda":
+                from .rccl_direct import DirectGather
+                self._direct = DirectGather.create(dev, self.group)
+
+    def _init_fused_tail(self, fused_tail):
+        """The fused tail: whether it runs, and its persistent geometry."""
         # one GPU, sparse step: the whole group is two launches (sks_loop_fused_step); the geometry of the current
         # parameters lives in a persistent state that every step leaves up to date for the next one
         # (the single-workgroup tail walks the views four at a time: a win for a handful of views -- H36M's 4 --, a loss
         # for Panoptic's 31, where the one-block-per-view kernels stay)
-        self.fused_tail = (self.sparse and not self.exchange and Vl > 0 and bg is None and not self._stopping
+        self.fused_tail = (self.sparse and not self.exchange and len(self.local_ids) > 0 and self.bg is None and not self._stopping
                            and (fused_tail is True or (fused_tail is None and self.V <= 8)))
         self._fstate = None          # persistent ForwardState (geom + radii) of the fused tail
         self._geom_valid = False     # does it describe the current parameters?
         if self.fused_tail:          # persistent buffers are allocated here, never inside a graph capture
             with torch.no_grad():
-                self._fstate = R.geometry_views(self.views_all, gaussians._xyz.detach(),
-                                                gaussians.get_features.reshape(P, -1).shape[1], gaussians._opacity,
-                                                gaussians._scaling, gaussians._rotation, None,
-                                                antialiasing=self.antialiasing, raw_params=True)
+                self._refresh_geometry()
             self._fbuf = (self._shard, self._sums)
+
+    def _refresh_geometry(self):
+        """The fused tail's persistent geometry from the parameters as they are now (in place once it exists)."""
+        gm = self.gm
+        self._fstate = R.geometry_views(self.views_all, gm._xyz.detach(), gm.get_features.reshape(self.P, -1).shape[1], gm._opacity,
+                                        gm._scaling, gm._rotation, None, antialiasing=self.antialiasing, raw_params=True,
+                                        out=self._fstate)
 
     def _merge_totals(self):
         """Mixed sizes: the per-size-group heat-map totals -> the (V_local,2) table of the all-views batch."""
@@ -463,8 +533,7 @@ class MultiViewLoop:
         """[all_gather of the shards ->] sks_loop_adam_step on the view-major (one rank) or rank-major (gathered) table."""
         from . import _lib
         lib = _lib.load()
-        gm, dev = self.gm, self.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = torch.cuda.current_stream(self.device).cuda_stream
         if self.exchange:
             # every rank needs every view's gradients (train.py:175, 215-218): ONE all_gather of the padded shards over
             # RCCL; the optimiser kernel reads the gathered buffer in place (view v = row (v % world) * vmax + v // world)
@@ -476,39 +545,34 @@ class MultiViewLoop:
             full, world = self._allg, self.world
         else:
             full, world = self._shard, 1
+        block = self._optimiser_block(group_mask, last_view, n_iters)      # (this entry point takes its tensors as pointers)
+        args = (self.V, self.P, full.data_ptr(), *[a.data_ptr() if torch.is_tensor(a) else a for a in block], world)
+        step, what = lib.sks_loop_adam_step, "sks_loop_adam_step"
         if self._es_device:
             es = self.early_stopping
-            _lib.check(lib.sks_loop_adam_step_es(self.V, self.P, full.data_ptr(), self.accumulated_grads.data_ptr(), group_mask,
-                                                 last_view, gm._xyz.data_ptr(), gm._scaling.data_ptr(), gm._rotation.data_ptr(),
-                                                 gm._opacity.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                                 self.counters.data_ptr(), n_iters, self._sched, self._lrs, self._adam,
-                                                 float(self.lambda_consistency), self._limb, world,
-                                                 None if world > 1 else self._sums.data_ptr(), self._es_state.data_ptr(),
-                                                 int(es.window_size), float(es.repeat_tolerance), self._es_flag.data_ptr(), stream),
-                       "sks_loop_adam_step_es")
-            return
-        _lib.check(lib.sks_loop_adam_step(self.V, self.P, full.data_ptr(), self.accumulated_grads.data_ptr(), group_mask,
-                                          last_view, gm._xyz.data_ptr(), gm._scaling.data_ptr(), gm._rotation.data_ptr(),
-                                          gm._opacity.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                                          self.counters.data_ptr(), n_iters, self._sched, self._lrs, self._adam,
-                                          float(self.lambda_consistency), self._limb, world, stream), "sks_loop_adam_step")
+            step, what = lib.sks_loop_adam_step_es, "sks_loop_adam_step_es"
+            args += (None if world > 1 else self._sums.data_ptr(), self._es_state.data_ptr(), int(es.window_size),
+                     float(es.repeat_tolerance), self._es_flag.data_ptr())
+        _lib.check(step(*args, stream), what)
 
-    def _device_group(self, group_mask, last_view, n_iters):
-        """forward -> fused masked-L2 -> backward -> pack -> [all_gather] -> Adam, all enqueued, no host sync."""
+    def _optimiser_block(self, group_mask, last_view, n_iters):
+        gm = self.gm
+        return (self.accumulated_grads, group_mask, last_view, gm._xyz, gm._scaling, gm._rotation, gm._opacity, self.exp_avg,
+                self.exp_avg_sq, self.counters, n_iters, self._sched, self._lrs, self._adam, self.lambda_consistency, self._limb)
+
+    def _device_group(self, group_mask, last_view, n_iters, grp=None):
+        """forward -> fused masked-L2 -> backward -> pack -> [all_gather] -> Adam, all enqueued, no host sync.
+        `grp`: the Group the key is of; step_group hands it over for a host criterion, which may cut it."""
         gm, P = self.gm, self.P
         with torch.no_grad():
             if self.fused_tail:
                 feats = gm.get_features.reshape(P, -1)
                 if not self._geom_valid:
-                    self._fstate = R.geometry_views(self.views_all, gm._xyz.detach(), feats.shape[1], gm._opacity, gm._scaling,
-                                                    gm._rotation, None, antialiasing=self.antialiasing, raw_params=True,
-                                                    out=self._fstate)
+                    self._refresh_geometry()
                     self._geom_valid = True
                 packed, sums = self._fbuf
-                R.loop_fused_step(self._fstate, self.stats_all, feats, packed, sums, self.accumulated_grads, group_mask,
-                                  last_view, gm._xyz, gm._scaling, gm._rotation, gm._opacity, self.exp_avg, self.exp_avg_sq,
-                                  self.counters, n_iters, self._sched, self._lrs, self._adam, float(self.lambda_consistency),
-                                  self._limb)
+                R.loop_fused_step(self._fstate, self.stats_all, feats, packed, sums,
+                                  *self._optimiser_block(group_mask, last_view, n_iters))
                 self.last_losses = (sums[:, 0], sums[:, 1])
                 return
             if self.local_ids:
@@ -516,7 +580,7 @@ class MultiViewLoop:
                 Vl = len(self.local_ids)
                 self.last_losses = (self._sums[:Vl, 0], self._sums[:Vl, 1])
             if self._stopping and not self._es_device:
-                group_mask, last_view, n_iters = self._early_stop_cut(group_mask, last_view, n_iters)
+                group_mask, last_view, n_iters = self._early_stop_cut(grp)
             self._device_adam(group_mask, last_view, n_iters)
 
     ES_SYNC_GROUPS = 8      # view-sharded ranks look at the device criterion's flag every this many groups (step_group)
@@ -532,32 +596,40 @@ class MultiViewLoop:
             self.iteration = it
         return self.stopped_at
 
-    def _early_stop_cut(self, group_mask, last_view, n_iters):
+    def _early_stop_cut(self, grp):
         """train.py:155-233 with the group's views batched: feed the criterion the losses of the group's iterations in
         order; if it fires at the k-th, only the first k views' slots are refreshed, view k's scaling / rotation /
-        opacity gradients win, the optimiser steps at once and the scene ends.  One host sync per group."""
+        opacity gradients win, the optimiser steps at once and the scene ends.  One host sync per group.  Returns the key of the
+        group that steps: `grp`'s, cut where the criterion fired."""
         Vl = len(self.local_ids)
         if self.exchange:
             pad = torch.zeros((self.vmax, 2), dtype=torch.float64, device=self.device)
             pad[:Vl] = self._sums[:Vl]
             dist.all_gather_into_tensor(self._sums_all, pad, group=self.group)
-            rows = [(v % self.world) * self.vmax + v // self.world for v in range(self.V)]
-            sums = self._sums_all[rows].cpu()
+            sums = self._sums_all.index_select(0, self._gathered_rows()).cpu()
         else:
             sums = self._sums[:Vl].cpu()
         l2 = (sums[:, 0] / sums[:, 1].clamp_min(1.0)).to(torch.float32)
         cons = torch.zeros((), dtype=torch.float32)
         if self.lambda_consistency != 0.0:
             cons = (limb_3d_consistency_loss(self.gm._xyz.detach(), self.dataset) * self.lambda_consistency).float().cpu()
-        it0 = self.iteration + 1
-        mask = 0
-        for k in range(n_iters):
-            v = (it0 + k - 1) % self.V
-            mask |= 1 << v
+        return self._cut_where_stopped(grp, l2, cons).key
+
+    def _gathered_rows(self):
+        """rank r, slot k  <->  view r + k * world: the row of every view in a gathered table, in view order (built once)."""
+        if self._rows is None:
+            self._rows = torch.tensor([(v % self.world) * self.vmax + v // self.world for v in range(self.V)],
+                                      dtype=torch.long, device=self.device)
+        return self._rows
+
+    def _cut_where_stopped(self, grp, l2, cons):
+        """The host criterion sees the losses of the group's iterations in order; where it fires, the group is cut and the scene ends."""
+        for k, v in enumerate(grp.views):
             if self.early_stopping(float(l2[v] + cons)):
-                self.stopped_at = it0 + k
-                return mask, v, k + 1
-        return group_mask, last_view, n_iters
+                grp = grp.cut(k)
+                self.stopped_at = grp.end
+                break
+        return grp
 
     def step_group(self, parameters_untouched=False):
         """Runs iterations self.iteration+1 .. up to the next optimiser step (train.py:130-222).
@@ -567,37 +639,28 @@ class MultiViewLoop:
         captured graph of several groups does inside).  There is no way to see a write through `.data` or a raw pointer from here,
         so the default is to recompute."""
         gm = self.gm
-        it0 = self.iteration + 1
-        it1 = it0
-        while it1 % self.acc_steps != 0:
-            it1 += 1
-        view_of_iter = [(it - 1) % self.V for it in range(it0, it1 + 1)]   # train.py:136-138
         if self.stopped_at is not None:
             return self.iteration
+        grp = next_group(self.iteration, self.acc_steps, self.V)
         if self.device_tail:
-            mask = 0
-            for v in view_of_iter:
-                mask |= 1 << v
-            key = (mask, view_of_iter[-1], it1 - it0 + 1)
             if self.use_graph:
                 # (two graphs per group shape: one that first refreshes the geometry from the parameters, one -- replayed on the
                 # caller's word, parameters_untouched -- that starts from what the previous group's tail left)
                 chained = bool(parameters_untouched and self.fused_tail and self._geom_valid)
-                gkey = key + (chained,)
+                gkey = grp.key + (chained,)
                 if self._graphs.get(gkey) is None:
                     # capture one group; replays advance the device counters themselves
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph):
                         if not chained:
-                            self._geom_valid = False    # (see run(): a replay never assumes who ran before it)
-                        self._device_group(*key)
+                            self._geom_valid = False    # (see _enqueue: a replay never assumes who ran before it)
+                        self._device_group(*grp.key)
                     self._graphs[gkey] = graph          # the capture itself does not execute: replay below
                 self._graphs[gkey].replay()
-                self._graph = (key, self._graphs[gkey])
             else:
                 if not parameters_untouched:
                     self._geom_valid = False    # eager steps never assume the parameters were left untouched since the last one
-                self._device_group(*key)
+                self._device_group(*grp.key, grp)
             if self._es_device:
                 if self.exchange and self.world > 1:
                     # Sharded: every group holds a collective, so every rank must enqueue the SAME number of groups.  A free-running
@@ -610,7 +673,7 @@ class MultiViewLoop:
                         self._poll_stop(wait=True)
                 else:
                     self._poll_stop()       # (never waits: the groups enqueued behind a stop do nothing to the parameters)
-            self.iteration = it1 if self.stopped_at is None else self.stopped_at
+            self.iteration = grp.end if self.stopped_at is None else self.stopped_at
             return self.iteration
         if not self.local_ids:
             packed, losses = None, None
@@ -628,11 +691,7 @@ class MultiViewLoop:
                 shard[:packed.shape[0], n11] = losses.to(shard.dtype)
             allg = torch.empty((self.world * self.vmax, n11 + 1), device=dev)
             dist.all_gather_into_tensor(allg, shard, group=self.group)
-            # rank r, slot k  <->  view r + k * world: one precomputed row index, view order
-            if getattr(self, "_rows", None) is None:
-                self._rows = torch.tensor([(v % self.world) * self.vmax + v // self.world for v in range(self.V)],
-                                          dtype=torch.long, device=dev)
-            rows = allg.index_select(0, self._rows)
+            rows = allg.index_select(0, self._gathered_rows())
             full, losses_all = rows[:, :n11].reshape(self.V, self.P, 11), rows[:, n11]
         else:
             full, losses_all = packed, losses
@@ -643,15 +702,11 @@ class MultiViewLoop:
             # gradients win, the optimiser steps at once and the scene ends (the same numbers on every rank: the same decision)
             l2 = losses_all.detach().to(torch.float32).cpu()
             cons = torch.zeros((), dtype=torch.float32) if lcons is None else lcons.detach().to(torch.float32).cpu()
-            for k, v in enumerate(view_of_iter):
-                if self.early_stopping(float(l2[v] + cons)):
-                    self.stopped_at = it0 + k
-                    view_of_iter, it1 = view_of_iter[:k + 1], it0 + k
-                    break
+            grp = self._cut_where_stopped(grp, l2, cons)
         # every view's loss contains the consistency term, so every slot carries its gradient (train.py:150-152,175)
-        for v in dict.fromkeys(view_of_iter):
+        for v in dict.fromkeys(grp.views):
             self.accumulated_grads[v] = full[v, :, 0:3] + gcons
-        last = view_of_iter[-1]                                            # quirk Q7: last view's grads win
+        last = grp.last_view                                               # quirk Q7: last view's grads win
         if gm._xyz.grad is None:
             for p in (gm._xyz, gm._scaling, gm._rotation, gm._opacity):
                 p.grad = torch.zeros_like(p)
@@ -659,45 +714,26 @@ class MultiViewLoop:
         gm._rotation.grad = full[last, :, 6:10].contiguous()
         gm._opacity.grad = full[last, :, 10:11].contiguous()
         gm._xyz.grad = self.accumulated_grads.mean(dim=0)                  # train.py:215-218
-        gm.update_learning_rate(it1)                                       # quirk Q9: schedule indexed by iteration
+        gm.update_learning_rate(grp.end)                                   # quirk Q9: schedule indexed by iteration
         with torch.no_grad():
             gm.optimizer.step()
             gm.optimizer.zero_grad(set_to_none=True)
-        self.iteration = it1
+        self.iteration = grp.end
         self.last_losses = losses
-        return it1
+        return grp.end
+
+    def _all_stopped(self):
+        return self.stopped_at is not None
+
+    def _after_replay(self):
+        if self._es_device:
+            self._poll_stop(wait=self.exchange and self.world > 1)     # (sharded: see step_group)
 
     def run(self, iterations=500, groups_per_graph=25):
         """Runs the loop up to `iterations`.  With use_graph, `groups_per_graph` consecutive accumulation groups are
         captured into ONE hipGraph (the step has no host state: counters, LR schedule and Adam live on the device), so
         a 500-iteration scene is a handful of graph launches."""
-        if self.use_graph and self.acc_steps % self.V == 0 and self.iteration % self.acc_steps == 0 \
-                and self.stopped_at is None:
-            mask = (1 << self.V) - 1
-            key = (mask, (self.acc_steps - 1) % self.V, self.acc_steps)
-            remaining = (iterations - self.iteration) // self.acc_steps
-            G = min(int(groups_per_graph), remaining)
-            if G > 1:
-                if getattr(self, "_multi", None) is None or self._multi[0] != (key, G):
-                    self._device_group(*key)            # one eager group: warms allocations, counts as a real step
-                    self.iteration += self.acc_steps
-                    remaining -= 1
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph):
-                        self._geom_valid = False    # every replay starts by refreshing the geometry (new_scene, eager steps)
-                        for _ in range(G):
-                            self._device_group(*key)
-                    self._multi = ((key, G), graph)
-                while remaining >= G and self.stopped_at is None:
-                    self._multi[1].replay()
-                    self.iteration += G * self.acc_steps
-                    remaining -= G
-                    if self._es_device:
-                        self._poll_stop(wait=self.exchange and self.world > 1)     # (sharded: see step_group)
-        chained = False       # (between run()'s own consecutive groups nobody else touches the parameters)
-        while self.iteration < iterations and self.stopped_at is None:
-            self.step_group(parameters_untouched=chained)
-            chained = True
+        self._enqueue(iterations, groups_per_graph, graphs=self.stopped_at is None)
         if self.device_tail and self._es_device and self.stopped_at is None:
             self._poll_stop(wait=True)      # the ONE synchronisation of a scene with the criterion on the device
         return self.gm._xyz.detach()
@@ -750,7 +786,7 @@ def _frame_criterion(early_stopping):
     return int(w), float(es.repeat_tolerance)
 
 
-class FrameBatchLoop:
+class FrameBatchLoop(_GroupLoop):
     """F independent frames, optimised side by side in the sparse fused step -- seen by the SAME cameras (`cameras=`), or each
     by one rig of a bank (`rigs=` a rigs.RigBank; then `new_scenes(..., rig_ids=)` names every frame's rig).
 
@@ -782,7 +818,6 @@ class FrameBatchLoop:
 
     def __init__(self, gaussians, cameras=None, frames=None, dataset="h36m", accumulation_steps=4, lambda_consistency=1e-5,
                  antialiasing=False, use_graph=False, factored=True, early_stopping="no_stopping", rigs=None):
-        import ctypes
         if (cameras is None) == (rigs is None):
             raise ValueError("FrameBatchLoop takes either cameras= (one rig for all frames) or rigs= (a RigBank)")
         if frames is None:
@@ -830,13 +865,7 @@ class FrameBatchLoop:
             self._es_flags_np = self._es_flags.numpy()
         self._packed = torch.zeros((F * V, P, 11), device=dev)
         self._sums = torch.zeros((F * V, 2), dtype=torch.float64, device=dev)
-        cfg = gm.opt_cfg
-        self._sched = (ctypes.c_double * 5)(cfg["lr_init"], cfg["lr_final"], cfg["lr_delay_mult"],
-                                            float(cfg["lr_delay_steps"]), float(cfg["lr_max_steps"]))
-        self._lrs = (ctypes.c_double * 3)(cfg["lr_scaling"], cfg["lr_rotation"], cfg["lr_opacity"])
-        self._adam = (ctypes.c_double * 3)(cfg["betas"][0], cfg["betas"][1], cfg["eps"])
-        limbs = [i for pair in DATASETS[dataset]["limbs"] for i in pair]
-        self._limb = (ctypes.c_int * 8)(*limbs) if self.lambda_consistency != 0.0 else None
+        self._sched, self._lrs, self._adam, self._limb = _optimiser_arrays(gm.opt_cfg, dataset, self.lambda_consistency)
         cams_all = [cameras[k % V] for k in range(F * V)]
         self._cams_all = cams_all
 
@@ -860,11 +889,7 @@ class FrameBatchLoop:
         if self.factored:
             self.views_all = views_of(range(F * V), allow_mixed=True)
             self.factors = R.HeatmapFactors(F * V, self.C, self.views_all.W, self.views_all.H, dev)
-            st = R.GtStats()
-            st.gt, st.tile_S, st.tile_N = None, None, None
-            st.totals = torch.zeros((F * V, 2), dtype=torch.float64, device=dev)
-            st.factors = self.factors
-            self.stats_all = st
+            self.stats_all = R.GtStats.of_factors(self.factors)
         else:
             # planes of all F x V views (frame-major) in one flat buffer; views of one size adjacent (H36M: two sizes)
             self.hset = R.HeatmapSet(sizes, self.C, dev)
@@ -878,11 +903,7 @@ class FrameBatchLoop:
                 self.views_all, self.stats_all = self.size_groups[0][1], self.size_groups[0][3]
             else:
                 self.views_all = views_of(range(F * V), allow_mixed=True)
-                st = R.GtStats()
-                st.gt, st.tile_S, st.tile_N = self.hset.flat, None, None
-                st.totals = torch.zeros((F * V, 2), dtype=torch.float64, device=dev)
-                st.offsets = self.hset.offsets
-                self.stats_all = st
+                self.stats_all = R.GtStats.of_set(self.hset)
         self.rigs, self._sel, self._hf_all = rigs, None, None
         if rigs is not None:
             from .rigs import RigSelection
@@ -991,6 +1012,10 @@ class FrameBatchLoop:
         self.iteration = 0
         return self
 
+    def _optimiser_block(self, group_mask, last_view, n_iters):
+        return (self.accumulated_grads, group_mask, last_view, self.xyz, self.scaling, self.rotation, self.opacity, self.exp_avg,
+                self.exp_avg_sq, self.counters, n_iters, self._sched, self._lrs, self._adam, self.lambda_consistency, self._limb)
+
     def _device_group(self, group_mask, last_view, n_iters):
         with torch.no_grad():
             if not self._geom_valid:
@@ -1000,10 +1025,8 @@ class FrameBatchLoop:
                 self._geom_valid = True
             es = {} if self._es is None else dict(es_state=self._es_state, es_window=self._es[0], es_tolerance=self._es[1],
                                                   es_flags=self._es_flags)
-            R.loop_fused_step(self._fstate, self.stats_all, self.features, self._packed, self._sums, self.accumulated_grads,
-                              group_mask, last_view, self.xyz, self.scaling, self.rotation, self.opacity, self.exp_avg,
-                              self.exp_avg_sq, self.counters, n_iters, self._sched, self._lrs, self._adam,
-                              self.lambda_consistency, self._limb, **es)
+            R.loop_fused_step(self._fstate, self.stats_all, self.features, self._packed, self._sums,
+                              *self._optimiser_block(group_mask, last_view, n_iters), **es)
         s = self._sums.view(self.F, self.V, 2)
         self.last_losses = (s[..., 0], s[..., 1])       # per (frame, view) {S, N}: loss = S / N
 
@@ -1014,15 +1037,8 @@ class FrameBatchLoop:
         once every frame has stopped."""
         if self._all_stopped():
             return self.iteration
-        it0 = self.iteration + 1
-        it1 = it0
-        while it1 % self.acc_steps != 0:
-            it1 += 1
-        view_of_iter = [(it - 1) % self.V for it in range(it0, it1 + 1)]
-        mask = 0
-        for v in view_of_iter:
-            mask |= 1 << v
-        key = (mask, view_of_iter[-1], it1 - it0 + 1)
+        grp = next_group(self.iteration, self.acc_steps, self.V)
+        key = grp.key
         if self.use_graph:
             if self._graph is None or self._graph[0] != key:
                 graph = torch.cuda.CUDAGraph()
@@ -1035,8 +1051,8 @@ class FrameBatchLoop:
             if not parameters_untouched:
                 self._geom_valid = False
             self._device_group(*key)
-        self.iteration = it1
-        return it1
+        self.iteration = grp.end
+        return grp.end
 
     @property
     def stopped_at(self):
@@ -1065,33 +1081,6 @@ class FrameBatchLoop:
         stream has been synchronised, which run() with early stopping does itself."""
         if self._sel is not None:
             self._sel.check()
-
-    def _enqueue(self, iterations, groups_per_graph):
-        """run() without its final synchronisation (FramePipeline drives several loops with it)."""
-        if self.use_graph and self.acc_steps % self.V == 0 and self.iteration % self.acc_steps == 0:
-            key = ((1 << self.V) - 1, (self.acc_steps - 1) % self.V, self.acc_steps)
-            remaining = (iterations - self.iteration) // self.acc_steps
-            G = min(int(groups_per_graph), remaining)
-            if G > 1:
-                if self._multi is None or self._multi[0] != (key, G):
-                    self._geom_valid = False
-                    self._device_group(*key)
-                    self.iteration += self.acc_steps
-                    remaining -= 1
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph):
-                        self._geom_valid = False
-                        for _ in range(G):
-                            self._device_group(*key)
-                    self._multi = ((key, G), graph)
-                while remaining >= G and not self._all_stopped():
-                    self._multi[1].replay()
-                    self.iteration += G * self.acc_steps
-                    remaining -= G
-        chained = False
-        while self.iteration < iterations and not self._all_stopped():
-            self.step_group(parameters_untouched=chained)
-            chained = True
 
     def _next_batch(self, pts, p2d, b, initial=None, rig_ids=None):
         """new_scenes for the frames b .. b + F of a sequence (a short last batch is filled up by repeating its final

@@ -16,6 +16,28 @@ class GtStats:
         self.offsets = None
         self.factors = None      # HeatmapFactors: the heat-maps in separable form, no planes (then gt is None)
 
+    @classmethod
+    def _all_views(cls, V, device):
+        """No per-tile arrays; a zeroed (V,2) `totals` table the caller has filled per scene."""
+        st = cls()
+        st.gt = st.tile_S = st.tile_N = None
+        st.totals = torch.zeros((V, 2), dtype=torch.float64, device=device)
+        return st
+
+    @classmethod
+    def of_set(cls, hset):
+        """All views of a HeatmapSet, whatever their sizes, in one batch: its flat buffer and per-view offsets."""
+        st = cls._all_views(len(hset.sizes), hset.flat.device)
+        st.gt, st.offsets = hset.flat, hset.offsets
+        return st
+
+    @classmethod
+    def of_factors(cls, factors):
+        """The views of a HeatmapFactors: no planes at all."""
+        st = cls._all_views(factors.V, factors.row.device)
+        st.factors = factors
+        return st
+
 
 class HeatmapFactors:
     """The pseudo-GT heat-maps of V views in SEPARABLE form -- plane(v, j) = (row[v,j][:, None] * col[v,j][None, :] -

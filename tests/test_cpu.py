@@ -260,6 +260,51 @@ def test_recorded_layouts_are_the_headers():
     assert _lib.FWD["stream"] == len(_lib.FWD) - 1 and _lib.BWD["stream"] == len(_lib.BWD) - 1      # (rasterizer._replay's default)
 
 
+def test_step_tables_are_the_headers():
+    """The by-value step entry points (sks_loop_adam_step / _es, sks_loop_fused_step / _es) take their signatures from named tables
+    of skelsplat_amd._lib: the tables are the header's prototypes, name for name, type for type and in order; and the optimiser
+    block, which loop.py fills from one place, is one contiguous run of all six step prototypes (the *_dv ones name the schedule
+    `lr_sched_dev`: it lives on the device there), followed in the early-stopping entries by the criterion's suffix."""
+    import ctypes
+    from skelsplat_amd import _lib
+    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "skelsplat_hip.h")).read(), flags=re.S)
+    scalars = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
+               "unsigned long long": ctypes.c_ulonglong}
+
+    def prototype(symbol):
+        proto = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % symbol, hdr).group(1)
+        out = []
+        for param in proto.split(","):
+            ctype, name = re.fullmatch(r"\s*(.*?)(\w+)\s*", param, flags=re.S).groups()
+            out.append((name, ctypes.c_void_p if "*" in ctype else scalars[" ".join(ctype.split())]))
+        return out
+
+    def run_at(block, proto):
+        """Where `block` sits in `proto` as a contiguous run (exactly once)."""
+        at = [i for i in range(len(proto) - len(block) + 1) if proto[i:i + len(block)] == list(block)]
+        assert len(at) == 1, (block[0], at)
+        return at[0]
+    assert set(_lib.STEP_PARAMS) == {"sks_loop_adam_step", "sks_loop_adam_step_es", "sks_loop_fused_step", "sks_loop_fused_step_es"}
+    for symbol, table in _lib.STEP_PARAMS.items():
+        assert prototype(symbol) == list(table), symbol
+        assert _lib.SIGNATURES[symbol] == (ctypes.c_int, [ct for _, ct in table])
+    assert [n for n, _ in _lib.OPTIMISER_PARAMS] == ["slots", "group_mask", "last_view", "xyz", "scaling", "rotation", "opacity",
+                                                     "exp_avg", "exp_avg_sq", "counters", "acc_steps", "lr_sched", "lrs", "adam",
+                                                     "lambda_consistency", "limb"]
+    assert [(n.replace("lr_sched_dev", "lr_sched"), ct) for n, ct in _lib.OPTIMISER_DV_PARAMS] == list(_lib.OPTIMISER_PARAMS)
+    assert [n for n, _ in _lib.ES_PARAMS] == ["es_state", "es_window", "es_tolerance", "es_host_flag"]
+    assert [n for n, _ in _lib.ES_FRAMES_PARAMS] == ["es_state", "es_window", "es_tolerance", "es_host_flags"]
+    for symbol in _lib.STEP_PARAMS:
+        run_at(_lib.OPTIMISER_PARAMS, prototype(symbol))
+    for symbol in ("sks_loop_fused_step_dv", "sks_loop_fused_step_es_dv"):
+        run_at(_lib.OPTIMISER_DV_PARAMS, prototype(symbol))
+    for symbol, suffix in (("sks_loop_adam_step_es", _lib.ES_PARAMS), ("sks_loop_fused_step_es", _lib.ES_FRAMES_PARAMS),
+                           ("sks_loop_fused_step_es_dv", _lib.ES_FRAMES_PARAMS)):
+        proto = prototype(symbol)
+        assert run_at(suffix, proto) == len(proto) - len(suffix) - 1 and proto[-1] == ("stream", ctypes.c_void_p), symbol
+    assert _lib.load().sks_version() == 14
+
+
 def test_product_refuses_cpu_tensors_and_bad_arguments():
     from diff_gaussian_rasterization_h36m import GaussianRasterizationSettings, GaussianRasterizer
     import gaussian_renderer

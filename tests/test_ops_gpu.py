@@ -580,6 +580,34 @@ def test_scene_streaming_reuses_graphs(device, sparse):
         assert torch.equal(a.detach(), b.detach())
 
 
+def test_run_that_captures_again_sees_the_callers_write(device):
+    """run() with another `groups_per_graph` captures again, and the eager group that warms the capture is a real step: on the fused
+    tail it must refresh the geometry from the parameters, which the caller has written since the last run -- nobody told the
+    loop otherwise.  Graph run against eager step_group()s through the same write: the same bits."""
+    from skelsplat_amd.loop import MultiViewLoop
+    from skelsplat_amd.heatmaps import generate_heatmaps
+    sc, model = _make_loop_scene(device)
+    gma, gmb = model(device), model(device)
+    hm = generate_heatmaps(gma._xyz.detach(), gma.get_scaling.detach(), gma._rotation.detach(),
+                           torch.tensor(sc.poses_2d, device=device), sc.cameras)
+    a = MultiViewLoop(gma, sc.cameras, hm, dataset="h36m", sparse=True, use_graph=True)
+    b = MultiViewLoop(gmb, sc.cameras, hm, dataset="h36m", sparse=True, use_graph=False)
+    assert a.fused_tail
+    a.run(12, groups_per_graph=2)
+    for _ in range(3):
+        b.step_group()
+    assert a._multi[0][1] == 2 and a.iteration == b.iteration == 12
+    with torch.no_grad():
+        gma._xyz.data += 3.0
+        gmb._xyz.data += 3.0
+    a.run(28, groups_per_graph=3)
+    for _ in range(4):
+        b.step_group()
+    assert a._multi[0][1] == 3 and a.iteration == b.iteration == 28        # (captured again: one eager group, one replay of three)
+    for pa, pb in ((gma._xyz, gmb._xyz), (gma._scaling, gmb._scaling), (gma._rotation, gmb._rotation), (gma._opacity, gmb._opacity)):
+        assert torch.equal(pa.detach(), pb.detach())
+
+
 def test_fused_step_tail_many_views(device):
     """The single-workgroup tail walks the views four at a time: 7 views of a 19-joint skeleton (two rounds, the second
     one partial) still equal the separate kernels bit for bit."""
