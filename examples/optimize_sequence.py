@@ -2,12 +2,15 @@
 """A whole synthetic SEQUENCE through the hot path, the way the reference's train.py walks a dataset (one frame after the
 other, train.py:74-99) -- but many frames per launch: noisy 2D detections of N frames -> DLT initial guesses -> 500
 iterations of the multi-view loop for every frame (loop.FramePipeline) -> MPJPE per frame.
-python examples/optimize_sequence.py [--frames 64] [--per-launch 16] [--streams 2] [--iters 500] [--init host|device] [--rigs R]
+python examples/optimize_sequence.py [--frames 64] [--per-launch 16] [--streams 2] [--iters 500] [--init host|device|fuse] [--rigs R]
 --rigs R: the frames cycle through R jittered ring rigs (SyntheticScene seeds 0 .. R-1), as a dataset whose scenes bring their own
 cameras does; one rigs.RigBank holds them on the device and every batch names its frames' rigs (rig_ids).
 --init host (default): the DLT runs on the host, frame by frame, and its points are uploaded; --init device: the detections
-go to the device once and every batch is triangulated there (FramePipeline.optimize_sequence(None, ...)); the timed region
-runs from the detections to the joints either way."""
+go to the device once and every batch is triangulated there (FramePipeline.optimize_sequence(None, ...)); --init fuse: the
+reference's "metrabs" guess instead of the DLT -- synthetic monocular 3D predictions of every view (ground truth + 20-50 mm of
+noise per view) go to the device once with the detections, and every batch starts from their reprojection-error-weighted mean
+(initial_guess.fuse_predictions through optimize_sequence(None, ..., poses_3d=...)).  The timed region runs from the detections
+(and predictions) to the joints every way."""
 import argparse
 import os
 import sys
@@ -30,7 +33,7 @@ def main():
     ap.add_argument("--per-launch", type=int, default=16)
     ap.add_argument("--streams", type=int, default=2)
     ap.add_argument("--iters", type=int, default=500)
-    ap.add_argument("--init", choices=("host", "device"), default="host")
+    ap.add_argument("--init", choices=("host", "device", "fuse"), default="host")
     ap.add_argument("--rigs", type=int, default=1)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -62,6 +65,12 @@ def main():
     if args.init == "device":
         p2d_dev = torch.as_tensor(p2d, device=dev)
         run = lambda: pipe.optimize_sequence(None, p2d_dev, iterations=args.iters, return_initial=True, **ids)
+    elif args.init == "fuse":
+        sigma = np.linspace(20.0, 50.0, args.views)[:, None, None]
+        p3d = np.stack([gt[f][None] + rng.normal(0, 1.0, (args.views,) + gt[f].shape) * sigma
+                        for f in range(args.frames)]).astype(np.float32)
+        p2d_dev, p3d_dev = torch.as_tensor(p2d, device=dev), torch.as_tensor(p3d, device=dev)
+        run = lambda: pipe.optimize_sequence(None, p2d_dev, iterations=args.iters, return_initial=True, poses_3d=p3d_dev, **ids)
     else:
         def run():
             init = host_init()
@@ -78,7 +87,8 @@ def main():
     e1 = np.mean([io.mpjpe(pred[f], gt[f]) for f in range(args.frames)])
     print(f"{args.dataset} V={args.views} {sc.W}x{sc.H}: {args.frames} frames x {args.iters} iterations in {dt * 1e3:.1f} ms "
           f"({args.frames / dt:.0f} frames/s, {args.per_launch} frames per launch on {args.streams} streams, {args.rigs} rig(s)); "
-          f"mean MPJPE {e0:.2f} mm (DLT on the {args.init}) -> {e1:.2f} mm")
+          f"mean MPJPE {e0:.2f} mm ({'fused predictions on the device' if args.init == 'fuse' else f'DLT on the {args.init}'}) "
+          f"-> {e1:.2f} mm")
 
 
 if __name__ == "__main__":

@@ -261,6 +261,29 @@ int sks_triangulate(int N, int V, int J, const double* proj, size_t rig_stride, 
                     const double* poses_2d_f64, const unsigned char* valid, float* xyz, double* xyzw, int* n_used,
                     void* stream);
 
+/* Initial joints of N frames as the reprojection-error-weighted mean of the V views' monocular 3D predictions, one launch
+ * (reference: compute_weighted_average_pose, dataset_tools/h36m/compute_initial_guess.py:23-116 and dataset_tools/panoptic/
+ * compute_initial_guess_panoptic.py:23-117 -- the configs' initial_guess "metrabs" / "metrabs_occ_3").  Per (frame, joint), with
+ * candidate X_i = view i's prediction: u_ic = the pixel of P_c [X_i; 1] (no test for points behind a camera), e_ic = |u_ic - x_c|,
+ * ebar_i = mean over c, w_i = (1 / ebar_i) / sum_k (1 / ebar_k), result = sum_i w_i X_i / sum_i w_i.  Added to sks_version 14: the
+ * number did not move (a caller that must know looks the symbol up).
+ * proj, rig_stride, valid: as sks_triangulate takes them; the predictions (N,V,J,3), world coordinates, as float (poses_3d) or as
+ * double (poses_3d_f64), exactly one of the two; the detections (N,V,J,2) likewise; float inputs are widened exactly.
+ * valid[n,v,j] == 0 takes view v out of joint j of frame n in both roles: its candidate gets no weight and its detection enters
+ * no ebar_i, whose mean then divides by the number of kept views.
+ * norm_f32 == 0: everything is float64 (the H36M script).  != 0: u - x is rounded to float32, the norm, the mean over cameras,
+ * the reciprocal and the normalisation are float32, the average multiplies the float64 candidates by the float32 weights and
+ * accumulates in float64 (the Panoptic script).
+ * outputs, at least one of the first two: xyz (N,J,3) float -- what the loop consumes, xyz_f64 rounded to nearest --, xyz_f64
+ * (N,J,3) double; optional reproj_err (N,V,J) double = ebar_i (NaN for a view left out), n_used (N,J) = kept views.  A joint with
+ * n_used == 0 comes back NaN, with n_used == 1 it is that candidate; ebar_i == 0 follows IEEE as the reference does (inf weight,
+ * NaN result).  1 <= V <= SKS_MAX_VIEWS.  The sums over cameras and over candidates run in index order (numpy's order for ebar):
+ * a joint's result depends on V and its own inputs only, never on N, on its place in the batch or on the stream. */
+int sks_fuse_predictions(int N, int V, int J, const double* proj, size_t rig_stride, const float* poses_3d,
+                         const double* poses_3d_f64, const float* poses_2d, const double* poses_2d_f64,
+                         const unsigned char* valid, int norm_f32, float* xyz, double* xyz_f64, double* reproj_err,
+                         int* n_used, void* stream);
+
 /* Replaces fusedssim (submodules/fused-ssim/ssim.cu:368-404, binding ext.cpp): img1, img2, ssim_map and the three
  * optional partial-derivative maps (train == true) are (B,CH,H,W) fp32; "same" zero padding. */
 int sks_fused_ssim_fwd(int B, int CH, int H, int W, float C1, float C2, const float* img1, const float* img2,

@@ -377,7 +377,7 @@ class MultiViewLoop(_GroupLoop):
             self.stats_all.totals.index_copy_(0, idx, stats.totals)
 
     # -- scene streaming ---------------------------------------------------------------------------------------
-    def new_scene(self, points, poses_2d=None, heatmaps=None, dropout=False):
+    def new_scene(self, points, poses_2d=None, heatmaps=None, dropout=False, poses_3d=None):
         """Next frame seen by the SAME cameras (the reference's outer loop, train.py:74-99: new GaussianModel, new
         heat-maps, iteration counter back to 0).  Everything is re-initialised in place -- parameters, Adam moments,
         step counters, V-slot buffer, heat-maps and their tile statistics keep their storage -- so the hipGraphs
@@ -386,10 +386,15 @@ class MultiViewLoop(_GroupLoop):
         `points=None`: the initial joints are the DLT triangulation of `poses_2d` (triangulation.triangulate_sequence, on
         the device, on the current stream; with `dropout` the dropped planes' detections stay out of it).  It needs all V
         views' detections, so a view-sharded loop (world > 1) refuses it; a joint kept in fewer than two views has no
-        triangulation and starts as NaN."""
+        triangulation and starts as NaN.
+        `poses_3d` (V,J,3), with `points=None`: the initial joints are instead the reprojection-error-weighted mean of the
+        views' 3D predictions (initial_guess.fuse_predictions, the reference's "metrabs" guess), under the same conditions; a
+        joint whose views are all dropped starts as NaN.  Together with explicit `points` it is refused."""
         from .heatmaps import generate_heatmaps
         gm = self.gm
         if points is not None:
+            if poses_3d is not None:
+                raise ValueError("new_scene: poses_3d are fused into the initial joints when points is None; give one of the two")
             gm.reset_from_points(points)
         else:
             if poses_2d is None:
@@ -424,7 +429,14 @@ class MultiViewLoop(_GroupLoop):
                 p2d = torch.as_tensor(poses_2d, device=self.device)
                 if p2d.dim() != 3 or tuple(p2d.shape[:2]) != (self.V, self.P):
                     raise ValueError(f"poses_2d must be (V,J,2) = {(self.V, self.P, 2)}, got {tuple(p2d.shape)}")
-                gm.reset_from_points(triangulate_sequence(self._proj, p2d, valid=None if drop is None else ~drop))
+                if poses_3d is not None:
+                    from .initial_guess import fuse_predictions
+                    p3d = torch.as_tensor(poses_3d, device=self.device)
+                    if tuple(p3d.shape) != (self.V, self.P, 3):
+                        raise ValueError(f"poses_3d must be (V,J,3) = {(self.V, self.P, 3)}, got {tuple(p3d.shape)}")
+                    gm.reset_from_points(fuse_predictions(self._proj, p3d, p2d, valid=None if drop is None else ~drop))
+                else:
+                    gm.reset_from_points(triangulate_sequence(self._proj, p2d, valid=None if drop is None else ~drop))
             for grp in self.size_groups:
                 slots, vb, gt, stats, idx = grp
                 ids = [self.local_ids[k] for k in slots]
@@ -750,6 +762,18 @@ def _sequence_inputs(points, poses_2d):
     return pts, p2d, pts.shape[0]
 
 
+def _sequence_predictions(points, poses_3d, N):
+    """optimize_sequence's `poses_3d` -> None or the (N,V,J,3) predictions as a tensor where they are (arrays: on the host)."""
+    if poses_3d is None:
+        return None
+    if points is not None:
+        raise ValueError("optimize_sequence: poses_3d are fused into the initial joints when points is None; give one of the two")
+    p3d = poses_3d if torch.is_tensor(poses_3d) else torch.as_tensor(np.asarray(poses_3d))
+    if p3d.dim() != 4 or p3d.shape[0] != N or p3d.shape[-1] != 3:
+        raise ValueError(f"poses_3d must be (N,V,J,3) with N = {N} frames like poses_2d, got {tuple(p3d.shape)}")
+    return p3d
+
+
 def _sequence_rig_ids(sel, rig_ids, N):
     """optimize_sequence's `rig_ids` -> None or an (N,) integer tensor on the device: host ids are validated against the bank
     and uploaded once per sequence; a device tensor is taken as it is (the gather kernel checks its bounds)."""
@@ -922,7 +946,7 @@ class FrameBatchLoop(_GroupLoop):
         self.iteration = 0
         self.last_losses = None
 
-    def new_scenes(self, points, poses_2d=None, heatmaps=None, drop_masks=None, rig_ids=None):
+    def new_scenes(self, points, poses_2d=None, heatmaps=None, drop_masks=None, rig_ids=None, poses_3d=None):
         """The next F frames: `points` (F,P,3) initial joints; either `poses_2d` (F,V,J,2) -- the heat-maps are generated
         from the re-initialised Gaussians like general_utils.py:175-304, all frames in two launches per image size -- or
         ready `heatmaps` (F,V,C,H,W) / a list of F lists of V (C,H_v,W_v) planes.  `drop_masks`: optional (F,V,J) bool of
@@ -933,6 +957,10 @@ class FrameBatchLoop(_GroupLoop):
         them: detections already on the device never touch the host.  `drop_masks` are then also the DLT's
         `valid = ~drop_masks` -- a dropped plane is a detection the caller does not trust --, and a joint kept in fewer than
         two views has no triangulation: it starts as NaN.  Ready `heatmaps` carry no detections: refused.
+        `poses_3d` (F,V,J,3), with `points=None`: the initial joints are instead the reprojection-error-weighted mean of the
+        views' 3D predictions (initial_guess.fuse_predictions, the reference's "metrabs" guess), written into `self.xyz` by one
+        launch in the same place with the same `valid = ~drop_masks`; a joint whose views are all dropped starts as NaN.
+        Together with explicit `points` it is refused.
         `rig_ids` (F,) ints, host or device (a loop over a rig bank): frame f is seen by rig rig_ids[f] -- one gather launch on
         the current stream fills the batch's camera rows, per-view scalars, projection matrices and schedule rows in place, in
         front of the triangulation and the heat-map factors that read them.  Host ids are validated here; ids in a device
@@ -960,7 +988,14 @@ class FrameBatchLoop(_GroupLoop):
                 if p2d_dlt.dim() != 4 or tuple(p2d_dlt.shape[:3]) != (F, V, P) or p2d_dlt.shape[3] < 2:
                     raise ValueError(f"poses_2d must be (F,V,J,2) = {(F, V, P, 2)}, got {tuple(p2d_dlt.shape)}")
                 poses_2d = p2d_dlt[..., :2]
+                if poses_3d is not None:
+                    p3d = torch.as_tensor(poses_3d, device=self.device)
+                    if tuple(p3d.shape) != (F, V, P, 3):
+                        raise ValueError(f"poses_3d must be (F,V,J,3) = {(F, V, P, 3)}, got {tuple(p3d.shape)}")
             else:
+                if poses_3d is not None:
+                    raise ValueError("new_scenes: poses_3d are fused into the initial joints when points is None; give one of "
+                                     "the two")
                 pts = points if torch.is_tensor(points) else torch.as_tensor(np.asarray(points))
                 if tuple(pts.shape) != (F, P, 3):
                     raise ValueError(f"points must be (F,P,3) = {(F, P, 3)}, got {tuple(pts.shape)}")
@@ -973,7 +1008,12 @@ class FrameBatchLoop(_GroupLoop):
                 self._es_state.zero_()
             if points is None:
                 keep = None if drop_masks is None else ~torch.as_tensor(drop_masks).to(device=self.device, dtype=torch.bool)
-                triangulate_sequence(self._proj, p2d_dlt, valid=None if keep is None else keep.reshape(F, V, P), out=self.xyz)
+                keep = None if keep is None else keep.reshape(F, V, P)
+                if poses_3d is not None:
+                    from .initial_guess import fuse_predictions
+                    fuse_predictions(self._proj, p3d, p2d_dlt, valid=keep, out=self.xyz)
+                else:
+                    triangulate_sequence(self._proj, p2d_dlt, valid=keep, out=self.xyz)
             else:
                 self.xyz.copy_(pts.to(device=self.device, dtype=torch.float32))
             self.scaling.copy_(self._init[0].expand(F, P, 3))
@@ -1082,36 +1122,43 @@ class FrameBatchLoop(_GroupLoop):
         if self._sel is not None:
             self._sel.check()
 
-    def _next_batch(self, pts, p2d, b, initial=None, rig_ids=None):
+    def _next_batch(self, pts, p2d, b, initial=None, rig_ids=None, p3d=None):
         """new_scenes for the frames b .. b + F of a sequence (a short last batch is filled up by repeating its final
         frame, rig included); `pts` None: triangulated from the detections.  `initial` (N,P,3): receives the batch's initial
-        joints.  `rig_ids`: None or the sequence's (N,) ids as _sequence_rig_ids left them."""
+        joints.  `rig_ids`: None or the sequence's (N,) ids as _sequence_rig_ids left them.  `p3d`: None or the sequence's
+        (N,V,J,3) predictions, fused into the initial joints instead of the triangulation (`pts` None)."""
         N, F = p2d.shape[0], self.F
         if b + F <= N:      # a full batch: views of the inputs, no gather
             self.new_scenes(None if pts is None else pts[b:b + F], poses_2d=p2d[b:b + F],
-                            rig_ids=None if rig_ids is None else rig_ids[b:b + F])
+                            rig_ids=None if rig_ids is None else rig_ids[b:b + F],
+                            poses_3d=None if p3d is None else p3d[b:b + F])
         else:
             idx = [min(b + i, N - 1) for i in range(F)]
             self.new_scenes(None if pts is None else pts[idx], poses_2d=p2d[idx],
-                            rig_ids=None if rig_ids is None else rig_ids[idx])
+                            rig_ids=None if rig_ids is None else rig_ids[idx],
+                            poses_3d=None if p3d is None else p3d[idx])
         if initial is not None:
             initial[b:min(b + F, N)] = self.xyz[:min(F, N - b)]
 
-    def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, return_initial=False, rig_ids=None):
+    def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, return_initial=False, rig_ids=None,
+                          poses_3d=None):
         """The reference's outer loop over the frames of a sequence (train.py:74-99) F frames at a time: `points`
         (N,P,3) initial joints and `poses_2d` (N,V,J,2) detections of N frames -> (N,P,3) optimised joints.  A last batch
         with fewer than F frames is filled up by repeating its final frame (frames are independent: the filler changes
         nothing and is dropped).  `points=None`: every batch's initial joints are triangulated from its detections on
         the device (new_scenes); `poses_2d` may be a device tensor and is then never copied to the host.
         `return_initial=True`: returns (joints, initial joints), both (N,P,3) on the device.
-        `rig_ids` (N,) ints, host or device (a loop over a rig bank): the rig of every frame, see new_scenes."""
+        `rig_ids` (N,) ints, host or device (a loop over a rig bank): the rig of every frame, see new_scenes.
+        `poses_3d` (N,V,J,3), with `points=None`: every batch's initial joints are fused from the views' 3D predictions
+        instead (new_scenes); a device tensor is never copied to the host."""
         pts, p2d, N = _sequence_inputs(points, poses_2d)
+        p3d = _sequence_predictions(points, poses_3d, N)
         ids = _sequence_rig_ids(self._sel, rig_ids, N)
         F = self.F
         out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
         initial = torch.empty_like(out) if return_initial else None
         for b in range(0, N, F):
-            self._next_batch(pts, p2d, b, initial, ids)
+            self._next_batch(pts, p2d, b, initial, ids, p3d)
             res = self.run(iterations, groups_per_graph)
             out[b:min(b + F, N)] = res[:min(F, N - b)]
         self.check_rigs()
@@ -1139,7 +1186,7 @@ class FramePipeline:
         self.stopped_at = None       # early stopping: (N,) int64 of the last optimize_sequence, 0 = ran to the end
 
     def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, interleave=100,
-                          return_initial=False, rig_ids=None):
+                          return_initial=False, rig_ids=None, poses_3d=None):
         """(N,P,3) initial joints + (N,V,J,2) detections -> (N,P,3) optimised joints (train.py:74-99 over the frames).
         The loops' graph launches are issued round-robin, `interleave` iterations at a time, so that every stream always
         has work queued; a last batch with fewer than `frames` frames is padded by repeating its final frame.
@@ -1147,8 +1194,11 @@ class FramePipeline:
         stream (FrameBatchLoop.new_scenes), behind whatever the caller's stream did to `poses_2d`; detections given as a
         device tensor are never copied to the host.  `return_initial=True`: returns (joints, initial joints).
         `rig_ids` (N,) ints, host or device (loops over a rig bank, `rigs=`): the rig of every frame, see
-        FrameBatchLoop.new_scenes; check_rigs() reports an id a device tensor held outside the bank."""
+        FrameBatchLoop.new_scenes; check_rigs() reports an id a device tensor held outside the bank.
+        `poses_3d` (N,V,J,3), with `points=None`: every batch's initial joints are fused from the views' 3D predictions
+        instead of triangulated, by one launch in the same place (initial_guess.fuse_predictions)."""
         pts, p2d, N = _sequence_inputs(points, poses_2d)
+        p3d = _sequence_predictions(points, poses_3d, N)
         ids = _sequence_rig_ids(self.loops[0]._sel, rig_ids, N)     # (uploaded on the caller's stream, which every stream waits for)
         F, S = self.F, len(self.loops)
         out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
@@ -1159,7 +1209,7 @@ class FramePipeline:
             self.stopped_at = torch.zeros(N, dtype=torch.int64, device=self.device)
             for st in self.streams:
                 st.wait_stream(cur)
-            self._sequence_es(pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial, ids)
+            self._sequence_es(pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial, ids, p3d)
             for st in self.streams:
                 cur.wait_stream(st)
             self.check_rigs()
@@ -1170,7 +1220,7 @@ class FramePipeline:
             active = list(zip(self.loops, self.streams, starts[w:w + S]))
             for fb, st, b in active:
                 with torch.cuda.stream(st):
-                    fb._next_batch(pts, p2d, b, initial, ids)
+                    fb._next_batch(pts, p2d, b, initial, ids, p3d)
             for k in range(0, iterations, max(int(interleave), 1)):
                 for fb, st, b in active:
                     with torch.cuda.stream(st):
@@ -1188,7 +1238,8 @@ class FramePipeline:
         for fb in self.loops:
             fb.check_rigs()
 
-    def _sequence_es(self, pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial=None, rig_ids=None):
+    def _sequence_es(self, pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial=None, rig_ids=None,
+                     p3d=None):
         """optimize_sequence with early stopping: every stream keeps its own batch and takes the next one as soon as its
         batch is done -- all frames stopped (seen in the pinned flags, without waiting) or `iterations` enqueued -- instead
         of waiting for the other streams' batches.  Results and stopping iterations are copied on the batch's stream."""
@@ -1200,7 +1251,7 @@ class FramePipeline:
             if b is None:
                 return None
             with torch.cuda.stream(st):
-                fb._next_batch(pts, p2d, b, initial, rig_ids)
+                fb._next_batch(pts, p2d, b, initial, rig_ids, p3d)
             return [fb, st, b, 0]
 
         step = max(int(interleave), 1)
