@@ -20,7 +20,10 @@ _LIB = None
 def build(force=False):
     so = os.path.join(_HERE, "libsks_oracle.so")
     srcs = [os.path.join(_HERE, f) for f in ("sks_oracle.c",)]
-    if force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+    # the Makefile's other targets (the fused-SSIM oracle, oracle/ssim_ref.py) ride along with `make`
+    others = [os.path.join(_HERE, f) for f in ("libsks_ssim_oracle_f32.so", "libsks_ssim_oracle_f64.so")]
+    if (force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs)
+            or not all(os.path.exists(o) for o in others)):
         subprocess.check_call(["make", "-C", _HERE, "-s"])
     return so
 

@@ -17,7 +17,8 @@
 // into v_pk_fma_f32 and pays for it with ~60 v_mov per item.
 // Taps are accumulated left-to-right / top-to-bottom like ssim.cu:100-185 with explicit FMAs (nvcc contracts the
 // reference's `sum += g * v` the same way); sigma = E[x^2] - mu^2 and the map / partial-derivative expressions are
-// ssim.cu:262-283 as written (their quotients through div_by below: same bits, fewer instructions).
+// ssim.cu:262-283 as written (their quotients through div_by below: the same bits in the range stated there, fewer
+// instructions).  The whole sequence is restated pixel by pixel in oracle/sks_ssim_oracle.c and held to it bit for bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -65,10 +66,18 @@ __device__ __forceinline__ float gk(int t)   // ssim.cu:9-19
 }
 
 // IEEE quotients that share a denominator: one refined reciprocal per denominator, two residual corrections per
-// numerator (the hardware's own division sequence without the range scaling).  Bit-identical to `n / d` for
-// d in [2^-40, 2^8), |n| in [2^-60, 2^12) -- 4.3e9 random pairs, tools/div_check.hip -- which covers the denominators
-// A B, A A B, A B B (A >= C1, B >= C2 up to rounding) and numerators of ssim.cu:262-283; 44 instead of 77 instructions for
-// the seven quotients of the training form.
+// numerator (the hardware's own division sequence without the range scaling); 44 instead of 77 instructions for the
+// seven quotients of the training form.  Where it is `n / d`, and what holds that:
+//   * d in [2^-100, 2^100), |n| in [2^-100, 2^100) or n = 0, the quotient a normal number: the same bits as IEEE `n / d`
+//     for a reciprocal seed anywhere within one ulp of 1 / d (the sequence restated with fmaf on the CPU, seeds at
+//     -1 / 0 / +1 ulp, tests/test_ssim_oracle_cpu.py), and on the device, through the kernels, against the sequential
+//     oracle oracle/sks_ssim_oracle.c on every input class of tests/ssim_cases.py (tests/test_ssim_oracle_gpu.py).  The
+//     denominators A B, A A B, A B B (A >= C1, B >= C2 up to rounding) and the numerators of ssim.cu:262-283 lie there
+//     for images of magnitude up to 255 and constants down to 2^-12;
+//   * a nonzero |n| below 2^-100 (mu2 * 2 * D under the tail of a normalised heat-map): within one ulp of `n / d`, not
+//     always equal (the residual n - d q is no longer exact); dm_dmu1 is then within 2 x the sum of its four quotients'
+//     ulps.  The same tests hold the kernels to these bounds; MEASUREMENTS.md has what the MI355X showed;
+//   * div_by(-0, d) is +0.
 __device__ __forceinline__ float refined_rcp(float d)
 {
     const float r = __builtin_amdgcn_rcpf(d);

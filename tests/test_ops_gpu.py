@@ -6,26 +6,11 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from tests import util
+from tests.ssim_cases import ssim_torch
 
 pytestmark = pytest.mark.gpu
-
-
-def ssim_torch(img1, img2):
-    """The reference's own SSIM oracle (utils/loss_utils.py:253-300 == submodules/fused-ssim/tests/test.py:24-54)."""
-    ch = img1.size(-3)
-    g = torch.tensor([math.exp(-(x - 5) ** 2 / float(2 * 1.5 ** 2)) for x in range(11)])
-    g = (g / g.sum()).unsqueeze(1)
-    win = g.mm(g.t()).float()[None, None].expand(ch, 1, 11, 11).contiguous().to(img1)
-    mu1 = F.conv2d(img1, win, padding=5, groups=ch)
-    mu2 = F.conv2d(img2, win, padding=5, groups=ch)
-    s1 = F.conv2d(img1 * img1, win, padding=5, groups=ch) - mu1.pow(2)
-    s2 = F.conv2d(img2 * img2, win, padding=5, groups=ch) - mu2.pow(2)
-    s12 = F.conv2d(img1 * img2, win, padding=5, groups=ch) - mu1 * mu2
-    C1, C2 = 0.01 ** 2, 0.03 ** 2
-    return ((2 * mu1 * mu2 + C1) * (2 * s12 + C2)) / ((mu1.pow(2) + mu2.pow(2) + C1) * (s1 + s2 + C2))
 
 
 SSIM_SHAPES = [(2, 3, 67, 45), (1, 17, 128, 160), (5, 5, 270, 480), (1, 2, 33, 200), (1, 1, 12, 16), (2, 1, 97, 131)]

@@ -1,5 +1,7 @@
 // Checks, over random operands in the ranges the SSIM expressions produce, that a quotient computed from a shared
 // refined reciprocal with two residual corrections equals the IEEE quotient n / d bit for bit.
+// A tool, run by hand; the claim itself is carried by tests/test_ssim_oracle_cpu.py (the sequence on the CPU, seeds at
+// -1 / 0 / +1 ulp) and tests/test_ssim_oracle_gpu.py (the kernels against oracle/sks_ssim_oracle.c).
 //   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt tools/div_check.hip -o tools/div_check
 #include <hip/hip_runtime.h>
 #include <stdint.h>
