@@ -520,6 +520,43 @@ int sks_loop_fused_step_es_dv(int V, int P, int C, int W, int H, const float* vi
                               int frames, const float* const* hm_factors /*HOST 4 or NULL*/, int* es_state, int es_window,
                               float es_tolerance, int* es_host_flags /*pinned HOST frames or NULL*/, void* stream);
 
+/* What the reference reports about a pose while and after it optimises it (train.py:184-213, 227-229, 239-242; eval.py:115-142),
+ * on the device (csrc/sks_report.hip; added to sks_version 14).  One launch each on `stream`, nothing synchronises, no atomics;
+ * every sum has a fixed order, so every result is bitwise the same from run to run.  Device memory unless marked HOST.
+ *
+ * sks_pose_errors: pred, gt (N,P,3) floats -> per_joint (N,P,2) or NULL, mean (N,2).  Column 0 is ||pred - gt|| of the joint,
+ *   column 1 ||(pred - pred[0]) - (gt - gt[0])|| (root-relative, in that order of operations); the mean runs over the frame's P
+ *   joints in float, a fixed order that depends on P alone.  Any N >= 1, any P >= 1.  A NaN joint poisons its own frame's means.
+ *
+ * sks_loop_report: the per-group launch of a frame batch (behind sks_loop_fused_step*; once behind the initialisation of the
+ *   frames, where it finds n = 0).  One wavefront per frame reads counters (frames,2), es_state (as sks_loop_fused_step_es's, with
+ *   its es_window; NULL: no early stopping), xyz (frames,P,3), gt (frames,P,3) or NULL, loss_sums (frames*V,2) or NULL, and with
+ *   n = counters[f,1], the Adam steps frame f has made, writes
+ *     trace_err (frames,capacity,2): row n = sks_pose_errors' two means of xyz[f], bit for bit (gt given);
+ *     trace_loss (frames,capacity,V): row n, column v = (float)(S / max(N, 1)) of view v's loss sums, as the early-stopping
+ *       criterion forms it (loss_sums given; trace_loss and loss_sums go together);
+ *     final_err (frames,P,2): sks_pose_errors' per-joint errors of xyz[f] (gt given);
+ *     snaps (frames,K,P,3): slot k, s = save_iterations[k] (HOST, K <= SKS_REPORT_MAX_SAVES ints >= 0, copied by value): xyz[f] if
+ *       the frame is running and s / acc_steps == n, or if it stopped at exactly iteration s -- the parameters as they stood at the
+ *       end of iteration s, for a frame that got there.  For a frame that stopped before s the slot is set to NaN, the value the
+ *       caller initialises the slots with: the reference writes no file for an iteration a scene never ran.
+ *   Rows n >= capacity are dropped, never written.  Everything written depends only on what the launch reads, so replaying it for a
+ *   frame that has stopped rewrites the values that are there.  The caller fills traces and snapshots with NaN per batch.
+ *
+ * sks_eval_sequence: pred, gt (N,P,3) floats, group_ids (N) ints or NULL (n_groups = 0), abs_valid (N) bytes or NULL ->
+ *   out (1 + n_groups, 2) doubles: row 0 = {absolute, root-relative} MPJPE over all frames (the mean of sks_pose_errors' per-joint
+ *   errors over frames and joints), row 1 + g the same over the frames with group_ids == g (an id outside [0, n_groups) is in no
+ *   group).  Frames with abs_valid == 0 are left out of the absolute figures only (eval.py:62-63); a row without frames is NaN.
+ *   Norms in float, sums in double: one workgroup per row, thread t adds frames t, t + 256, ... in index order, then a fixed tree. */
+#define SKS_REPORT_MAX_SAVES 8
+#define SKS_EVAL_MAX_GROUPS 64
+int sks_pose_errors(int N, int P, const float* pred, const float* gt, float* per_joint, float* mean, void* stream);
+int sks_loop_report(int frames, int V, int P, const int* counters, const int* es_state, int es_window, const float* xyz,
+                    const float* gt, const double* loss_sums, int acc_steps, int capacity, float* trace_err, float* trace_loss,
+                    float* final_err, int K, const int* save_iterations /*HOST K or NULL*/, float* snaps, void* stream);
+int sks_eval_sequence(int N, int P, const float* pred, const float* gt, const int* group_ids, int n_groups,
+                      const unsigned char* abs_valid, double* out, void* stream);
+
 /* Measurement hook used by bench.py (no reference counterpart; state per HOST THREAD, like the error text): while enabled, the dominant kernel of sks_forward
  * (kind 0: forward compositor) and of sks_backward (kind 1: backward compositor) is bracketed by hipEvents recorded
  * on the caller's stream (the small path's kernels carry the pair on their own dispatch, hipExtLaunchKernelGGL).  The low 16

@@ -25,6 +25,8 @@ SKS_FB_NO_JOIN = 1
 SKS_BIN_GROUPS_SHIFT = 16
 SKS_SSIM_SCRATCH_BYTES = 64 * 8
 SKS_SOFTARGMAX_STATS = 6
+SKS_REPORT_MAX_SAVES = 8
+SKS_EVAL_MAX_GROUPS = 64
 
 
 def SKS_BIN_GROUPS(n):
@@ -136,6 +138,9 @@ SIGNATURES = {
     "sks_triangulate": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sks_fuse_predictions": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     **{name: (_i, [ct for _, ct in params]) for name, params in {**STEP_PARAMS, **DV_PARAMS}.items()},
+    "sks_pose_errors": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sks_loop_report": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "sks_eval_sequence": (_i, [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "sks_prof_enable": (_i, [_i]),
     "sks_prof_spin": (_i, [C.c_double, _vp]),
     "sks_prof_read": (_i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),

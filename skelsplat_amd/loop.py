@@ -789,6 +789,41 @@ def _sequence_rig_ids(sel, rig_ids, N):
     return torch.as_tensor(validate_rig_ids(rig_ids, sel.bank.R, N), dtype=torch.int32).to(sel.ids.device)
 
 
+def _checked_gt(loop, gt, n, what):
+    """The ground truth handed to set_ground_truth -> the (n,P,3) float32 tensor on the loop's device that `what` (new_scenes: n = F
+    frames; optimize_sequence: n = N frames) needs; None stays None; anything else is refused."""
+    if gt is None:
+        return None
+    want = (n, loop.P, 3)
+    if tuple(gt.shape) != want:
+        raise ValueError(f"{what}: the ground truth given to set_ground_truth must be {want}, got {tuple(gt.shape)}")
+    return gt
+
+
+def _accept_gt(loop, gt):
+    """set_ground_truth's argument: None, or a float32 (n,P,3) tensor on the loop's device, for a loop whose error reporting is on."""
+    if gt is None:
+        return None
+    if loop._report is None or loop._report.steps == 0:
+        raise ValueError("ground truth is given, but error reporting is off: the errors against it are trace rows, which need "
+                         "FrameBatchLoop / FramePipeline(..., report_steps=rows) with rows > 0"
+                         + (" (this loop has save_iterations only: snapshots need no ground truth)" if loop._report is not None else ""))
+    dev = loop.xyz.device
+    if (not torch.is_tensor(gt) or gt.dim() != 3 or tuple(gt.shape[1:]) != (loop.P, 3) or gt.dtype != torch.float32
+            or gt.device != dev):
+        got = f"{tuple(gt.shape)} {gt.dtype} on {gt.device}" if torch.is_tensor(gt) else type(gt).__name__
+        raise ValueError(f"the ground truth must be a float32 tensor (frames,P,3) = (frames, {loop.P}, 3) on {dev}, got {got}")
+    return gt
+
+
+def _sequence_report(loop, N):
+    """optimize_sequence's `report`: None for a loop that reports nothing."""
+    if loop._report is None:
+        return None
+    from .report import SequenceReport
+    return SequenceReport(loop, N)
+
+
 def _frame_criterion(early_stopping):
     """FrameBatchLoop's `early_stopping` -> None (off) or (window, tolerance) of the reference's criterion, which the frame
     batch runs per frame on the device; anything else is refused."""
@@ -841,7 +876,10 @@ class FrameBatchLoop(_GroupLoop):
     to FrameBatchLoop(cameras=that rig) running it alone.  The image size of a view slot stays fixed across rigs."""
 
     def __init__(self, gaussians, cameras=None, frames=None, dataset="h36m", accumulation_steps=4, lambda_consistency=1e-5,
-                 antialiasing=False, use_graph=False, factored=True, early_stopping="no_stopping", rigs=None):
+                 antialiasing=False, use_graph=False, factored=True, early_stopping="no_stopping", rigs=None, report_steps=0,
+                 save_iterations=()):
+        from .report import check_report_args
+        check_report_args(report_steps, save_iterations)
         if (cameras is None) == (rigs is None):
             raise ValueError("FrameBatchLoop takes either cameras= (one rig for all frames) or rigs= (a RigBank)")
         if frames is None:
@@ -889,6 +927,13 @@ class FrameBatchLoop(_GroupLoop):
             self._es_flags_np = self._es_flags.numpy()
         self._packed = torch.zeros((F * V, P, 11), device=dev)
         self._sums = torch.zeros((F * V, 2), dtype=torch.float64, device=dev)
+        # reporting (report.LoopReport): None = off, and then the launch sequence of a group is the one without it
+        self._report = None
+        if report_steps or save_iterations:
+            from .report import LoopReport
+            self._report = LoopReport(F, V, P, report_steps, save_iterations, dev)
+        self.report = None      # optimize_sequence's report.SequenceReport of the last sequence
+        self._gt_next = None    # set_ground_truth's tensor, until the next new_scenes / optimize_sequence takes it
         self._sched, self._lrs, self._adam, self._limb = _optimiser_arrays(gm.opt_cfg, dataset, self.lambda_consistency)
         cams_all = [cameras[k % V] for k in range(F * V)]
         self._cams_all = cams_all
@@ -965,7 +1010,11 @@ class FrameBatchLoop(_GroupLoop):
         the current stream fills the batch's camera rows, per-view scalars, projection matrices and schedule rows in place, in
         front of the triangulation and the heat-map factors that read them.  Host ids are validated here; ids in a device
         tensor are bounds-checked by the kernel, which skips a frame whose id is outside the bank (it keeps the cameras its
-        slot had) and raises an error word that `check_rigs()` reports.  None: the frames keep the rigs they have."""
+        slot had) and raises an error word that `check_rigs()` reports.  None: the frames keep the rigs they have.
+        A loop that reports (`report_steps` / `save_iterations`): the ground truth given to `set_ground_truth` since the last batch,
+        (F,P,3), is copied in place -- without one the errors of this batch are NaN, losses and snapshots are reported all the
+        same --, the traces and snapshots go back to NaN and one report launch behind everything above writes row 0 and the
+        snapshots of iteration 0 from the initial joints."""
         from .heatmaps import generate_heatmaps, heatmap_factors, heatmap_planes
         from .triangulation import triangulate_sequence
         F, V, P = self.F, self.V, self.P
@@ -973,6 +1022,7 @@ class FrameBatchLoop(_GroupLoop):
             raise ValueError("ready heat-map planes need FrameBatchLoop(..., factored=False)")
         if rig_ids is not None and self._sel is None:
             raise ValueError("rig_ids needs a rig bank: FrameBatchLoop(gaussians, rigs=RigBank(rigs, device), frames=F)")
+        gt_pose, self._gt_next = _checked_gt(self, self._gt_next, F, "new_scenes"), None      # (`gt` below: heat-map planes)
         with torch.no_grad():
             if self._sel is not None:
                 self._sel.check()       # (an id a device tensor of an earlier batch held outside the bank; never waits)
@@ -1048,8 +1098,18 @@ class FrameBatchLoop(_GroupLoop):
                                       drop_mask=None if drop_all is None else drop_all[idx.cpu()], frames=F)
                 if len(self.size_groups) > 1:
                     self.stats_all.totals.index_copy_(0, idx, stats.totals)
+            if self._report is not None:
+                self._report.reset(gt_pose)
+                self._report.launch(self, losses=False)
         self._geom_valid = False
         self.iteration = 0
+        return self
+
+    def set_ground_truth(self, gt):
+        """The ground truth of the NEXT batch or sequence (a loop with `report_steps`): (F,P,3) for `new_scenes`, (N,P,3) for
+        `optimize_sequence`, float32 on the loop's device.  The next of those calls takes it -- the errors it reports are against
+        it -- and forgets it; None withdraws one that has not been taken.  Returns the loop."""
+        self._gt_next = _accept_gt(self, gt)
         return self
 
     def _optimiser_block(self, group_mask, last_view, n_iters):
@@ -1067,6 +1127,8 @@ class FrameBatchLoop(_GroupLoop):
                                                   es_flags=self._es_flags)
             R.loop_fused_step(self._fstate, self.stats_all, self.features, self._packed, self._sums,
                               *self._optimiser_block(group_mask, last_view, n_iters), **es)
+            if self._report is not None:
+                self._report.launch(self)
         s = self._sums.view(self.F, self.V, 2)
         self.last_losses = (s[..., 0], s[..., 1])       # per (frame, view) {S, N}: loss = S / N
 
@@ -1105,6 +1167,33 @@ class FrameBatchLoop(_GroupLoop):
     def _all_stopped(self):
         return self._es is not None and bool(self._es_flags_np.all())
 
+    # What the loop reports (report_steps / save_iterations; report.LoopReport says what each holds): the loop's own buffers,
+    # as they stand on the stream -- none of these waits.  None for what is switched off.
+    @property
+    def trace_errors(self):
+        """(F,report_steps,2): row n = mean absolute / root-relative error after n optimiser steps."""
+        return None if self._report is None else self._report.trace_err
+
+    @property
+    def trace_losses(self):
+        """(F,report_steps,V): row n >= 1 = every view's loss in the group that led to step n."""
+        return None if self._report is None else self._report.trace_loss
+
+    @property
+    def final_errors(self):
+        """(F,P,2): per-joint absolute / root-relative error of the current joints."""
+        return None if self._report is None else self._report.final_err
+
+    @property
+    def snapshots(self):
+        """(F,K,P,3): the joints at the end of iteration save_iterations[k]; NaN for a frame that stopped before it."""
+        return None if self._report is None else self._report.snaps
+
+    @property
+    def steps(self):
+        """(F,) int32: optimiser steps every frame has made (the last row of its traces)."""
+        return self.counters[:, 1]
+
     def run(self, iterations=500, groups_per_graph=25):
         """All F frames up to `iterations`; returns the joints (F,P,3).  With use_graph, `groups_per_graph` groups are one
         hipGraph, as in MultiViewLoop.run.  With early stopping, the flags are polled between launches without waiting,
@@ -1122,12 +1211,15 @@ class FrameBatchLoop(_GroupLoop):
         if self._sel is not None:
             self._sel.check()
 
-    def _next_batch(self, pts, p2d, b, initial=None, rig_ids=None, p3d=None):
+    def _next_batch(self, pts, p2d, b, initial=None, rig_ids=None, p3d=None, gt=None):
         """new_scenes for the frames b .. b + F of a sequence (a short last batch is filled up by repeating its final
         frame, rig included); `pts` None: triangulated from the detections.  `initial` (N,P,3): receives the batch's initial
         joints.  `rig_ids`: None or the sequence's (N,) ids as _sequence_rig_ids left them.  `p3d`: None or the sequence's
-        (N,V,J,3) predictions, fused into the initial joints instead of the triangulation (`pts` None)."""
+        (N,V,J,3) predictions, fused into the initial joints instead of the triangulation (`pts` None).  `gt`: None or the sequence's
+        (N,P,3) ground truth as _checked_gt left it."""
         N, F = p2d.shape[0], self.F
+        if gt is not None:
+            self._gt_next = gt[b:b + F] if b + F <= N else gt[[min(b + i, N - 1) for i in range(F)]]
         if b + F <= N:      # a full batch: views of the inputs, no gather
             self.new_scenes(None if pts is None else pts[b:b + F], poses_2d=p2d[b:b + F],
                             rig_ids=None if rig_ids is None else rig_ids[b:b + F],
@@ -1150,17 +1242,24 @@ class FrameBatchLoop(_GroupLoop):
         `return_initial=True`: returns (joints, initial joints), both (N,P,3) on the device.
         `rig_ids` (N,) ints, host or device (a loop over a rig bank): the rig of every frame, see new_scenes.
         `poses_3d` (N,V,J,3), with `points=None`: every batch's initial joints are fused from the views' 3D predictions
-        instead (new_scenes); a device tensor is never copied to the host."""
+        instead (new_scenes); a device tensor is never copied to the host.
+        A loop that reports: the return value is the same, and `self.report` (a report.SequenceReport) holds the loop's traces,
+        final errors, snapshots and step counts for all N frames -- the errors against the (N,P,3) ground truth given to
+        `set_ground_truth` before this call, NaN without one."""
         pts, p2d, N = _sequence_inputs(points, poses_2d)
         p3d = _sequence_predictions(points, poses_3d, N)
         ids = _sequence_rig_ids(self._sel, rig_ids, N)
+        gt, self._gt_next = _checked_gt(self, self._gt_next, N, "optimize_sequence"), None
+        self.report = _sequence_report(self, N)
         F = self.F
         out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
         initial = torch.empty_like(out) if return_initial else None
         for b in range(0, N, F):
-            self._next_batch(pts, p2d, b, initial, ids, p3d)
+            self._next_batch(pts, p2d, b, initial, ids, p3d, gt)
             res = self.run(iterations, groups_per_graph)
             out[b:min(b + F, N)] = res[:min(F, N - b)]
+            if self.report is not None:
+                self.report.take(self, b, min(F, N - b))
         self.check_rigs()
         return (out, initial) if return_initial else out
 
@@ -1184,6 +1283,14 @@ class FramePipeline:
         self.streams = [torch.cuda.Stream(self.device) for _ in self.loops]
         self.F, self.P = self.loops[0].F, self.loops[0].P
         self.stopped_at = None       # early stopping: (N,) int64 of the last optimize_sequence, 0 = ran to the end
+        self.report = None           # loops that report: report.SequenceReport of the last optimize_sequence
+        self._gt_next = None         # set_ground_truth's tensor, until the next optimize_sequence takes it
+
+    def set_ground_truth(self, gt):
+        """The (N,P,3) float32 ground truth, on the device, of the NEXT optimize_sequence (loops with `report_steps`), which takes
+        it and forgets it; None withdraws one that has not been taken.  Returns the pipeline."""
+        self._gt_next = _accept_gt(self.loops[0], gt)
+        return self
 
     def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, interleave=100,
                           return_initial=False, rig_ids=None, poses_3d=None):
@@ -1196,10 +1303,15 @@ class FramePipeline:
         `rig_ids` (N,) ints, host or device (loops over a rig bank, `rigs=`): the rig of every frame, see
         FrameBatchLoop.new_scenes; check_rigs() reports an id a device tensor held outside the bank.
         `poses_3d` (N,V,J,3), with `points=None`: every batch's initial joints are fused from the views' 3D predictions
-        instead of triangulated, by one launch in the same place (initial_guess.fuse_predictions)."""
+        instead of triangulated, by one launch in the same place (initial_guess.fuse_predictions).
+        Loops that report (`report_steps` / `save_iterations`): `self.report` holds traces, final errors, snapshots and step counts
+        of all N frames, copied on each batch's own stream -- the errors against the (N,P,3) ground truth given to
+        `set_ground_truth` before this call, NaN without one.  The return value is the same."""
         pts, p2d, N = _sequence_inputs(points, poses_2d)
         p3d = _sequence_predictions(points, poses_3d, N)
         ids = _sequence_rig_ids(self.loops[0]._sel, rig_ids, N)     # (uploaded on the caller's stream, which every stream waits for)
+        gt, self._gt_next = _checked_gt(self.loops[0], self._gt_next, N, "optimize_sequence"), None
+        self.report = _sequence_report(self.loops[0], N)
         F, S = self.F, len(self.loops)
         out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
         initial = torch.empty_like(out) if return_initial else None
@@ -1209,7 +1321,7 @@ class FramePipeline:
             self.stopped_at = torch.zeros(N, dtype=torch.int64, device=self.device)
             for st in self.streams:
                 st.wait_stream(cur)
-            self._sequence_es(pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial, ids, p3d)
+            self._sequence_es(pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial, ids, p3d, gt)
             for st in self.streams:
                 cur.wait_stream(st)
             self.check_rigs()
@@ -1220,7 +1332,7 @@ class FramePipeline:
             active = list(zip(self.loops, self.streams, starts[w:w + S]))
             for fb, st, b in active:
                 with torch.cuda.stream(st):
-                    fb._next_batch(pts, p2d, b, initial, ids, p3d)
+                    fb._next_batch(pts, p2d, b, initial, ids, p3d, gt)
             for k in range(0, iterations, max(int(interleave), 1)):
                 for fb, st, b in active:
                     with torch.cuda.stream(st):
@@ -1228,6 +1340,8 @@ class FramePipeline:
             for fb, st, b in active:
                 with torch.cuda.stream(st):
                     out[b:min(b + F, N)] = fb.xyz[:min(F, N - b)]
+                    if self.report is not None:
+                        self.report.take(fb, b, min(F, N - b))
         for st in self.streams:
             cur.wait_stream(st)
         self.check_rigs()
@@ -1239,7 +1353,7 @@ class FramePipeline:
             fb.check_rigs()
 
     def _sequence_es(self, pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial=None, rig_ids=None,
-                     p3d=None):
+                     p3d=None, gt=None):
         """optimize_sequence with early stopping: every stream keeps its own batch and takes the next one as soon as its
         batch is done -- all frames stopped (seen in the pinned flags, without waiting) or `iterations` enqueued -- instead
         of waiting for the other streams' batches.  Results and stopping iterations are copied on the batch's stream."""
@@ -1251,7 +1365,7 @@ class FramePipeline:
             if b is None:
                 return None
             with torch.cuda.stream(st):
-                fb._next_batch(pts, p2d, b, initial, rig_ids, p3d)
+                fb._next_batch(pts, p2d, b, initial, rig_ids, p3d, gt)
             return [fb, st, b, 0]
 
         step = max(int(interleave), 1)
@@ -1268,6 +1382,8 @@ class FramePipeline:
                         n = min(F, N - b)
                         out[b:b + n] = fb.xyz[:n]
                         self.stopped_at[b:b + n] = fb._es_state[:n, 1]      # (0: the frame ran to the end)
+                        if self.report is not None:
+                            self.report.take(fb, b, n)
                         slot = take(fb, st)
                 if slot is not None:
                     nxt.append(slot)

@@ -10,9 +10,17 @@ sequence of S x F x 4 frames through FramePipeline (S streams of F frames, graph
   bank_cycle   FramePipeline(rigs=bank), frame f on rig f % R;
   naive        what a caller had to do before: per batch, the cameras of the batch's rig rebuilt on the host (Camera objects, a
                new FrameBatchLoop with its ViewBatch) and the graphs captured again (one rig per batch: frames are taken rig by rig);
-and the host cost of building one rig's Cameras alone.  Prints one line per case: median frames/s, min, max."""
+and the host cost of building one rig's Cameras alone.  Prints one line per case: median frames/s, min, max.
+
+bench_frames.py --report [--reps N] [--frames F] [--streams S] [--parent DIR]: what reporting costs (FramePipeline(report_steps=,
+save_iterations=), set_ground_truth(gt)): the H36M pipeline (S streams of F frames, graphs on, ITERS iterations) with reporting
+  off          as it ran before: the launch sequence of a group is unchanged;
+  on           errors and losses at every optimiser step, three snapshots: one more launch of F wavefronts per group;
+  parent_off   (--parent DIR, a built checkout of the commit to compare with) that tree's pipeline, reporting unknown to it.
+Every tree is measured by a worker process of its own that stays warm; the driver asks them for one repetition of one case at a
+time, round-robin, N times, so drift hits all cases alike.  Prints median, min and max per case and the ratios of the medians."""
 import os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.environ.get("SKS_BENCH_ROOT") or os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch
 from skelsplat_amd.loop import MultiViewLoop, FrameBatchLoop
@@ -98,6 +106,100 @@ def bench_rigs(argv):
           f"{F} x 4 per batch of distinct rigs {(time.perf_counter() - t0) / 20 * F * 1e3:.2f} ms")
 
 
+def report_worker(argv):
+    """One tree's pipeline(s), warm; per line on stdin ("off" / "on") one timed sequence, its frames/s on stdout."""
+    import inspect
+    from skelsplat_amd.loop import FramePipeline
+    F, S = int(argv[0]), int(argv[1])
+    iters = int(os.environ.get("ITERS", "500"))
+    N = S * F * 4
+    sc = SyntheticScene("h36m", n_views=4, seed=0, device=dev)
+    rng = np.random.default_rng(1)
+    pts = np.stack([sc.pose_3d_init + rng.normal(0, 10.0, (17, 3)) for _ in range(N)]).astype(np.float32)
+    p2d = np.stack([sc.poses_2d + rng.normal(0, 2.0, (4, 17, 2)) for _ in range(N)]).astype(np.float32)
+    gt = torch.as_tensor(np.asarray(sc.pose_3d_gt, np.float32), device=dev)[None].repeat(N, 1, 1).contiguous()
+
+    def model():
+        gm = GaussianModel().create_from_points(sc.pose_3d_init, sc.spatial_lr_scale, 17, device=dev)
+        gm.training_setup()
+        return gm
+    pipes = {"off": (FramePipeline(model(), sc.cameras, frames=F, streams=S, dataset="h36m"), None)}
+    if "report_steps" in inspect.signature(FrameBatchLoop.__init__).parameters:
+        pipes["on"] = (FramePipeline(model(), sc.cameras, frames=F, streams=S, dataset="h36m", report_steps=iters // 4 + 1,
+                                     save_iterations=(0, iters // 2, iters)), gt)
+    for pipe, truth in pipes.values():
+        if truth is not None:
+            pipe.set_ground_truth(truth)
+        pipe.optimize_sequence(pts, p2d, iterations=iters)       # warm-up: allocations, graph capture
+    torch.cuda.synchronize()
+    print("ready " + ",".join(pipes), flush=True)
+    for line in sys.stdin:
+        pipe, truth = pipes[line.strip()]
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        if truth is not None:
+            pipe.set_ground_truth(truth)
+        pipe.optimize_sequence(pts, p2d, iterations=iters)
+        torch.cuda.synchronize()
+        print(f"{N / (time.perf_counter() - t0):.1f}", flush=True)
+
+
+def bench_report(argv):
+    import argparse, statistics, subprocess
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--report", action="store_true")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--streams", type=int, default=2)
+    ap.add_argument("--parent", default=None)
+    a = ap.parse_args(argv)
+    if a.reps < 5:
+        ap.error("--reps: at least 5 repetitions")
+
+    def worker(root):
+        env = dict(os.environ, SKS_BENCH_ROOT=os.path.abspath(root))
+        w = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--report-worker", str(a.frames), str(a.streams)],
+                             stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env=env, cwd=root)
+        head = w.stdout.readline().split()
+        if not head or head[0] != "ready":
+            raise SystemExit(f"the worker of {root} did not start")
+        return w, head[1].split(",")
+
+    def ask(w, case):
+        w.stdin.write(case + "\n"); w.stdin.flush()
+        return float(w.stdout.readline())
+    here, cases_here = worker(ROOT)
+    cases = [(c, here) for c in cases_here]
+    parent = None
+    if a.parent:
+        parent, _ = worker(a.parent)
+        cases.append(("parent_off", parent))
+    rates = {c: [] for c, _ in cases}
+    for rep in range(a.reps):       # interleaved: one repetition of every case after the other
+        for c, w in cases:
+            rates[c].append(ask(w, "off" if c == "parent_off" else c))
+    for w in (here, parent):
+        if w is not None:
+            w.stdin.close(); w.wait()
+    N = a.frames * a.streams * 4
+    med = {c: statistics.median(v) for c, v in rates.items()}
+    for c, v in rates.items():
+        print(f"report {c:10s}: median {med[c]:7.0f} frames/s  min {min(v):7.0f}  max {max(v):7.0f}  ({a.streams} streams x "
+              f"{a.frames} frames, {N} frames, {os.environ.get('ITERS', '500')} iterations, {a.reps} interleaved repetitions)  all: "
+              + " ".join(f"{x:.0f}" for x in v))
+    if "on" in med:
+        print(f"report on / off = {med['on'] / med['off']:.4f}")
+    if "parent_off" in med:
+        lo, hi = min(rates["parent_off"]), max(rates["parent_off"])
+        print(f"report off / parent_off = {med['off'] / med['parent_off']:.4f}; median of off "
+              f"{'inside' if lo <= med['off'] <= hi else 'OUTSIDE'} the parent's own range [{lo:.0f}, {hi:.0f}]")
+
+
+if "--report-worker" in sys.argv:
+    report_worker(sys.argv[sys.argv.index("--report-worker") + 1:])
+    sys.exit(0)
+if "--report" in sys.argv:
+    bench_report(sys.argv[1:])
+    sys.exit(0)
 if "--rigs" in sys.argv:
     bench_rigs(sys.argv[1:])
     sys.exit(0)
