@@ -62,7 +62,10 @@ extern "C" {
    No result bit depends on it.  sks_forward_backward uses it to run group g's backward on the second stream while group g + 1's
    forward streams on the first; sks_backward must be given the value its sks_forward had (like every other flag).  A field of
    zero asks for the default: one group, unless the build sets SKS_BIN_FB_GROUPS or the process's SKS_BIN_GROUPS environment
-   variable (a tuning sweep; read once) names another count -- the same for every entry point. */
+   variable (a tuning sweep; read once) names another count -- the same for every entry point.
+   The SMALL path has no view groups and reads the same three bits as the early fill's E (SKS_EARLY_FILL below): a caller that
+   passes SKS_BIN_GROUPS(n) whatever P is forces E = (n - 1) sixteenths of the planes on its small-path calls instead of the
+   measured default -- the same bits in the results, possibly a few microseconds slower. */
 #define SKS_BIN_GROUPS_SHIFT 16
 #define SKS_BIN_GROUPS(n) ((unsigned)(((n) - 1) & 7) << SKS_BIN_GROUPS_SHIFT)
 #define SKS_FILL_LINEAR (1u << 21)  /* tuning/tests: forward fill blocks always in linear (pass-major) mode */
@@ -72,6 +75,15 @@ extern "C" {
 /* bits 23..25: tuning/tests, workgroups per (view, Gaussian) of the wave-resident backward = 16 >> (value - 1)
    (0 = automatic: 16 for a few views, fewer and longer ones when V x P is large; the results do not depend on it) */
 #define SKS_BWD_WG_SHIFT 23
+/* Small path, plain sks_forward with cover rows and no debug planes: the geometry launch also zeroes the call's LAST E (view, plane)
+   planes, whole, with nothing in front of its stores (k_geom_fwd_fill), and the fill + composite launch behind it streams the rest and
+   stores every covered tile, the early planes' included ("Early fill").  No result bit depends on either of the two: */
+#define SKS_NO_EARLY_FILL (1u << 30)   /* tuning/tests: the geometry launch fills nothing, the fill + composite launch streams every plane */
+/* tuning/tests, E: on the small path, which has no view groups, the three bits 16..18 (SKS_BIN_GROUPS_SHIFT) are E's field:
+   0 = automatic (the rule in sks_raster.hip, early_fill_planes); n = 1..6: n sixteenths of the (C + 1) * V planes, rounded up;
+   7: every plane.  Ignored where the early fill is not used (the cases above, sks_forward_backward, SKS_DEBUG_SYNC, row-aligned
+   fill blocks).  Bits 19 and 31 stay free. */
+#define SKS_EARLY_FILL(n) (((unsigned)(n) & 7u) << SKS_BIN_GROUPS_SHIFT)
 
 const char* sks_last_error(void);
 int sks_version(void);
@@ -92,7 +104,9 @@ int sks_scratch_bytes(int V, int P, int C, int W, int H, size_t bin_capacity,
 /* Replaces _C.rasterize_gaussians (DGR/rasterize_points.cu:35-124 -> rasterizer_impl.cu:198-341).
  * features: (P,C) -- the reference reads them from `sh` with M == 1.
  * Outputs: out_color (V,C,H,W), out_invdepth (V,1,H,W), radii (V,P); every element is written
- * (no pre-zeroing needed).  out_color / out_invdepth must be 16-byte aligned (refused otherwise); 128-byte aligned
+ * (no pre-zeroing needed) -- on the small path by two launches back to back, the geometry launch, which also zeroes the call's last
+ * few planes (SKS_NO_EARLY_FILL: it fills nothing), and the fill + composite launch; the outputs are complete in `stream` order
+ * behind the second.  out_color / out_invdepth must be 16-byte aligned (refused otherwise); 128-byte aligned
  * buffers -- every torch allocation is -- take the fastest fill (whole cache lines per pass).  Optional debug outputs final_T (V,H,W) / n_contrib (V,H,W) reproduce the
  * reference's ImageState (rasterizer_impl.h:52-60) for parity tests; pass NULL on the fast path.
  * num_rendered_dev (V ints, may be NULL): number of (Gaussian,tile) pairs, written on the binned path. */

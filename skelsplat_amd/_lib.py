@@ -29,6 +29,14 @@ SKS_REPORT_MAX_SAVES = 8
 SKS_EVAL_MAX_GROUPS = 64
 
 
+SKS_NO_EARLY_FILL = 1 << 30
+
+
+def SKS_EARLY_FILL(n):
+    """Tuning/tests, small path: the geometry launch zeroes n sixteenths of the call's planes (n = 1..6), all of them (7); 0 = automatic."""
+    return (int(n) & 7) << SKS_BIN_GROUPS_SHIFT
+
+
 def SKS_BIN_GROUPS(n):
     """Flag bits for `n` view groups on the binned path (include/skelsplat_hip.h)."""
     return ((int(n) - 1) & 7) << SKS_BIN_GROUPS_SHIFT

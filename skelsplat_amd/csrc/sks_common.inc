@@ -44,13 +44,14 @@ struct ProfState {
 };
 thread_local ProfState* tl_prof = nullptr;   // allocated by the first sks_prof_enable of the thread
 
-struct ProfScope {  // brackets ONE kernel launch with a begin / end event pair
+struct ProfScope {  // brackets ONE kernel launch -- or two back to back, SKS_LAUNCH_FIRST -- with a begin / end event pair
     // Two ways: recorded = hipEventRecord before and after (two marker packets in the queue: ~3 us of queue time per
     // bracketed launch, measured: 68 -> 73 -> 82 us per H36M step bracketing no / every 8th / every launch); ext = the
     // pair is handed to hipExtLaunchKernelGGL, which stamps it from the kernel's own dispatch packet (SKS_LAUNCH below).
     ProfKind* k = nullptr;
     hipStream_t st;
     bool ext;
+    bool began = false;   // the begin event already stands in front of, or rides on, an earlier dispatch of this scope (SKS_LAUNCH_FIRST)
     ProfScope(int kind, hipStream_t s, bool ext_ = false) : st(s), ext(ext_)
     {
         ProfState* ps = tl_prof;
@@ -78,8 +79,16 @@ struct ProfScope {  // brackets ONE kernel launch with a begin / end event pair
 // launch inside an `ext` ProfScope: the scope's events ride on the kernel's dispatch when it is active
 #define SKS_LAUNCH(prof, kernel, grid, block, lds, stream, ...)                                                  \
     do {                                                                                                         \
-        if ((prof).k) hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, (prof).eb(), (prof).ee(), 0, __VA_ARGS__); \
+        if ((prof).k)                                                                                            \
+            hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, (prof).began ? nullptr : (prof).eb(), (prof).ee(), 0, __VA_ARGS__); \
         else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                  \
+    } while (0)
+// the first of TWO launches one scope brackets: the begin event rides on this dispatch, the end event on the SKS_LAUNCH behind it
+#define SKS_LAUNCH_FIRST(prof, kernel, grid, block, lds, stream, ...)                                            \
+    do {                                                                                                         \
+        if ((prof).k && (prof).ext) hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, (prof).eb(), nullptr, 0, __VA_ARGS__); \
+        else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);   /* (recorded: the scope's marker is in front) */ \
+        (prof).began = (prof).k != nullptr;                                                                      \
     } while (0)
 
 constexpr int NACC = 8;           // per-Gaussian accumulators before the feature block:

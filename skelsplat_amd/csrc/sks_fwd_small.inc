@@ -102,6 +102,28 @@ struct DynList {
 // middle (never inside a pair: W is even).  Each pass therefore carries two skip bits, one per pair, and a float4 with one
 // covered pair is written as the other pair's 8 bytes.
 // ------------------------------------------------------------------------------------------------------------
+// the bare stream of stores of a band no rect crosses (fwd_fill_role) and of the planes k_geom_fwd_fill zeroes: npass passes of
+// 256 * PPT floats from base0 on, clipped to the band's [0, Nb)
+template <int PPT, bool NT>
+__device__ __forceinline__ void fill_bare(float* out, float* outT, uint32_t* outN, int base0, int Nb, int npass)
+{
+    constexpr int PASS = 256 * PPT;
+    for (int k = 0; k < npass; k++) {
+        const int base = base0 + k * PASS;
+        if (base >= Nb) break;
+        if (base < 0) continue;          // (in front of the band: the short first pass, see `shift`)
+        if (PPT == 4) store4<NT>(out + base, 0.0f, 0.0f, 0.0f, 0.0f);   // (HALF: Nb is a multiple of 4, rows are even)
+        else out[base] = 0.0f;
+        if (outT || outN) {
+#pragma unroll
+            for (int p = 0; p < PPT; p++) {
+                if (outT) outT[base + p] = 1.0f;
+                if (outN) outN[base + p] = 0u;
+            }
+        }
+    }
+}
+
 template <int PPT, bool NT, bool HALF = false>
 __device__ __forceinline__ void fwd_fill_role(const FwdArgs& a, unsigned cp1_magic, int q, int band, int zid, int gy, int pb,
                                               const uint32_t* __restrict__ cover)
@@ -188,20 +210,7 @@ __device__ __forceinline__ void fwd_fill_role(const FwdArgs& a, unsigned cp1_mag
         // 8 waves per SIMD the launch is bound by that life time, and every instruction in front of or between its stores
         // shows in the kernel time -- the pair logic of the HALF mode alone, never taken here, cost 4.9 us of 46 on the pure
         // fill of a 1002-wide launch while it sat in this loop (interleaved A/B, tools/width_sweep2.py).
-        for (int k = 0; k < npass; k++) {
-            const int base = base0 + k * PASS;
-            if (base >= Nb) break;
-            if (base < 0) continue;          // (in front of the band: the short first pass, see `shift`)
-            if (PPT == 4) store4<NT>(out + base, 0.0f, 0.0f, 0.0f, 0.0f);   // (HALF: Nb is a multiple of 4, rows are even)
-            else out[base] = 0.0f;
-            if (outT || outN) {
-#pragma unroll
-                for (int p = 0; p < PPT; p++) {
-                    if (outT) outT[base + p] = 1.0f;
-                    if (outN) outN[base + p] = 0u;
-                }
-            }
-        }
+        fill_bare<PPT, NT>(out, outT, outN, base0, Nb, npass);
         return;
     }
     unsigned skipmask = 0u, skipmask2 = 0u;   // skipmask2 (HALF): the float4's second pair
@@ -424,3 +433,59 @@ __global__ __launch_bounds__(256) SKS_FWD_WAVES_ATTR void k_render_fwd_sparse(Fw
     fwd_fill_role<PPT, NT, HALF>(a, cp1_magic, xq, band_id, zid, gy, pb, cover);
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// The geometry launch of a plain small-path sks_forward, carrying the zero fill of the call's LAST planes: for the ~5 us
+// of k_geom_fwd (72 workgroups, two dependent round trips) the memory system carries nothing, and a fill block that
+// zeroes its passes unconditionally needs nothing from the geometry -- the tiles it should have skipped are written
+// again by the composite blocks of k_render_fwd_sparse, the NEXT launch in the stream, which then streams only the
+// planes zid < zid0 (launch_fwd_small).  1-D grid: blocks 0 .. ngeom - 1 are k_geom_fwd's blocks (view, plane) -- first
+// in dispatch order, same arithmetic, same stores --, block ngeom + e is fill block (q, band, zid) of the early
+// region in memory order, e = ((zid - zid0) * gy + band) * fsplit + q.  A fill block loads nothing: every argument
+// comes by value, the divisions are multiply-highs by reciprocals the host made (exact: e * rows < 2^32,
+// early_fill_plan), and it runs fill_bare, the store loop of a band no rect crosses.
+// ------------------------------------------------------------------------------------------------------------
+struct EarlyFill {
+    float* out_color;
+    float* out_invdepth;
+    int C, W, H, gy;
+    int gplanes;          // k_geom_fwd's grid.z: C + 1 (a cover row set per plane) or 1
+    int ngeom;            // V * gplanes geometry blocks in front
+    int zid0;             // first early plane, zid = view * (C + 1) + plane
+    int fsplit, pb;       // fill blocks per (plane, band) row / passes per block: those of the main launch (fill_geometry)
+    unsigned cp1_magic;   // FwdArgs::cp1_magic
+    unsigned row_magic;   // ceil(2^32 / (fsplit * gy)), 0 when that divisor is 1
+    unsigned fs_magic;    // ceil(2^32 / fsplit), likewise
+};
+
+template <int PPT, bool NT>
+__global__ __launch_bounds__(256) void k_geom_fwd_fill(EarlyFill f, int P, ViewTan vt, const float* __restrict__ vms,
+                                                       const float* __restrict__ pms, const float* __restrict__ means,
+                                                       const float* __restrict__ opac, const float* __restrict__ scales,
+                                                       const float* __restrict__ rots, const float* __restrict__ cov3Dp, float smod,
+                                                       unsigned flags, Geom g, int* __restrict__ radii,
+                                                       const float* __restrict__ features, int cover_planes)
+{
+    const int b = blockIdx.x;
+    if (b < f.ngeom) {
+        const int v = f.gplanes == 1 ? b : (int)(((unsigned)b * f.cp1_magic) >> 20);
+        extern __shared__ __attribute__((aligned(16))) char s_dyn[];   // gy * cover_cw(W) words: what the call's cover rows need, so that
+                                                                       // the fill blocks behind keep 8 workgroups per CU (k_geom_fwd's fixed 24 KB: 6)
+        geom_fwd_block((uint32_t*)s_dyn, 0, v, b - v * f.gplanes, P, f.W, f.H, vt, vms, pms, means, opac, scales, rots, cov3Dp, smod, flags, g, radii, 0,
+                       nullptr, nullptr, features, f.C, nullptr, nullptr, cover_planes);
+        return;
+    }
+    const unsigned e = (unsigned)(b - f.ngeom);
+    const unsigned rows = (unsigned)(f.fsplit * f.gy);
+    const unsigned zr = f.row_magic ? __umulhi(e, f.row_magic) : e;        // (a magic of 0 stands for the divisor 1)
+    const unsigned rem = e - zr * rows;
+    const int band = (int)(f.fs_magic ? __umulhi(rem, f.fs_magic) : rem);
+    const int q = (int)rem - band * f.fsplit;
+    const int zid = f.zid0 + (int)zr;
+    const int v = (int)(((unsigned)zid * f.cp1_magic) >> 20);
+    const int plane = zid - v * (f.C + 1);
+    const size_t HW = (size_t)f.H * f.W;
+    const int Nb = min(TILE, f.H - band * TILE) * f.W;
+    float* out = (plane == f.C ? f.out_invdepth + (size_t)v * HW : f.out_color + ((size_t)v * f.C + plane) * HW) + (size_t)band * TILE * f.W;
+    const int shift = (int)((reinterpret_cast<uintptr_t>(out) >> 2) & 31u);   // passes cut on 128-byte lines of the address (fwd_fill_role)
+    fill_bare<PPT, NT>(out, nullptr, nullptr, q * (256 * PPT) * f.pb + (int)threadIdx.x * PPT - shift, Nb, min(f.pb, 32));
+}

@@ -87,19 +87,18 @@ __device__ __forceinline__ uint4 geom_fwd_one(int P, const VT& vt, const float* 
 #ifndef SKS_GEOM_COVER_THREADS
 #define SKS_GEOM_COVER_THREADS 256    // (the small path: one block per (view, plane) with a cover row set per plane, else per view)
 #endif
-__global__ __launch_bounds__(SKS_GEOM_COVER_THREADS > 256 ? SKS_GEOM_COVER_THREADS : 256) void k_geom_fwd(int P, int W, int H, ViewTan vt, const float* __restrict__ vms,
-                                                   const float* __restrict__ pms, const float* __restrict__ means,
-                                                   const float* __restrict__ opac, const float* __restrict__ scales,
-                                                   const float* __restrict__ rots, const float* __restrict__ cov3Dp,
-                                                   float smod, unsigned flags, Geom g, int* __restrict__ radii, int vf,
-                                                   uint32_t* __restrict__ count = nullptr, uint32_t* __restrict__ touched = nullptr,
-                                                   const float* __restrict__ features = nullptr, int C = 0,
-                                                   uint2* __restrict__ fmask = nullptr, uint32_t* __restrict__ bin_hdr = nullptr,
-                                                   int cover_planes = 0)
+// the body of k_geom_fwd for block (bx, v, pz) -- shared with k_geom_fwd_fill (sks_fwd_small.inc), whose first blocks are
+// these blocks of a small-path call; s_cov: LDS for one plane's (or view's) cover rows, gy * cover_cw(W) words (unused without g.cover)
+__device__ __forceinline__ void geom_fwd_block(uint32_t* s_cov, int bx, int v, int pz, int P, int W, int H, const ViewTan& vt, const float* __restrict__ vms,
+                                               const float* __restrict__ pms, const float* __restrict__ means,
+                                               const float* __restrict__ opac, const float* __restrict__ scales,
+                                               const float* __restrict__ rots, const float* __restrict__ cov3Dp,
+                                               float smod, unsigned flags, const Geom& g, int* __restrict__ radii, int vf,
+                                               uint32_t* __restrict__ count, uint32_t* __restrict__ touched,
+                                               const float* __restrict__ features, int C,
+                                               uint2* __restrict__ fmask, uint32_t* __restrict__ bin_hdr, int cover_planes)
 {
-    __shared__ uint32_t s_cov[COVER_MAX_WORDS];
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // (256 threads; SKS_GEOM_BINNED_THREADS on the binned path, which has no cover rows to build)
-    const int v = blockIdx.y;
+    const int idx = bx * blockDim.x + threadIdx.x;   // (256 threads; SKS_GEOM_BINNED_THREADS on the binned path, which has no cover rows to build)
     const bool live = idx < P;
     // vf > 0: the views are vf per FRAME and every frame has its own P Gaussians (parameters stacked (F,P,..)): view v renders
     // frame v / vf.  Everything downstream is per (view, Gaussian) record and never sees the difference.
@@ -114,9 +113,8 @@ __global__ __launch_bounds__(SKS_GEOM_COVER_THREADS > 256 ? SKS_GEOM_COVER_THREA
     // gridDim.z > 1 (the small path with a cover row set per plane): block z builds plane z's rows only -- every block computes the
     // view's (<= 256) Gaussians, block 0 stores them.  One block per view doing all C + 1 planes one after the other (4 536 words to
     // clear, fill and write for H36M) took 5.9-6.4 us on the critical path of every step; side by side: the single plane's time.
-    const int pz = blockIdx.z;
     const uint4 rect = geom_fwd_one(P, vt, vms, pms, means, opac, scales, rots, cov3Dp, smod, flags, g, radii, v, idx, live, pz == 0);
-    if (bin_hdr && blockIdx.x == 0 && blockIdx.y == 0 && pz == 0 && threadIdx.x < 64) bin_hdr[threadIdx.x] = 0u;   // (Bin::hdr: the kernels behind add to it)
+    if (bin_hdr && bx == 0 && v == 0 && pz == 0 && threadIdx.x < 64) bin_hdr[threadIdx.x] = 0u;   // (Bin::hdr: the kernels behind add to it)
     if (count) {
         // binned path: the reference's tiles_touched (forward.cu:271); the per-tile entry counts are k_bin_band_count's (a workgroup
         // per tile band, LDS atomics: until round 5 they were one global atomic per tile of the rect here, 14 us on the stress scene)
@@ -158,6 +156,21 @@ __global__ __launch_bounds__(SKS_GEOM_COVER_THREADS > 256 ? SKS_GEOM_COVER_THREA
         uint32_t* out = g.cover + ((size_t)v * (cover_planes ? C + 1 : 1) + (cover_planes ? pz : 0)) * pw;
         for (int i = threadIdx.x; i < pw; i += blockDim.x) out[i] = s_cov[i];
     }
+}
+
+__global__ __launch_bounds__(SKS_GEOM_COVER_THREADS > 256 ? SKS_GEOM_COVER_THREADS : 256) void k_geom_fwd(int P, int W, int H, ViewTan vt, const float* __restrict__ vms,
+                                                   const float* __restrict__ pms, const float* __restrict__ means,
+                                                   const float* __restrict__ opac, const float* __restrict__ scales,
+                                                   const float* __restrict__ rots, const float* __restrict__ cov3Dp,
+                                                   float smod, unsigned flags, Geom g, int* __restrict__ radii, int vf,
+                                                   uint32_t* __restrict__ count = nullptr, uint32_t* __restrict__ touched = nullptr,
+                                                   const float* __restrict__ features = nullptr, int C = 0,
+                                                   uint2* __restrict__ fmask = nullptr, uint32_t* __restrict__ bin_hdr = nullptr,
+                                                   int cover_planes = 0)
+{
+    __shared__ uint32_t s_cov[COVER_MAX_WORDS];
+    geom_fwd_block(s_cov, blockIdx.x, blockIdx.y, blockIdx.z, P, W, H, vt, vms, pms, means, opac, scales, rots, cov3Dp, smod, flags, g, radii, vf,
+                   count, touched, features, C, fmask, bin_hdr, cover_planes);
 }
 
 // sks_geometry_dv: the geometry pass of the fused-loss path (no cover rows, no binning) with the per-view scalars read from the

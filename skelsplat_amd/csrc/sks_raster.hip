@@ -97,19 +97,22 @@ inline void fill_geometry(const FwdArgs& a, bool have_cover, bool binned, int& f
     fsplit = (passes + pb - 1) / pb;                                  // fill blocks per (plane, band) row
 }
 
+// zfill: the fill role runs for the planes zid < zfill only (the rest were zeroed by the launch in front, launch_geom_fill); the
+// composite role runs for every (view, Gaussian) and stores its tiles on whatever plane they are
 template <int CG>
-void launch_fwd_small(const FwdArgs& a_in, int V, int gy, hipStream_t st, const ProfScope& prof)
+void launch_fwd_small(const FwdArgs& a_in, int V, int gy, int zfill, hipStream_t st, const ProfScope& prof)
 {
     FwdArgs a = a_in;
     const int ncomp = a.tslots * a.P * V;
     a.ncomp = ncomp;
     int fsplit, pb;
     fill_geometry(a, a.g.cover != nullptr, false, fsplit, pb);
-    const int rows_zy = (a.C + 1) * V * gy;
+    if (zfill == 0) fsplit = 0;                                       // (no plane left to fill: one z slice of composite blocks)
+    const int rows_zy = (zfill > 0 ? zfill : 1) * gy;                 // the composite blocks index the rows of THIS grid
     const int xc = (ncomp + rows_zy - 1) / rows_zy;                   // composite blocks appended to every row
     const int cap = (a.P + 15) & ~15;
     const size_t lds = DynList<CG>::bytes(cap, CG);
-    dim3 grid(fsplit + xc, gy, (a.C + 1) * V);
+    dim3 grid(fsplit + xc, gy, zfill > 0 ? zfill : 1);
     const bool nt = !(a.flags & SKS_NO_NT_STORES);
     if (a.W % 4 == 0) {
         if (nt) SKS_LAUNCH(prof, (k_render_fwd_sparse<CG, 4, true>), grid, dim3(256), lds, st, a, a.cp1_magic, gy, fsplit, pb, (const uint32_t*)a.g.cover);
@@ -119,6 +122,62 @@ void launch_fwd_small(const FwdArgs& a_in, int V, int gy, hipStream_t st, const 
     } else {
         SKS_LAUNCH(prof, (k_render_fwd_sparse<CG, 1, false>), grid, dim3(256), lds, st, a, a.cp1_magic, gy, fsplit, pb, (const uint32_t*)a.g.cover);
     }
+}
+
+// ---- early fill: the last E (view, plane) planes of a plain small-path forward are zeroed by the geometry launch ----
+// How many.  The early region should keep the stores going for as long as the geometry blocks need beside them and no
+// longer (its blocks run at the geometry role's occupancy, and every plane moved costs the main launch nothing but
+// leaves the geometry launch's tail exposed): a fixed number of BYTES, whatever the call -- the geometry role's duration
+// depends on P, not on the image --, in whole planes, and never more than a quarter of the call.
+// SKS_EARLY_FILL_BYTES = 36 MB: the interleaved sweep on the H36M two-call step (72 planes of 4 MB; E = 0 / 5 / 9 / 14 / 18
+// planes: 65.3 / 63.2 / 62.5 / 62.6 / 63.3 us per step, profiles/early_fill_sweep.jsonl, NOTES_experiments.md "Early fill");
+// 31 Panoptic views (620 planes of 8.3 MB) get 5 planes = 41 MB for the same geometry latency (measured: 882 -> 878 us).
+#ifndef SKS_EARLY_FILL_BYTES
+#define SKS_EARLY_FILL_BYTES (36u << 20)
+#endif
+inline int early_fill_planes(unsigned flags, int planes, size_t plane_bytes)
+{
+    const int field = (int)((flags >> SKS_BIN_GROUPS_SHIFT) & 7u);
+    if (field == 7) return planes;
+    if (field) return (planes * field + 15) / 16;
+    const size_t want = ((size_t)SKS_EARLY_FILL_BYTES + plane_bytes / 2) / plane_bytes;
+    return (int)(want < (size_t)(planes / 4) ? want : (size_t)(planes / 4));
+}
+
+inline unsigned magic32(unsigned d) { return (unsigned)(((1ull << 32) + d - 1) / d); }   // x / d == umulhi(x, magic32(d)) for x * d < 2^32 (d >= 2)
+
+// The geometry launch with the early-fill role (k_geom_fwd_fill) for the planes zid >= zid0.  The early blocks are always
+// linear (pass-major) fill blocks, also where the main launch uses row-aligned ones: whole planes change hands, so the
+// two launches need not agree on how a band is cut.
+// early_fill_cut: the early region's fill blocks per (plane, band) row and passes per block; false where the kernel's block
+// index arithmetic would not be exact (a forced large E on very large images: the caller then keeps the one-launch layout).
+bool early_fill_cut(const FwdArgs& a_in, int V, int gy, int gplanes, int zid0, int& fsplit, int& pb)
+{
+    FwdArgs a = a_in;
+    a.flags |= SKS_FILL_LINEAR;
+    fill_geometry(a, true, false, fsplit, pb);
+    const long long rows = (long long)fsplit * gy, nfill = rows * ((a.C + 1) * V - zid0);
+    return fsplit >= 1 && pb >= 1 && nfill * rows < (1ll << 32) && (long long)V * gplanes + nfill < (1ll << 31);
+}
+
+void launch_geom_fill(const FwdArgs& a, int V, int gy, int gplanes, int zid0, int fsplit, int pb, const ViewTan& vt,
+                      const float* viewmatrix, const float* projmatrix, const float* means3D, const float* opacities,
+                      const float* scales, const float* rotations, const float* cov3D_precomp, float smod, int* radii,
+                      hipStream_t st, ProfScope& prof)
+{
+    const long long rows = (long long)fsplit * gy, nfill = rows * ((a.C + 1) * V - zid0);
+    const int ngeom = V * gplanes;
+    const EarlyFill f{ a.out_color, a.out_invdepth, a.C, a.W, a.H, gy, gplanes, ngeom, zid0, fsplit, pb, a.cp1_magic,
+                       rows > 1 ? magic32((unsigned)rows) : 0u, fsplit > 1 ? magic32((unsigned)fsplit) : 0u };   // (0: divisor 1)
+    const dim3 grid((unsigned)(ngeom + nfill));
+    const size_t lds = (size_t)gy * cover_cw(a.W) * 4;   // one plane's cover rows (<= COVER_MAX_WORDS words: cover_enabled)
+    const bool nt = !(a.flags & SKS_NO_NT_STORES);   // (fill_half_mode implies it)
+    const int ppt = (a.W % 4 == 0 || fill_half_mode(a)) ? 4 : 1;
+#define SKS_GF_ARGS f, a.P, vt, viewmatrix, projmatrix, means3D, opacities, scales, rotations, cov3D_precomp, smod, a.flags, a.g, radii, a.features, a.cover_planes
+    if (ppt == 4 && nt) SKS_LAUNCH_FIRST(prof, (k_geom_fwd_fill<4, true>), grid, dim3(256), lds, st, SKS_GF_ARGS);
+    else if (ppt == 4) SKS_LAUNCH_FIRST(prof, (k_geom_fwd_fill<4, false>), grid, dim3(256), lds, st, SKS_GF_ARGS);
+    else SKS_LAUNCH_FIRST(prof, (k_geom_fwd_fill<1, false>), grid, dim3(256), lds, st, SKS_GF_ARGS);
+#undef SKS_GF_ARGS
 }
 
 template <int CG>
@@ -334,6 +393,32 @@ int forward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, con
     if (!small) g.cover = nullptr;   // (the binned path's cover rows are per plane: Bin::coverp, k_bin_scan + k_bin_sort_long)
     const int gthreads = small ? 256 : SKS_GEOM_BINNED_THREADS;
     const int gplanes = (small && g.cover && cover_per_plane(P, W, H, C)) ? C + 1 : 1;     // a block per plane's cover rows
+    FwdArgs a{ P, C, W, H, flags, g, features, out_color, out_invdepth, final_T, n_contrib, composite_slots(flags, V, P),
+               ((1u << 20) + (unsigned)C) / (unsigned)(C + 1), 0, (!small || (g.cover && cover_per_plane(P, W, H, C))) ? 1 : 0,
+               (W >= 2 && W < 16384) ? (unsigned)(((1ull << 32) + (unsigned)W - 1) / (unsigned)W) : 0u };
+    const int cg = pick_cg(C);
+    // Plain small-path forward with cover rows: the geometry launch zeroes the last `early` planes (launch_geom_fill), the fill +
+    // composite launch streams the planes in front of them, and ONE kind-0 scope spans both -- the time in which every byte of the
+    // output was written.  Not for sks_forward_backward (its geom_done event fires when the geometry records exist, not when
+    // the early fill has drained), not with the debug planes, not with a synchronise between the stages.
+    const int planes = (C + 1) * V;
+    int early = 0;
+    if (small && !hook && g.cover && !final_T && !n_contrib && !(flags & (SKS_DEBUG_SYNC | SKS_NO_EARLY_FILL)))
+        early = early_fill_planes(flags, planes, HW * 4);
+    int efs = 0, epb = 0;
+    if (early > 0 && early_fill_cut(a, V, gy, gplanes, planes - early, efs, epb)) {
+        ProfScope prof(0, st, true);
+        launch_geom_fill(a, V, gy, gplanes, planes - early, efs, epb, vt, viewmatrix, projmatrix, means3D, opacities, scales, rotations,
+                         cov3D_precomp, scale_modifier, radii, st, prof);
+        switch (cg) {
+            case 4: launch_fwd_small<4>(a, V, gy, planes - early, st, prof); break;
+            case 16: launch_fwd_small<16>(a, V, gy, planes - early, st, prof); break;
+            case 20: launch_fwd_small<20>(a, V, gy, planes - early, st, prof); break;
+            default: launch_fwd_small<32>(a, V, gy, planes - early, st, prof); break;
+        }
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     if (hook && small && hook->geom_done)
         hipExtLaunchKernelGGL(k_geom_fwd, dim3((P + gthreads - 1) / gthreads, V, gplanes), dim3(gthreads), 0, st, nullptr, hook->geom_done, 0,
                               P, W, H, vt, viewmatrix, projmatrix, means3D, opacities, scales, rotations, cov3D_precomp, scale_modifier,
@@ -349,18 +434,14 @@ int forward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, con
         if (int rc = hook->after_geom(hook->ctx)) return rc;
     }
 
-    FwdArgs a{ P, C, W, H, flags, g, features, out_color, out_invdepth, final_T, n_contrib, composite_slots(flags, V, P),
-               ((1u << 20) + (unsigned)C) / (unsigned)(C + 1), 0, (!small || (g.cover && cover_per_plane(P, W, H, C))) ? 1 : 0,
-               (W >= 2 && W < 16384) ? (unsigned)(((1ull << 32) + (unsigned)W - 1) / (unsigned)W) : 0u };
-    const int cg = pick_cg(C);
     if (small) {
         {
             ProfScope prof(0, st, true);
             switch (cg) {
-                case 4: launch_fwd_small<4>(a, V, gy, st, prof); break;
-                case 16: launch_fwd_small<16>(a, V, gy, st, prof); break;
-                case 20: launch_fwd_small<20>(a, V, gy, st, prof); break;
-                default: launch_fwd_small<32>(a, V, gy, st, prof); break;
+                case 4: launch_fwd_small<4>(a, V, gy, planes, st, prof); break;
+                case 16: launch_fwd_small<16>(a, V, gy, planes, st, prof); break;
+                case 20: launch_fwd_small<20>(a, V, gy, planes, st, prof); break;
+                default: launch_fwd_small<32>(a, V, gy, planes, st, prof); break;
             }
         }
         STAGE_CHECK("render(small)");
@@ -593,9 +674,10 @@ int sks_forward_backward(int V, int P, int C, int W, int H, const float* viewmat
     // keeps the second stream's tail for itself (SKS_FB_NO_JOIN: a sharded step's collective wants the gradients THERE).
     const bool crowded = small && (long long)V * P > FB_OVERLAP_MAX_PAIRS && !no_join;
     if (!aux_stream || aux_stream == stream || P == 0 || (flags & SKS_DEBUG_SYNC) || (!small && ng < 2) || crowded) {
-        // nothing to run side by side: one after the other on the caller's stream
+        // nothing to run side by side: one after the other on the caller's stream (the one-call form keeps its launch layout on
+        // every route: no early fill)
         if (int rc = forward_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, means3D, features, opacities, scales, rotations,
-                                  cov3D_precomp, scale_modifier, flags, out_color, out_invdepth, radii, geom, binning, bin_capacity,
+                                  cov3D_precomp, scale_modifier, flags | SKS_NO_EARLY_FILL, out_color, out_invdepth, radii, geom, binning, bin_capacity,
                                   num_rendered_dev, nullptr, nullptr, stream, nullptr))
             return rc;
         if (int rc = backward_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, bg, means3D, features, opacities, scales,
