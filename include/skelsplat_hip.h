@@ -338,14 +338,18 @@ int sks_knn3_meandist2_grid(int P, const float* points, float* mean_dist2, void*
  * so render + clamp + masked-L2 + backward can be evaluated on the covered tiles alone.  Where the render is zero the
  * loss only sees the heat-maps (mask gt > 0, error gt^2): a per-frame constant; where it is positive the exact term
  * replaces that constant.
- *  sks_gt_tile_stats (once per frame): per-view totals {sum of gt^2, count of gt > 0} (V x 2 doubles); optionally
- *      (tile_S / tile_N non-NULL) the same per (view, tile, channel) as (V, Ty*Tx, C) floats;
+ *  sks_gt_tile_stats (once per frame): per-view totals {sum of gt^2 over the pixels with gt > 0, count of gt > 0} (V x 2
+ *      doubles) -- the masked-L2 sums S and N of an all-zero render, whose mask leaves out every pixel with gt <= 0: planes
+ *      need not be normalised to [0, 1], a negative entry adds to neither (for planes without negative entries the first is
+ *      the plain sum of squares); optionally (tile_S / tile_N non-NULL) the same per (view, tile, channel) as (V, Ty*Tx, C) floats;
  *  sks_geometry: the geometry stage of sks_forward alone (fills `geom` and `radii`);
  *  sks_backward_fused_loss: like sks_backward, but takes the heat-maps `gt` (V,C,H,W) instead of dL/d(render):
  *      re-composites each covered pixel, forms 2 (clamp(r) - gt) on the mask {gt > 0 or r > 0} on the fly, and
  *      returns per-view {S, N} (loss_v = S/N) in loss_sums = gt_totals + the corrections of the pixels with a
  *      positive render; gradients are UNSCALED (multiply by 1/N_v, e.g. with sks_loop_pack_grads).  P <= 64.
- *      tile_S / tile_N are not read (may be NULL).
+ *      tile_S / tile_N are not read (may be NULL).  A view whose mask is empty (all-zero heat-maps, nothing rendered)
+ *      returns {0, 0} and gradients that are exactly zero; packed_raw_grads, which divides by N_v, is scaled by 1 for such
+ *      a view (N_v < 1) and stays finite: zero.
  *  Views of different image sizes in ONE launch sequence (H36M mixes 1000- and 1002-wide sensors,
  *  scene/dataset_readers.py:68-80): nothing dense is written on this path, so sks_geometry, sks_backward_fused_loss
  *  and sks_loop_fused_step accept view_wh = V x {W_v, H_v} (W, H arguments: the largest) and, for the heat-maps,

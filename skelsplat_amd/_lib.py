@@ -23,6 +23,7 @@ SKS_BIN_CLEAN = 64
 SKS_RAW_GRADS = 128
 SKS_FB_NO_JOIN = 1
 SKS_BIN_GROUPS_SHIFT = 16
+SKS_BWD_WG_SHIFT = 23     # bits 23..25: workgroups per (view, Gaussian) of the wave-resident backward = 16 >> (value - 1); 0 = automatic
 SKS_SSIM_SCRATCH_BYTES = 64 * 8
 SKS_SOFTARGMAX_STATS = 6
 SKS_REPORT_MAX_SAVES = 8

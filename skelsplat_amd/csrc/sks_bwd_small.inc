@@ -618,11 +618,15 @@ __global__ __launch_bounds__(256, (DFEAT || CG > 20) ? 1 : 4) void k_render_bwd_
     }
 }
 
-// per (view, tile, channel) statistics of the constant pseudo-GT heat-maps, once per scene: sum of gt^2 and count of
-// gt > 0 (what the masked-L2 loss sees wherever the render is zero), and their per-view totals.
+// per (view, tile, channel) statistics of the constant pseudo-GT heat-maps, once per scene: sum of gt^2 over gt > 0 and count
+// of gt > 0 (what the masked-L2 loss sees wherever the render is zero: its mask leaves a pixel with gt <= 0 out, so a negative
+// entry of planes that are not normalised to [0, 1] adds nothing, as in k_masked_l2 and in k_render_bwd_wave's correction),
+// and their per-view totals.  For planes without negative entries the sums are the plain sums of squares, bit for bit.
 // Streaming layout: block (band, channel, view); a thread owns one 4-pixel column of a tile and walks the tile's 16
 // rows (16 independent 16-byte loads; a wavefront reads 1 KB contiguous per row), the four threads of a tile are
 // combined with DPP quad permutes in a fixed order -- one pass over the heat-maps at streaming rate, reproducible sums.
+__device__ __forceinline__ float pos_sq(float g) { return g > 0.0f ? g * g : 0.0f; }
+
 __global__ __launch_bounds__(256) void k_gt_tile_stats(int C, int W, int H, const float* __restrict__ gt, float* __restrict__ tile_S,
                                                         float* __restrict__ tile_N, double* __restrict__ totals)
 {
@@ -645,7 +649,7 @@ __global__ __launch_bounds__(256) void k_gt_tile_stats(int C, int W, int H, cons
                     g[r] = r < rows ? *reinterpret_cast<const float4*>(plane + (size_t)(y0 + r) * W + x) : make_float4(0, 0, 0, 0);
 #pragma unroll
                 for (int r = 0; r < TILE; r++) {
-                    S += (g[r].x * g[r].x + g[r].y * g[r].y) + (g[r].z * g[r].z + g[r].w * g[r].w);
+                    S += (pos_sq(g[r].x) + pos_sq(g[r].y)) + (pos_sq(g[r].z) + pos_sq(g[r].w));
                     N += ((g[r].x > 0.0f ? 1.0f : 0.0f) + (g[r].y > 0.0f ? 1.0f : 0.0f)) +
                          ((g[r].z > 0.0f ? 1.0f : 0.0f) + (g[r].w > 0.0f ? 1.0f : 0.0f));
                 }
@@ -654,7 +658,7 @@ __global__ __launch_bounds__(256) void k_gt_tile_stats(int C, int W, int H, cons
                     for (int k = 0; k < 4; k++)
                         if (x + k < W) {
                             const float g = plane[(size_t)(y0 + r) * W + x + k];
-                            S += g * g;
+                            S += pos_sq(g);
                             N += g > 0.0f ? 1.0f : 0.0f;
                         }
             }

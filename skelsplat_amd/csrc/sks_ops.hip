@@ -319,6 +319,9 @@ namespace {
 // ------------------------------------------------------------------------------------------------------------
 // TOTALS: also accumulates, per view, the sum of out^2 and the count of out > 0 (what sks_gt_tile_stats would read back
 // from the planes: the masked-L2 loss of an all-zero render), so a frame's heat-maps are written and never re-read.
+// (sks_gt_tile_stats squares an entry only where it is positive; here every entry is non-negative by construction -- cmin is the
+// product of the factors' minima, fp32 multiplication is monotone and the factors are non-negative, so row * col - cmin >= 0 and
+// den > 0 -- and the plain sum of squares is the same sum.  The same holds for k_heatmap_totals.)
 __global__ void k_heatmap_totals_finish(int V, double* __restrict__ totals);
 template <bool TOTALS>
 __global__ __launch_bounds__(256) void k_heatmaps(int W, int H, int J, const float* __restrict__ row, const float* __restrict__ col,

@@ -8,8 +8,9 @@ from ._base import ForwardState, ViewBatch, _accum, _bg_channels, _f32c, _f32c_p
 
 class GtStats:
     """Per-scene statistics of the constant pseudo-GT heat-maps (V,C,H,W): what the masked-L2 loss sees wherever the
-    render is zero.  `offsets` (HOST size_t array or None): views of different sizes -- `gt` is then a flat fp32 buffer
-    and offsets[v] the start (in floats) of view v's (C,H_v,W_v) planes (HeatmapSet)."""
+    render is zero (sum of gt^2 and count over the pixels with gt > 0: a negative entry is outside the mask).  `offsets`
+    (HOST size_t array or None): views of different sizes -- `gt` is then a flat fp32 buffer and offsets[v] the start (in
+    floats) of view v's (C,H_v,W_v) planes (HeatmapSet)."""
     __slots__ = ("gt", "tile_S", "tile_N", "totals", "offsets", "factors")
 
     def __init__(self):
@@ -128,7 +129,8 @@ class HeatmapSet:
 
 
 def gt_tile_stats(gt, out=None, tiles=False):
-    """Per-view heat-map totals (what the masked-L2 loss is for an all-zero render); `tiles=True` also fills the per
+    """Per-view heat-map totals (what the masked-L2 loss is for an all-zero render: {sum of gt^2 over gt > 0, count of gt > 0},
+    planes of any sign); `tiles=True` also fills the per
     (view, tile, channel) arrays.  `out`: a GtStats of the same shape to refill in place (scene streaming keeps every
     pointer stable)."""
     gt = _f32c(gt, "gt")

@@ -259,6 +259,138 @@ def run_fused_loss_case(seed, dev):
         raise AssertionError(f"{tag} -> {str(e)[:300]}") from None
 
 
+def _plane_stats(views, planes, C, dev):
+    """GtStats of per-view (C,H_v,W_v) planes: one (V,C,H,W) tensor, or (views of different sizes) a HeatmapSet's flat buffer
+    with the totals of each size group."""
+    if not views.mixed:
+        return R.gt_tile_stats(torch.stack(list(planes)))
+    hs = R.HeatmapSet(views.sizes, C, dev)
+    for v, pl in enumerate(planes):
+        hs.planes[v].copy_(pl)
+    stats = R.GtStats.of_set(hs)
+    for key, vs in hs.groups.items():
+        stats.totals[vs] = R.gt_tile_stats(hs.group(key)).totals
+    return stats
+
+
+def run_hard_loss_case(seed, dev, case=None, refs=None):
+    """The sparse fused-loss step on one scene of tests/fused_loss_cases.py (draw_hard(seed), or `case` with its references `refs`)
+    against the CPU reference of tests/fused_loss_ref.py: mask counts exactly, the loss sum within 1e-5, every gradient at the
+    oracle tolerance (or, where the case says so, the oracle's computed rounding bound); the same bits whatever the workgroup count
+    and from run to run; the dense device path at its own tolerance; planes against factors where the case has heat-map inputs.
+    -> dict(s_ratio = largest |S - S_ref| / S_ref, grad_excess = largest share of the gradient tolerance used -- in units of
+    2^-24 x sum|terms| where the bound is the tolerance --, mask_pixels, wg = the default's workgroups per (view, Gaussian))."""
+    import copy
+    from tests import fused_loss_cases as FC
+    from tests import fused_loss_ref as FR
+    from skelsplat_amd import _lib
+    from skelsplat_amd.ops import masked_l2
+    from skelsplat_amd.heatmaps import generate_heatmaps, heatmap_factors
+    case = FC.draw_hard(seed) if case is None else case
+    refs = FR.case_reference(case) if refs is None else refs
+    t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    V, P, C = case.V, case.P, case.C
+    tag = f"hard fused-loss case {case.name} seed {case.seed}: P={P} C={C} sizes={case.sizes} bg={case.bg is not None} aa={case.aa} " \
+          f"scale_modifier={case.smod} cov3D_precomp={case.cov is not None}"
+    out = dict(s_ratio=0.0, grad_excess=0.0, mask_pixels=float(min(r.N for r in refs)), wg=16.0 if V * P <= 400 else 8.0)
+    try:
+        cams = [copy.copy(cam).to(dev) for cam in case.cams]
+        views = R.ViewBatch.from_cameras(cams, allow_mixed=True)
+        args = tuple(t(a) for a in case.params + (case.cov,))
+        bgt = None if case.bg is None else torch.tensor(case.bg, device=dev)
+        keys = [k for k, _ in FR.GRADS if (k not in ("scales", "rotations") or case.cov is None) and (k != "cov3D" or case.cov is not None)]
+        st = R.geometry_views(views, args[0], C, args[2], args[3], args[4], args[5], scale_modifier=case.smod, antialiasing=case.aa)
+        for v in range(V):
+            assert np.array_equal(st.radii[v].cpu().numpy(), refs[v].fwd["radii"]), f"radii of view {v}"
+        flags0 = st.flags
+
+        def step(stats, wg=0, packed=None):
+            st.flags = flags0 | (wg << _lib.SKS_BWD_WG_SHIFT)
+            try:
+                g, sums = R.backward_fused_loss(st, stats, *args, bg=bgt, packed_out=packed)
+            finally:
+                st.flags = flags0
+            return {k: g[k] for k in keys}, sums
+
+        def against_reference(what, g, sums, rs, gts):
+            gn, sn = {k: x.cpu().numpy() for k, x in g.items()}, sums.cpu().numpy()
+            for v, r in enumerate(rs):
+                assert sn[v, 1] == r.N, (f"{what}: mask count of view {v}", sn[v, 1], r.N)      # integers: exact
+                ratio = abs(sn[v, 0] - r.S) / r.S if r.S else abs(sn[v, 0])
+                out["s_ratio"] = max(out["s_ratio"], ratio)
+                terms = FR.corrected_sum(r, gts[v])      # (what the kernel's fp32 partial sums of S carry)
+                print(f"{case.name} {what} view {v}: N = {r.N}, S = {float(sn[v, 0])!r} vs {r.S!r}, |dS| / S = {ratio:.2e}"
+                      f" = {abs(sn[v, 0] - r.S) / (util.EPS32 * terms) if terms else 0.0:.2f} x 2^-24 x sum(e^2 + gt^2) over the corrected pixels")
+                assert abs(sn[v, 0] - r.S) <= 1e-5 * r.S, (f"{what}: loss sum of view {v}", sn[v, 0], r.S)
+                for ours, theirs in FR.GRADS:
+                    if ours not in gn:
+                        continue
+                    got, want = gn[ours][v], r.bwd[theirs].reshape(gn[ours][v].shape)
+                    if case.bounds:
+                        bound = r.bwd["bound"][theirs].reshape(got.shape)
+                        ex = util.bound_excess(got, want, bound)
+                        print(f"  {theirs}: excess {ex:.2f} x 2^-24 x sum|terms| (allowed {util.BOUND_KAPPA:g})")
+                        out["grad_excess"] = max(out["grad_excess"], ex)
+                        util.assert_close_bound(f"{what} view {v} {theirs}", got, want, bound, rtol=1e-3)
+                    else:
+                        w64 = np.abs(want.astype(np.float64))
+                        ex = float((np.abs(got.astype(np.float64) - want) / (1e-5 * (w64.max() + 1e-30) + 1e-3 * w64)).max())
+                        print(f"  {theirs}: {ex:.3f} of the tolerance")
+                        out["grad_excess"] = max(out["grad_excess"], ex)
+                        util.assert_close(f"{what} view {v} {theirs}", got, want, rtol=1e-3, atol_scale=1e-5)
+
+        planes = [t(g) for g in case.gt]
+        stats = _plane_stats(views, planes, C, dev)
+        packed = torch.full((V, P, 11), float("nan"), device=dev) if "empty" in case.claims else None
+        g0, s0 = step(stats, packed=packed)
+        against_reference("planes", g0, s0, refs, case.gt)
+        # 16, 8 and 4 workgroups per (view, Gaussian), and the default again: the same bits (the default is 16 up to 400 pairs, 8 beyond)
+        for wg in (1, 2, 3, 0):
+            g1, s1 = step(stats, wg=wg)
+            assert torch.equal(s1, s0), (f"loss sums with workgroup field {wg}", s1, s0)
+            for k in keys:
+                assert torch.equal(g1[k], g0[k]), f"{k} with workgroup field {wg}"
+        if packed is not None:      # nothing in the mask: {0, 0}, exact zeros, and the 1/N scale of the packed gradients is 1
+            assert not s0.any() and all(not g0[k].any() for k in keys), "an empty view must give zero sums and gradients"
+            assert torch.isfinite(packed).all() and not packed.any(), "packed gradients of an empty view"
+        # the dense device path: forward(clamp) -> masked L2 -> backward, one call per image size
+        for (w, h), vs in {sz: [v for v in range(V) if case.sizes[v] == sz] for sz in case.sizes}.items():
+            gviews = R.ViewBatch.from_cameras([cams[v] for v in vs])
+            color, _, radii, std = R.forward_views(gviews, *args, scale_modifier=case.smod, antialiasing=case.aa, clamp01=True)
+            dL, S, N = masked_l2(color, torch.stack([planes[v] for v in vs]))
+            gd = R.backward_views(std, *args, dL, bg=bgt)
+            assert torch.equal(s0[vs, 1], N), ("dense mask counts", s0[vs, 1], N)
+            assert ((s0[vs, 0] - S).abs() <= 1e-5 * S.abs()).all(), ("dense loss sums", s0[vs, 0], S)
+            for k in keys:
+                util.assert_close(f"sparse vs dense {k}", g0[k][vs].cpu(), gd[k].cpu(), rtol=1e-4, atol_scale=1e-5)
+        if case.hm is not None and not views.mixed:
+            # the loop's own kind of planes, as planes and as separable factors: the factor instantiations of this channel group
+            hmi = [t(case.hm[k]) for k in ("means", "scaling", "rotation", "p2d")]
+            hm = generate_heatmaps(*hmi, cams)
+            stats_p = R.gt_tile_stats(hm)
+            fac = R.HeatmapFactors(V, C, views.W, views.H, dev)
+            heatmap_factors(*hmi, cams, views=views, out=fac)
+            for v in range(V):
+                assert torch.equal(fac.planes(v), hm[v]), "factor planes"
+            fst = R.GtStats.of_factors(fac)
+            fac.totals(views, fst.totals)
+            assert torch.equal(fst.totals[:, 1], stats_p.totals[:, 1]), "factor totals N"
+            gp, sp = step(stats_p)
+            gf, sf = step(fst)
+            assert torch.equal(sf[:, 1], sp[:, 1]), ("factor mask counts", sf, sp)
+            assert ((sf[:, 0] - sp[:, 0]).abs() <= 1e-6 * sp[:, 0].abs()).all(), ("factor loss sums", sf, sp)
+            for k in keys:
+                assert torch.equal(gf[k], gp[k]), f"factors vs planes {k}"
+            hmn = hm.cpu().numpy()
+            assert float(hmn.min()) >= 0.0 and float(hmn.max()) > 0.5
+            rs = [FR.view_reference(case.params, case.ocams[v], hmn[v], bg=case.bg, antialiasing=case.aa, scale_modifier=case.smod,
+                                    cov3D_precomp=case.cov, bounds=case.bounds, fwd=refs[v].fwd) for v in range(V)]
+            against_reference("heat-map planes", gp, sp, rs, hmn)
+        return out
+    except AssertionError as e:
+        raise AssertionError(f"{tag} -> {str(e)[:400]}") from None
+
+
 def run_loop_case(seed, dev):
     """MultiViewLoop's production path (sparse fused step, device-side Adam tail, hipGraph) against its dense per-launch path (full
     images, sks_masked_l2, dense backward, the same optimiser) on a random scene: 1-6 views under an accumulation_steps of 1-5 (quirk

@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import util
+from tests import fused_loss_ref, util
 from skelsplat_amd import rasterizer as R
 from oracle import oracle as orc
 
@@ -123,7 +123,8 @@ def _check_backward(cams, params, dev, outs, states, seed=0, rtol=1e-3, bg=None,
 def _check_fused_loss(cams, params, dev, outs, hm_planes):
     """The sparse fused training step (sks_geometry + sks_backward_fused_loss: render, clamp(0, 1), masked L2 and its
     gradient on the covered tiles only; train.py:140-161, gaussian_renderer/__init__.py:129, loss_utils.py:86-100) against
-    oracle render -> clamp -> masked L2 -> oracle backward on dense images.  hm_planes[v]: (C,H_v,W_v) device tensor."""
+    oracle render -> clamp -> masked L2 -> oracle backward on dense images (tests/fused_loss_ref.py).  hm_planes[v]: (C,H_v,W_v)
+    device tensor."""
     np_params = [p.detach().cpu().numpy() for p in params]
     P, C = params[1].shape
     views = R.ViewBatch.from_cameras(cams, allow_mixed=True)
@@ -143,17 +144,10 @@ def _check_fused_loss(cams, params, dev, outs, hm_planes):
     g = {k: v.cpu().numpy() for k, v in g.items() if v is not None}
     sums = sums.cpu().numpy()
     for v, cam in enumerate(cams):
-        o = outs[v]
-        gt = hm_planes[v].cpu().numpy()
-        render = np.clip(o["color"], 0.0, 1.0)
-        mask = (gt > 0) | (render > 0)
-        diff = (render - gt).astype(np.float32)
-        S = float((diff.astype(np.float64) ** 2)[mask].sum())
-        N = int(mask.sum())
+        r = fused_loss_ref.view_reference(np_params, _ocam(cam), hm_planes[v].cpu().numpy(), fwd=outs[v])
+        S, N, b = r.S, r.N, r.bwd
         assert int(sums[v, 1]) == N, (v, sums[v, 1], N)                     # mask counts are integers: exact
         assert abs(sums[v, 0] - S) <= 1e-5 * S, (v, sums[v, 0], S)
-        dL = (2.0 * diff * mask * ((o["color"] >= 0) & (o["color"] <= 1))).astype(np.float32)   # clamp's pass-through
-        b = orc.backward(o, *np_params, None, _ocam(cam), dL, None)
         for ours, theirs in GRADS[:5]:
             util.assert_close(f"fused view {v} {theirs}", g[ours][v], b[theirs].reshape(g[ours][v].shape), rtol=1e-3)
         assert np.abs(b["dL_dmeans3D"]).max() > 0

@@ -459,6 +459,36 @@ def test_gt_tile_stats(device, shape):
     torch.testing.assert_close(st3.totals[:, 0], st.totals[:, 0], rtol=1e-12, atol=0)
 
 
+@pytest.mark.parametrize("shape", [(2, 3, 48, 64), (1, 17, 50, 70), (2, 2, 33, 1030), (1, 5, 16, 4100)],
+                         ids=lambda s: "x".join(map(str, s)))
+def test_gt_tile_stats_signed(device, shape):
+    """test_gt_tile_stats' shapes with a fifth of the non-zero entries negative: the masked L2 of an all-zero render leaves a
+    pixel with gt <= 0 out (utils/loss_utils.py:88-91), so a negative entry adds to neither sum -- per tile and in the totals."""
+    from skelsplat_amd import rasterizer as R
+    V, C, H, W = shape
+    g = torch.Generator().manual_seed(3)
+    gt = torch.rand(shape, generator=g)
+    gt = torch.where(torch.rand(shape, generator=g) < 0.6, torch.zeros(()), gt)
+    gt = torch.where(torch.rand(shape, generator=g) < 0.2, -gt, gt)
+    assert int((gt < 0).sum()) > 100
+    st = R.gt_tile_stats(gt.to(device), tiles=True)
+    gy, gx = (H + 15) // 16, (W + 15) // 16
+    pad = torch.zeros((V, C, gy * 16, gx * 16), dtype=torch.float64)
+    pad[:, :, :H, :W] = gt.double()
+    t = pad.reshape(V, C, gy, 16, gx, 16)
+    S = (t * t * (t > 0)).sum(dim=(3, 5)).permute(0, 2, 3, 1).reshape(V, gy * gx, C)
+    N = (t > 0).double().sum(dim=(3, 5)).permute(0, 2, 3, 1).reshape(V, gy * gx, C)
+    assert torch.equal(st.tile_N.cpu().double(), N)
+    torch.testing.assert_close(st.tile_S.cpu().double(), S, rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(st.totals.cpu()[:, 0], S.sum(dim=(1, 2)), rtol=1e-6, atol=1e-6)
+    assert torch.equal(st.totals.cpu()[:, 1], N.sum(dim=(1, 2)))
+    assert float((S.sum(dim=(1, 2)) - (t * t).sum(dim=(1, 2, 3, 4, 5))).abs().min()) > 1.0      # (the plain sum of squares is another number)
+    # the negative entries set to zero: the same bits, per tile and in the totals
+    st0 = R.gt_tile_stats(gt.clamp_min(0.0).to(device), tiles=True)
+    assert torch.equal(st0.tile_S, st.tile_S) and torch.equal(st0.tile_N, st.tile_N) and torch.equal(st0.totals[:, 1], st.totals[:, 1])
+    torch.testing.assert_close(st0.totals[:, 0], st.totals[:, 0], rtol=1e-12, atol=0)
+
+
 @pytest.mark.parametrize("W,H", [(200, 160), (130, 77), (1030, 40)], ids=["200x160", "130x77", "1030x40"])
 def test_heatmap_kernel_equals_formula(device, W, H):
     """sks_heatmaps writes exactly what the tensor-op formula of skelsplat_amd/heatmaps.py gives (which the CPU suite
