@@ -143,6 +143,61 @@ int sks_backward(int V, int P, int C, int W, int H,
                  train.py:215-217); for V * P <= 256 it comes out of the same launch as the geometry backward */,
                  void* stream);
 
+/* Prefill (added to sks_version 14): the small-path backward zeroes planes for the NEXT forward.  A two-call step -- sks_forward,
+ * a loss that reads the image, sks_backward -- leaves HBM idle for the backward's two latency-bound launches (the compositing
+ * backward k_render_bwd_wave and the geometry backward k_geom_bwd_all), and a step's only mandatory bytes that do not depend on its
+ * own inputs are the zeros of the forward's output.  A caller that keeps TWO output sets and alternates between them lets the
+ * backward of step N write zeros over the last planes of the set step N + 1 renders into (the image of step N, in the other set,
+ * stays the caller's):
+ *
+ *  sks_prefill_planes: host only.  The rule: how many whole planes the compositing backward's launch (planes_wave) and the geometry
+ *  backward's launch (planes_geom) should carry for this call -- a function of the call (V, P, the image size, flags), 0 / 0 where
+ *  there is no prefill: off the wave-resident small path (P > 64, SKS_FORCE_BINNED), without 16-byte stores (they need W % 4 == 0, or
+ *  W % 4 == 2 with an even H), with SKS_NO_NT_STORES or SKS_DEBUG_SYNC -- and outside what its constants were measured on (the H36M
+ *  step): V * P outside 51 .. 85, C > 20, W % 4 != 0.  A caller that also asks for dL_dfeatures should not prefill either.  Together with the forward's own early region
+ *  (SKS_EARLY_FILL) never more than half of the (C + 1) * V planes.
+ *
+ *  sks_backward_prefill: sks_backward, bit for bit, whose launches also store 0.0f over the LAST planes_wave + planes_geom planes
+ *  of the set (next_color (V,C,H,W), next_invdepth (V,1,H,W)), in the plane order view-major, a view's C colour planes then its
+ *  inverse depth -- whole planes, non-temporal 16-byte stores, in blocks that run behind the launches' own (extra blockIdx.z layers
+ *  of k_render_bwd_wave, blocks 1.. of k_geom_bwd_all) and leave before any load or barrier.  Nothing else of the set is touched.  The
+ *  geometry backward's share rides in its launch when that is k_geom_bwd_all (dL_dmeans3D_mean given and V * P <= 256) and in the
+ *  compositing launch otherwise.  Both counts 0: exactly sks_backward (the set may be NULL).  Counts the call cannot carry are
+ *  refused, not ignored: off the wave-resident small path, without 16-byte stores, with SKS_DEBUG_SYNC (SKS_NO_NT_STORES in ITS flags
+ *  is ignored: that is the forward's store kind).  Any count on any other shape is carried, also where the rule answers 0 / 0.  The zeros are complete in `stream` order behind the call.
+ *
+ *  sks_forward_prefilled: sks_forward told that the LAST prefilled_planes planes of (out_color, out_invdepth) are zero already
+ *  -- written by nothing since an sks_backward_prefill of at least that many planes ordered before this call on `stream` (or by
+ *  anything else that left them 0.0f).  The fill + composite launch then streams the planes in front of them only (the geometry
+ *  launch's early region sits right in front of the prefilled one) and the composite blocks store their tiles on every plane, as
+ *  ever: the outputs are bit for bit those of sks_forward.  0: exactly sks_forward.  The promise is IGNORED -- every plane is
+ *  filled -- with final_T / n_contrib, with SKS_DEBUG_SYNC, off the small path, and for a launch that the measurement hook samples
+ *  without having bracketed the backward in front of it (below).  sks_forward_backward neither prefills nor takes a promise. */
+int sks_prefill_planes(int V, int P, int C, int W, int H, unsigned flags, int* planes_wave, int* planes_geom);
+int sks_forward_prefilled(int V, int P, int C, int W, int H,
+                          const float* viewmatrix, const float* projmatrix,
+                          const float* tanfovx /*HOST V*/, const float* tanfovy /*HOST V*/,
+                          const float* means3D, const float* features, const float* opacities,
+                          const float* scales, const float* rotations, const float* cov3D_precomp,
+                          float scale_modifier, unsigned flags,
+                          float* out_color, float* out_invdepth, int* radii,
+                          void* geom, void* binning, size_t bin_capacity, int* num_rendered_dev,
+                          float* final_T, uint32_t* n_contrib, int prefilled_planes, void* stream);
+int sks_backward_prefill(int V, int P, int C, int W, int H,
+                         const float* viewmatrix, const float* projmatrix,
+                         const float* tanfovx /*HOST V*/, const float* tanfovy /*HOST V*/,
+                         const float* bg,
+                         const float* means3D, const float* features, const float* opacities,
+                         const float* scales, const float* rotations, const float* cov3D_precomp,
+                         float scale_modifier, unsigned flags,
+                         const int* radii, const void* geom, const void* binning, size_t bin_capacity,
+                         const float* dL_dout_color, const float* dL_dout_invdepth,
+                         void* accum,
+                         float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dopacity,
+                         float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* dL_dfeatures,
+                         float* dL_dmeans3D_mean,
+                         float* next_color, float* next_invdepth, int planes_wave, int planes_geom, void* stream);
+
 /* sks_forward + sks_backward of the same inputs as ONE call, for a caller whose upstream gradient does not depend on the image
  * this call renders (dL_dout_color / dL_dout_invdepth complete in `stream` order when the call is made: a known gradient, or the
  * previous evaluation's).  On the small path (P <= SKS_SMALL_P) the backward needs the forward's geometry records, not its image,
@@ -580,7 +635,12 @@ int sks_eval_sequence(int N, int P, const float* pred, const float* gt, const in
  * on the caller's stream (the small path's kernels carry the pair on their own dispatch, hipExtLaunchKernelGGL).  The low 16
  * bits of `on`: 1 = every launch, n > 1 = every n-th launch of each kind (a bracketed launch costs ~6 us of queue time, so
  * sampling keeps the measured loop undisturbed); bits 16-17: kinds to leave OUT (bit 16: kind 0, bit 17: kind 1).  sks_prof_read waits for the recorded events, returns
- * the summed kernel time in milliseconds and the number of BRACKETED launches since the last read, and resets them. */
+ * the summed kernel time in milliseconds and the number of BRACKETED launches since the last read, and resets them.
+ * A kind-0 sample is the time in which every byte of the call's output was written.  For a forward that takes prefilled planes that
+ * is two intervals: its own launches, plus the launches of the sks_backward_prefill in front of it -- that call sees that the next
+ * forward will be sampled, brackets its two launches with marker events and parks the pair, the forward's sample takes it over, and
+ * the three readers below add the two intervals and count ONE sample per forward.  (A forward whose prefilling backward ran before
+ * the hook was enabled fills every plane itself, so its sample is whole too.) */
 int sks_prof_enable(int on);
 /* Enqueues ONE wavefront that idles for `microseconds` (wall clock) on `stream`: a stand-in for the wire time of a latency-bound
  * collective, so that one GPU can measure what a rank of many sees when the exchange takes that long (bench.py rank_step_8gpu). */

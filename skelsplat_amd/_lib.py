@@ -59,6 +59,11 @@ _FORWARD_IO = (("out_color", _vp), ("out_invdepth", _vp), ("radii", _vp), ("geom
 FORWARD_PARAMS = _CAMERAS + _GAUSSIANS + _FORWARD_IO + (("final_T", _vp), ("n_contrib", _vp), ("stream", _vp))
 BACKWARD_PARAMS = _CAMERAS + (("bg", _vp),) + _GAUSSIANS + (("radii", _vp), ("geom", _vp), ("binning", _vp), ("bin_capacity", _sz)) \
     + _UPSTREAM + _GRADS + (("stream", _vp),)
+# the prefill pair (include/skelsplat_hip.h): the same blocks with their extra parameters in front of `stream`, so a recorded block of
+# sks_forward / sks_backward becomes theirs by inserting the extras at FWD["stream"] / BWD["stream"]
+FORWARD_PREFILLED_PARAMS = FORWARD_PARAMS[:-1] + (("prefilled_planes", _i), ("stream", _vp))
+BACKWARD_PREFILL_PARAMS = BACKWARD_PARAMS[:-1] + (("next_color", _vp), ("next_invdepth", _vp), ("planes_wave", _i), ("planes_geom", _i),
+                                                  ("stream", _vp))
 FORWARD_BACKWARD_PARAMS = _CAMERAS + _GAUSSIANS + _FORWARD_IO + (("bg", _vp),) + _UPSTREAM + _GRADS \
     + (("stream", _vp), ("aux_stream", _vp), ("fb_flags", _u))
 
@@ -119,6 +124,9 @@ SIGNATURES = {
     "sks_forward": (_i, [ct for _, ct in FORWARD_PARAMS]),
     "sks_backward": (_i, [ct for _, ct in BACKWARD_PARAMS]),
     "sks_forward_backward": (_i, [ct for _, ct in FORWARD_BACKWARD_PARAMS]),
+    "sks_forward_prefilled": (_i, [ct for _, ct in FORWARD_PREFILLED_PARAMS]),
+    "sks_backward_prefill": (_i, [ct for _, ct in BACKWARD_PREFILL_PARAMS]),
+    "sks_prefill_planes": (_i, [_i, _i, _i, _i, _i, _u, C.POINTER(_i), C.POINTER(_i)]),
     "sks_mark_visible": (_i, [_i, _vp, _vp, _vp, _vp, _vp]),
     "sks_mean_views": (_i, [_i, _i, _vp, _i, _vp, _vp]),
     "sks_export_lists": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
@@ -158,6 +166,10 @@ SIGNATURES = {
 }
 
 
+_PREFILL_SYMBOLS = ("sks_forward_prefilled", "sks_backward_prefill", "sks_prefill_planes")
+HAS_PREFILL = True      # False only for an SKS_LIB_OVERRIDE library that predates the prefill pair (load)
+
+
 def load(build_if_missing=True):
     """Returns the loaded CDLL; raises ImportError with the build error if it cannot be produced."""
     global _lib
@@ -173,8 +185,13 @@ def load(build_if_missing=True):
                 raise ImportError(f"libskelsplat_hip.so is missing and could not be built: {e}") from e
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} not found; run `python -m skelsplat_amd.build`")
-    lib = C.CDLL(os.environ.get("SKS_LIB_OVERRIDE") or LIB_PATH)   # override: A/B of build variants (tools/ab_libs.sh)
+    override = os.environ.get("SKS_LIB_OVERRIDE")
+    lib = C.CDLL(override or LIB_PATH)   # override: A/B of build variants (tools/ab_libs.sh)
+    global HAS_PREFILL
     for name, (res, args) in SIGNATURES.items():
+        if override and name in _PREFILL_SYMBOLS and not hasattr(lib, name):
+            HAS_PREFILL = False      # an A/B against a build from before the prefill pair: its Workspace keeps one output set
+            continue
         fn = getattr(lib, name)  # AttributeError = ABI drift, fail loudly
         fn.restype = res
         fn.argtypes = args
@@ -192,6 +209,14 @@ def scratch_bytes(V, P, C_, W, H, bin_capacity=0):
     g, b, a = _sz(0), _sz(0), _sz(0)
     check(load().sks_scratch_bytes(V, P, C_, W, H, bin_capacity, C.byref(g), C.byref(b), C.byref(a)), "sks_scratch_bytes")
     return g.value, b.value, a.value
+
+
+def prefill_planes(V, P, C_, W, H, flags=0):
+    """(planes_wave, planes_geom): how many of the call's last planes the small-path backward's two launches zero for the next forward
+    (the library's rule, sks_prefill_planes; (0, 0) = no prefill for this call)."""
+    nw, ng = _i(0), _i(0)
+    check(load().sks_prefill_planes(V, P, C_, W, H, flags, C.byref(nw), C.byref(ng)), "sks_prefill_planes")
+    return nw.value, ng.value
 
 
 def ptr(t):

@@ -311,9 +311,20 @@ __device__ __forceinline__ unsigned rlu(unsigned x, int lane) { return (unsigned
 // HMF (with LOSS): the heat-maps are given by their separable factors (BwdArgs::hm_*) instead of planes.
 // ES (with LOSS): per-frame early stopping -- a workgroup whose frame has stopped leaves before anything else (the step tail
 // reads none of what it would write), so a stopped frame costs the launch nothing but that one load.
-template <int CG, bool DFEAT, bool LOSS, bool HMF = false, bool ES = false>
-__global__ __launch_bounds__(256, (DFEAT || CG > 20) ? 1 : 4) void k_render_bwd_wave(BwdArgs a, ViewTan vt, ViewOff vo)
+// PF (empty, or one PreFill by value -- plain variants only): the prefill role of sks_backward_prefill.  The grid then has extra
+// blockIdx.z layers behind the role's own pf.zs, last in dispatch order; their blocks leave here, before any load or barrier.
+// With the pack empty the kernel's signature and body are what they were without the role.
+template <int CG, bool DFEAT, bool LOSS, bool HMF = false, bool ES = false, class... PF>
+__global__ __launch_bounds__(256, (DFEAT || CG > 20) ? 1 : 4) void k_render_bwd_wave(BwdArgs a, ViewTan vt, ViewOff vo, PF... pf)
 {
+    static_assert(sizeof...(PF) <= 1 && (!LOSS || sizeof...(PF) == 0), "the prefill role belongs to the plain variants");
+    if constexpr (sizeof...(PF) == 1) {
+        const PreFill& f = (pf, ...);
+        if ((int)blockIdx.z >= f.zs) {   // (workgroup-uniform)
+            prefill_block(f, ((unsigned)((int)blockIdx.z - f.zs) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
+            return;
+        }
+    }
     static_assert(!(DFEAT && LOSS), "the fused-loss variant has no feature gradient");
     static_assert(LOSS || !HMF, "heat-map factors belong to the fused-loss variant");
     static_assert(LOSS || !ES, "early stopping belongs to the fused-loss variant");
@@ -326,7 +337,9 @@ __global__ __launch_bounds__(256, (DFEAT || CG > 20) ? 1 : 4) void k_render_bwd_
     // sp + gridDim.z, ...; slot s sums the tiles s, s + BWD_SPLITS, ... of the rect.  16 workgroups (one slot each) is the
     // shortest chain for a handful of views; with hundreds of (view, Gaussian) pairs in flight fewer, longer workgroups
     // share the header below and leave fewer empty ones.  The sums do not depend on the choice.
-    const int g = blockIdx.x, v = blockIdx.y, sp = blockIdx.z, zs = gridDim.z, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int zs_ = gridDim.z;
+    if constexpr (sizeof...(PF) == 1) zs_ = (pf, ...).zs;
+    const int g = blockIdx.x, v = blockIdx.y, sp = blockIdx.z, zs = zs_, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int P = a.P, C = a.C, W = vt.w[v], H = vt.h[v];
     const int NVS = NACC + C;
     const size_t HW = (size_t)H * W;

@@ -33,6 +33,10 @@ constexpr int PROF_MAX = 16384;
 struct ProfKind {
     hipEvent_t b[PROF_MAX], e[PROF_MAX];
     int created = 0, n = 0;
+    // kind 0 only: sample i's second interval, the prefill-carrying launches of the backward in front of its forward (ProfState::park)
+    hipEvent_t xb[PROF_MAX], xe[PROF_MAX];
+    bool hasx[PROF_MAX];
+    int xcreated = 0;
 };
 struct ProfState {
     bool on = false;
@@ -41,6 +45,12 @@ struct ProfState {
     bool recorded = false;   // bracket with hipEventRecord marker packets even where the launch could carry the pair itself
     int seen[2] = { 0, 0 };
     ProfKind kind[2];
+    // A backward that zeroes planes of the NEXT forward's outputs (sks_backward_prefill) while that forward's kind-0 launch will be
+    // bracketed brackets its own launches with this pair and parks it; the forward's scope takes it over (ProfScope, take_parked),
+    // so that a kind-0 sample stays the time in which every byte of the call's output was written.
+    hipEvent_t park_b = nullptr, park_e = nullptr;
+    bool parked = false;
+    hipStream_t park_st = nullptr;
 };
 thread_local ProfState* tl_prof = nullptr;   // allocated by the first sks_prof_enable of the thread
 
@@ -52,16 +62,30 @@ struct ProfScope {  // brackets ONE kernel launch -- or two back to back, SKS_LA
     hipStream_t st;
     bool ext;
     bool began = false;   // the begin event already stands in front of, or rides on, an earlier dispatch of this scope (SKS_LAUNCH_FIRST)
-    ProfScope(int kind, hipStream_t s, bool ext_ = false) : st(s), ext(ext_)
+    // take_parked (kind 0): this forward renders into planes the backward in front of it zeroed -- its parked pair joins the sample
+    ProfScope(int kind, hipStream_t s, bool ext_ = false, bool take_parked = false) : st(s), ext(ext_)
     {
         ProfState* ps = tl_prof;
-        if (!ps || !ps->on || ((ps->skip >> kind) & 1)) return;
+        if (!ps) return;
+        const bool parked = kind == 0 && ps->parked && take_parked && ps->park_st == s;
+        if (kind == 0) ps->parked = false;   // (a parked pair belongs to the very next forward or to none)
+        if (!ps->on || ((ps->skip >> kind) & 1)) return;
         if (ps->seen[kind]++ % ps->every != 0) return;
         ProfKind& p = ps->kind[kind];
         if (p.n >= PROF_MAX) return;
         if (p.n >= p.created) {
             if (hipEventCreate(&p.b[p.created]) != hipSuccess || hipEventCreate(&p.e[p.created]) != hipSuccess) return;
             p.created++;
+        }
+        p.hasx[p.n] = false;
+        if (parked) {
+            while (p.xcreated <= p.n) {
+                if (hipEventCreate(&p.xb[p.xcreated]) != hipSuccess || hipEventCreate(&p.xe[p.xcreated]) != hipSuccess) return;
+                p.xcreated++;
+            }
+            hipEvent_t t = p.xb[p.n]; p.xb[p.n] = ps->park_b; ps->park_b = t;
+            t = p.xe[p.n]; p.xe[p.n] = ps->park_e; ps->park_e = t;
+            p.hasx[p.n] = true;
         }
         k = &p;
         if (ps->recorded) ext = false;
@@ -76,6 +100,40 @@ struct ProfScope {  // brackets ONE kernel launch -- or two back to back, SKS_LA
         k->n++;
     }
 };
+// Will the next kind-0 scope of this thread be a sample?  (what a prefilling backward and a prefill-consuming forward ask)
+inline bool prof_next_forward_sampled()
+{
+    const ProfState* ps = tl_prof;
+    return ps && ps->on && !(ps->skip & 1) && ps->seen[0] % ps->every == 0 && ps->kind[0].n < PROF_MAX;
+}
+inline bool prof_has_parked(hipStream_t st) { return tl_prof && tl_prof->parked && tl_prof->park_st == st; }
+// the prefilling backward's bracket: marker packets in front of its first and behind its last launch
+inline void prof_park_begin(hipStream_t st)
+{
+    ProfState* ps = tl_prof;
+    ps->parked = false;
+    if (!ps->park_b && (hipEventCreate(&ps->park_b) != hipSuccess || hipEventCreate(&ps->park_e) != hipSuccess)) { ps->park_b = ps->park_e = nullptr; return; }
+    ps->park_st = st;
+    ps->parked = hipEventRecord(ps->park_b, st) == hipSuccess;
+}
+inline void prof_park_end(hipStream_t st)
+{
+    ProfState* ps = tl_prof;
+    if (ps && ps->parked && ps->park_st == st && hipEventRecord(ps->park_e, st) != hipSuccess) ps->parked = false;
+}
+// a sample's duration: its own pair plus, where a parked pair joined it, that one
+inline hipError_t prof_elapsed(ProfKind& p, int i, float* ms)
+{
+    hipError_t e = hipEventSynchronize(p.e[i]);
+    if (e == hipSuccess) e = hipEventElapsedTime(ms, p.b[i], p.e[i]);
+    if (e == hipSuccess && p.hasx[i]) {
+        float x = 0;
+        e = hipEventSynchronize(p.xe[i]);
+        if (e == hipSuccess) e = hipEventElapsedTime(&x, p.xb[i], p.xe[i]);
+        *ms += x;
+    }
+    return e;
+}
 // launch inside an `ext` ProfScope: the scope's events ride on the kernel's dispatch when it is active
 #define SKS_LAUNCH(prof, kernel, grid, block, lds, stream, ...)                                                  \
     do {                                                                                                         \

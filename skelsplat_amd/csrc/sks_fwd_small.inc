@@ -489,3 +489,42 @@ __global__ __launch_bounds__(256) void k_geom_fwd_fill(EarlyFill f, int P, ViewT
     const int shift = (int)((reinterpret_cast<uintptr_t>(out) >> 2) & 31u);   // passes cut on 128-byte lines of the address (fwd_fill_role)
     fill_bare<PPT, NT>(out, nullptr, nullptr, q * (256 * PPT) * f.pb + (int)threadIdx.x * PPT - shift, Nb, min(f.pb, 32));
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// The prefill role of the small-path backward's two launches (k_render_bwd_wave, k_geom_bwd_all): while they run HBM
+// carries almost nothing, so the blocks behind a launch's own grid zero the LAST planes of ANOTHER output set, the one
+// the next forward renders into (sks_backward_prefill / sks_forward_prefilled).  Fill block e of the role is block
+// (q, band, zid) of the region [zid0, zid0 + nz) in memory order, e = ((zid - zid0) * gy + band) * fsplit + q, as in
+// k_geom_fwd_fill: every argument by value, multiply-high index splits the host checked (prefill_cut), nothing loaded,
+// 16-byte non-temporal stores only (launchers: W % 4 == 0, or W % 4 == 2 with an even H).
+// ------------------------------------------------------------------------------------------------------------
+struct PreFill {
+    float* out_color;     // the OTHER output set
+    float* out_invdepth;
+    int C, W, H, gy;
+    int zid0;             // first plane of this launch's share, zid = view * (C + 1) + plane
+    unsigned nfill;       // fill blocks of this launch: fsplit * gy * planes
+    int fsplit, pb;       // fill blocks per (plane, band) row / passes per block
+    int zs;               // k_render_bwd_wave: the role's own gridDim.z (the layers behind it are fill blocks)
+    unsigned cp1_magic;   // FwdArgs::cp1_magic
+    unsigned row_magic;   // ceil(2^32 / (fsplit * gy)), 0 when that divisor is 1
+    unsigned fs_magic;    // ceil(2^32 / fsplit), likewise
+};
+
+__device__ __forceinline__ void prefill_block(const PreFill& f, unsigned e)
+{
+    if (e >= f.nfill) return;
+    const unsigned rows = (unsigned)(f.fsplit * f.gy);
+    const unsigned zr = f.row_magic ? __umulhi(e, f.row_magic) : e;        // (a magic of 0 stands for the divisor 1)
+    const unsigned rem = e - zr * rows;
+    const int band = (int)(f.fs_magic ? __umulhi(rem, f.fs_magic) : rem);
+    const int q = (int)rem - band * f.fsplit;
+    const int zid = f.zid0 + (int)zr;
+    const int v = (int)(((unsigned)zid * f.cp1_magic) >> 20);
+    const int plane = zid - v * (f.C + 1);
+    const size_t HW = (size_t)f.H * f.W;
+    const int Nb = min(TILE, f.H - band * TILE) * f.W;
+    float* out = (plane == f.C ? f.out_invdepth + (size_t)v * HW : f.out_color + ((size_t)v * f.C + plane) * HW) + (size_t)band * TILE * f.W;
+    const int shift = (int)((reinterpret_cast<uintptr_t>(out) >> 2) & 31u);   // passes cut on 128-byte lines of the address (fwd_fill_role)
+    fill_bare<4, true>(out, nullptr, nullptr, q * 1024 * f.pb + (int)threadIdx.x * 4 - shift, Nb, min(f.pb, 32));
+}

@@ -472,8 +472,18 @@ __global__ __launch_bounds__(256) void k_geom_bwd_binned(GeomBwdArgs a, ViewTan 
 // per-view joint gradients right after the backward -- xyz.grad = accumulated_grads.mean(dim=0), train.py:215-217 -- so a
 // caller that wants that mean does not pay another launch for 200 floats: thread t = (view t / P, Gaussian t % P); the views
 // of a Gaussian are summed in view order, then divided by V (the summation order of sks_loop_adam_step).
-__global__ __launch_bounds__(256) void k_geom_bwd_all(GeomBwdArgs a, ViewTan vt, int V, float* __restrict__ mean_out)
+// PF (empty, or one PreFill by value): the prefill role of sks_backward_prefill -- blocks 1 .. nfill zero planes of the next
+// forward's output set and leave before the barrier; block 0 is the geometry backward, as without the role.
+template <class... PF>
+__global__ __launch_bounds__(256) void k_geom_bwd_all(GeomBwdArgs a, ViewTan vt, int V, float* __restrict__ mean_out, PF... pf)
 {
+    static_assert(sizeof...(PF) <= 1, "at most one PreFill");
+    if constexpr (sizeof...(PF) == 1) {
+        if (blockIdx.x > 0) {   // (workgroup-uniform)
+            prefill_block((pf, ...), blockIdx.x - 1u);
+            return;
+        }
+    }
     const int t = threadIdx.x;
     const int v = t / a.P, idx = t - v * a.P;
     const bool live = v < V;

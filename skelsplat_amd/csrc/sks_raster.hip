@@ -146,26 +146,27 @@ inline int early_fill_planes(unsigned flags, int planes, size_t plane_bytes)
 
 inline unsigned magic32(unsigned d) { return (unsigned)(((1ull << 32) + d - 1) / d); }   // x / d == umulhi(x, magic32(d)) for x * d < 2^32 (d >= 2)
 
-// The geometry launch with the early-fill role (k_geom_fwd_fill) for the planes zid >= zid0.  The early blocks are always
+// The geometry launch with the early-fill role (k_geom_fwd_fill) for the planes zid0 <= zid < zid1 (zid1 = every plane of the call,
+// or the first plane a backward already zeroed: sks_forward_prefilled).  The early blocks are always
 // linear (pass-major) fill blocks, also where the main launch uses row-aligned ones: whole planes change hands, so the
 // two launches need not agree on how a band is cut.
 // early_fill_cut: the early region's fill blocks per (plane, band) row and passes per block; false where the kernel's block
 // index arithmetic would not be exact (a forced large E on very large images: the caller then keeps the one-launch layout).
-bool early_fill_cut(const FwdArgs& a_in, int V, int gy, int gplanes, int zid0, int& fsplit, int& pb)
+bool early_fill_cut(const FwdArgs& a_in, int V, int gy, int gplanes, int zid0, int zid1, int& fsplit, int& pb)
 {
     FwdArgs a = a_in;
     a.flags |= SKS_FILL_LINEAR;
     fill_geometry(a, true, false, fsplit, pb);
-    const long long rows = (long long)fsplit * gy, nfill = rows * ((a.C + 1) * V - zid0);
+    const long long rows = (long long)fsplit * gy, nfill = rows * (zid1 - zid0);
     return fsplit >= 1 && pb >= 1 && nfill * rows < (1ll << 32) && (long long)V * gplanes + nfill < (1ll << 31);
 }
 
-void launch_geom_fill(const FwdArgs& a, int V, int gy, int gplanes, int zid0, int fsplit, int pb, const ViewTan& vt,
+void launch_geom_fill(const FwdArgs& a, int V, int gy, int gplanes, int zid0, int zid1, int fsplit, int pb, const ViewTan& vt,
                       const float* viewmatrix, const float* projmatrix, const float* means3D, const float* opacities,
                       const float* scales, const float* rotations, const float* cov3D_precomp, float smod, int* radii,
                       hipStream_t st, ProfScope& prof)
 {
-    const long long rows = (long long)fsplit * gy, nfill = rows * ((a.C + 1) * V - zid0);
+    const long long rows = (long long)fsplit * gy, nfill = rows * (zid1 - zid0);
     const int ngeom = V * gplanes;
     const EarlyFill f{ a.out_color, a.out_invdepth, a.C, a.W, a.H, gy, gplanes, ngeom, zid0, fsplit, pb, a.cp1_magic,
                        rows > 1 ? magic32((unsigned)rows) : 0u, fsplit > 1 ? magic32((unsigned)fsplit) : 0u };   // (0: divisor 1)
@@ -246,9 +247,52 @@ inline void launch_bwd_loss(const BwdArgs& a, const ViewTan& vt, const ViewOff& 
     }
 }
 
+// ---- prefill: the small-path backward's two launches zero the last planes of the NEXT forward's output set ----
+// What sks_backward_prefill asks of backward_impl: the other set and the plane counts of the two launches.
+struct PrefillReq {
+    float* color;
+    float* invdepth;
+    int planes_wave, planes_geom;
+};
+// Passes (4 KB) per prefill block.  Its own knob: these blocks run at the backward's occupancy (4 workgroups per CU, not the
+// forward's 8), so fewer are resident and each carries more.  SKS_PREFILL_PB: tuning sweeps only.
+#ifndef SKS_PREFILL_PASSES
+#define SKS_PREFILL_PASSES 2   /* H36M step, 25 planes: 1 pass 59.2 us, 2: 55.1, 3: 55.2, 4: 56.1, 8: 56.1, 16: 56.5 (MEASUREMENTS.md "Prefill") */
+#endif
+inline int prefill_passes()
+{
+    static const int n = [] { const char* e = getenv("SKS_PREFILL_PB"); return (e && atoi(e) > 0) ? atoi(e) : SKS_PREFILL_PASSES; }();
+    return n > 32 ? 32 : n;
+}
+// 16-byte non-temporal stores on the wave-resident small path, or nothing
+inline bool prefill_possible(int P, int W, int H, unsigned flags)
+{
+    return P >= 1 && P <= 64 && P <= SKS_SMALL_P && !(flags & (SKS_FORCE_BINNED | SKS_NO_NT_STORES | SKS_DEBUG_SYNC | (1u << 20))) &&
+           (W % 4 == 0 || (W % 4 == 2 && H % 2 == 0));
+}
+// The role's arguments for the planes [zid0, zid0 + nz) of the set (color, invdepth); false where the kernel's index arithmetic
+// would not be exact or the grid would not fit (`extra` = blocks per unit the fill blocks are counted in: a blockIdx.z layer of
+// k_render_bwd_wave, or 1).
+bool prefill_cut(PreFill& f, float* color, float* invdepth, int V, int C, int W, int H, int zid0, int nz, long long per_unit, long long max_units)
+{
+    const int gy = (H + TILE - 1) / TILE;
+    // (null set: the rule asks -- it answers for the worst alignment a 16-byte aligned set can have, so that what it promises the call accepts)
+    const bool lines = color && invdepth && (((uintptr_t)color | (uintptr_t)invdepth) & 127u) == 0;
+    const int lead = (lines && (long long)H * W % 32 == 0 && TILE * W % 32 == 0) ? 0 : 31;   // (fill_geometry)
+    const int passes = (TILE * W + lead + 1023) / 1024;
+    const int pb = prefill_passes();
+    const int fsplit = (passes + pb - 1) / pb;
+    const long long rows = (long long)fsplit * gy, nfill = rows * nz;
+    if (zid0 < 0 || nz < 1 || zid0 + nz > (C + 1) * V || nfill * rows >= (1ll << 32) || (nfill + per_unit - 1) / per_unit > max_units) return false;
+    f = PreFill{ color, invdepth, C, W, H, gy, zid0, (unsigned)nfill, fsplit, pb, 0, ((1u << 20) + (unsigned)C) / (unsigned)(C + 1),
+                 rows > 1 ? magic32((unsigned)rows) : 0u, fsplit > 1 ? magic32((unsigned)fsplit) : 0u };
+    return true;
+}
+
+// pf: the prefill role's arguments (wave-resident variant only), or null
 template <int CG>
 void launch_bwd_small(const BwdArgs& a, const ViewTan& vt, const ViewOff& vo, int V, int gy, bool dfeat, hipStream_t st,
-                      const ProfScope& prof)
+                      const ProfScope& prof, const PreFill* pf = nullptr)
 {
     (void)gy;
     // slot index slowest: a (view, Gaussian) only has work for its first ceil(pixels / 256) slots, so the idle workgroups
@@ -256,6 +300,14 @@ void launch_bwd_small(const BwdArgs& a, const ViewTan& vt, const ViewOff& vo, in
     // wait for (the fused-loss kernel fits 3 workgroups per CU: 768 of H36M's 1 088 at once)
     if (a.P <= 64 && !(a.flags & (1u << 20))) {  // wave-resident variant (bit 20: force the LDS variant, tests)
         dim3 grid(a.P, V, bwd_wave_groups(V, a.P, a.flags));
+        if (pf) {
+            PreFill f = *pf;
+            f.zs = (int)grid.z;
+            grid.z += (unsigned)((f.nfill + (unsigned)(a.P * V) - 1) / (unsigned)(a.P * V));   // (<= 65535: prefill_cut)
+            if (dfeat) SKS_LAUNCH(prof, (k_render_bwd_wave<CG, true, false, false, false, PreFill>), grid, dim3(256), 0, st, a, vt, vo, f);
+            else SKS_LAUNCH(prof, (k_render_bwd_wave<CG, false, false, false, false, PreFill>), grid, dim3(256), 0, st, a, vt, vo, f);
+            return;
+        }
         if (dfeat) SKS_LAUNCH(prof, (k_render_bwd_wave<CG, true, false>), grid, dim3(256), 0, st, a, vt, vo);
         else SKS_LAUNCH(prof, (k_render_bwd_wave<CG, false, false>), grid, dim3(256), 0, st, a, vt, vo);
         return;
@@ -359,10 +411,11 @@ int forward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, con
                  const float* opacities, const float* scales, const float* rotations, const float* cov3D_precomp,
                  float scale_modifier, unsigned flags, float* out_color, float* out_invdepth, int* radii, void* geom,
                  void* binning, size_t bin_capacity, int* num_rendered_dev, float* final_T, uint32_t* n_contrib,
-                 void* stream, const FwdHook* hook)
+                 void* stream, const FwdHook* hook, int prefilled = 0)
 {
     if (int rc = check_common(V, P, C, W, H)) return rc;
     hipStream_t st = (hipStream_t)stream;
+    if (prefilled < 0 || prefilled > (C + 1) * V) return fail(-1, "prefilled_planes=%d out of range [0,%d]", prefilled, (C + 1) * V);
     if (!out_color || !out_invdepth) return fail(-2, "out_color / out_invdepth must be provided");
     if (((uintptr_t)out_color | (uintptr_t)out_invdepth) & 15u)
         return fail(-2, "out_color / out_invdepth must be 16-byte aligned (the planes are written with 16-byte stores)");
@@ -402,19 +455,30 @@ int forward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, con
     // output was written.  Not for sks_forward_backward (its geom_done event fires when the geometry records exist, not when
     // the early fill has drained), not with the debug planes, not with a synchronise between the stages.
     const int planes = (C + 1) * V;
+    // sks_forward_prefilled: the planes zid >= zp are zero already (the composite blocks still store their tiles there, as they
+    // do behind the early region).  Ignored -- everything is filled -- with the debug planes, SKS_DEBUG_SYNC, the one-call hook, off
+    // the small path, and where this launch is a kind-0 sample whose prefilling launches were not bracketed (the hook was enabled
+    // in between): a sample is the time in which EVERY byte of the output was written.
+    int pre = 0;
+    if (prefilled > 0 && small && !hook && !final_T && !n_contrib && !(flags & SKS_DEBUG_SYNC) &&
+        !(prof_next_forward_sampled() && !prof_has_parked(st)))
+        pre = prefilled;
+    const int zp = planes - pre;
     int early = 0;
-    if (small && !hook && g.cover && !final_T && !n_contrib && !(flags & (SKS_DEBUG_SYNC | SKS_NO_EARLY_FILL)))
+    if (small && !hook && g.cover && !final_T && !n_contrib && !(flags & (SKS_DEBUG_SYNC | SKS_NO_EARLY_FILL))) {
         early = early_fill_planes(flags, planes, HW * 4);
+        if (early > zp) early = zp;
+    }
     int efs = 0, epb = 0;
-    if (early > 0 && early_fill_cut(a, V, gy, gplanes, planes - early, efs, epb)) {
-        ProfScope prof(0, st, true);
-        launch_geom_fill(a, V, gy, gplanes, planes - early, efs, epb, vt, viewmatrix, projmatrix, means3D, opacities, scales, rotations,
+    if (early > 0 && early_fill_cut(a, V, gy, gplanes, zp - early, zp, efs, epb)) {
+        ProfScope prof(0, st, true, pre > 0);
+        launch_geom_fill(a, V, gy, gplanes, zp - early, zp, efs, epb, vt, viewmatrix, projmatrix, means3D, opacities, scales, rotations,
                          cov3D_precomp, scale_modifier, radii, st, prof);
         switch (cg) {
-            case 4: launch_fwd_small<4>(a, V, gy, planes - early, st, prof); break;
-            case 16: launch_fwd_small<16>(a, V, gy, planes - early, st, prof); break;
-            case 20: launch_fwd_small<20>(a, V, gy, planes - early, st, prof); break;
-            default: launch_fwd_small<32>(a, V, gy, planes - early, st, prof); break;
+            case 4: launch_fwd_small<4>(a, V, gy, zp - early, st, prof); break;
+            case 16: launch_fwd_small<16>(a, V, gy, zp - early, st, prof); break;
+            case 20: launch_fwd_small<20>(a, V, gy, zp - early, st, prof); break;
+            default: launch_fwd_small<32>(a, V, gy, zp - early, st, prof); break;
         }
         HIP_TRY(hipGetLastError());
         return 0;
@@ -436,12 +500,12 @@ int forward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, con
 
     if (small) {
         {
-            ProfScope prof(0, st, true);
+            ProfScope prof(0, st, true, pre > 0);
             switch (cg) {
-                case 4: launch_fwd_small<4>(a, V, gy, planes, st, prof); break;
-                case 16: launch_fwd_small<16>(a, V, gy, planes, st, prof); break;
-                case 20: launch_fwd_small<20>(a, V, gy, planes, st, prof); break;
-                default: launch_fwd_small<32>(a, V, gy, planes, st, prof); break;
+                case 4: launch_fwd_small<4>(a, V, gy, zp, st, prof); break;
+                case 16: launch_fwd_small<16>(a, V, gy, zp, st, prof); break;
+                case 20: launch_fwd_small<20>(a, V, gy, zp, st, prof); break;
+                default: launch_fwd_small<32>(a, V, gy, zp, st, prof); break;
             }
         }
         STAGE_CHECK("render(small)");
@@ -527,7 +591,7 @@ int backward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, co
                   const void* binning, size_t bin_capacity, const float* dL_dout_color, const float* dL_dout_invdepth,
                   void* accum, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dopacity, float* dL_dscales,
                   float* dL_drotations, float* dL_dcov3D, float* dL_dfeatures, float* dL_dmeans3D_mean, void* stream,
-                  unsigned phases, int group)
+                  unsigned phases, int group, const PrefillReq* pre = nullptr)
 {
     if (int rc = check_common(V, P, C, W, H)) return rc;
     if (P == 0) return 0;
@@ -548,13 +612,36 @@ int backward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, co
     int vg = V, ng = 1;
     if (!small) bin_groups(flags, V, vg, ng);
     if (group >= ng) return fail(-1, "view group %d of %d", group, ng);
+    // the geometry backward of all views in one workgroup (with the mean over the views): the launch that can carry planes_geom
+    const bool geom_all = dL_dmeans3D_mean && V * P <= 256 && small;
+    PreFill pfw{}, pfg{};
+    bool have_pfw = false, have_pfg = false;
+    if (pre && pre->planes_wave + pre->planes_geom > 0) {
+        // the call's last planes: the compositing backward's share first, the geometry backward's behind it -- all of them in the
+        // compositing launch where the geometry backward is not k_geom_bwd_all
+        const int planes = (C + 1) * V, n = pre->planes_wave + pre->planes_geom;
+        const int n_geom = geom_all ? pre->planes_geom : 0, nw = n - n_geom;
+        if (nw > 0) {
+            if (!prefill_cut(pfw, pre->color, pre->invdepth, V, C, W, H, planes - n, nw, (long long)P * V, 65535 - BWD_SPLITS))
+                return fail(-1, "sks_backward_prefill: %d planes of %dx%d do not fit the compositing backward's launch", nw, W, H);
+            have_pfw = true;
+        }
+        if (n_geom > 0) {
+            if (!prefill_cut(pfg, pre->color, pre->invdepth, V, C, W, H, planes - n_geom, n_geom, 1, (1ll << 31) - 2))
+                return fail(-1, "sks_backward_prefill: %d planes of %dx%d do not fit the geometry backward's launch", n_geom, W, H);
+            have_pfg = true;
+        }
+        // the next forward's kind-0 launch will be bracketed: so are the launches that write part of its output
+        if (prof_next_forward_sampled()) prof_park_begin(st);
+    }
     if ((phases & BWD_RENDER) && small) {
         ProfScope prof(1, st, true);
+        const PreFill* pf = have_pfw ? &pfw : nullptr;
         switch (cg) {
-            case 4: launch_bwd_small<4>(a, vt, vo, V, gy, dfeat, st, prof); break;
-            case 16: launch_bwd_small<16>(a, vt, vo, V, gy, dfeat, st, prof); break;
-            case 20: launch_bwd_small<20>(a, vt, vo, V, gy, dfeat, st, prof); break;
-            default: launch_bwd_small<32>(a, vt, vo, V, gy, dfeat, st, prof); break;
+            case 4: launch_bwd_small<4>(a, vt, vo, V, gy, dfeat, st, prof, pf); break;
+            case 16: launch_bwd_small<16>(a, vt, vo, V, gy, dfeat, st, prof, pf); break;
+            case 20: launch_bwd_small<20>(a, vt, vo, V, gy, dfeat, st, prof, pf); break;
+            default: launch_bwd_small<32>(a, vt, vo, V, gy, dfeat, st, prof, pf); break;
         }
         STAGE_CHECK("render-backward(small)");
     } else if (phases & BWD_RENDER) {
@@ -590,8 +677,9 @@ int backward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, co
         ga.cap = bin_capacity;
         ga.bin_hdr = b.hdr;
     }
-    if (dL_dmeans3D_mean && V * P <= 256 && small) {   // (the binned path's k_geom_bwd also re-arms the work cursors)
-        hipLaunchKernelGGL(k_geom_bwd_all, dim3(1), dim3(256), 0, st, ga, vt, V, dL_dmeans3D_mean);
+    if (geom_all) {   // (the binned path's k_geom_bwd also re-arms the work cursors)
+        if (have_pfg) hipLaunchKernelGGL((k_geom_bwd_all<PreFill>), dim3(1u + pfg.nfill), dim3(256), 0, st, ga, vt, V, dL_dmeans3D_mean, pfg);
+        else hipLaunchKernelGGL((k_geom_bwd_all<>), dim3(1), dim3(256), 0, st, ga, vt, V, dL_dmeans3D_mean);
     } else {
         if (small) hipLaunchKernelGGL(k_geom_bwd, dim3((P + 255) / 256, V), dim3(256), 0, st, ga, vt);
         else {
@@ -603,6 +691,7 @@ int backward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, co
         if (dL_dmeans3D_mean && (small || group < 0 || group == ng - 1))
             hipLaunchKernelGGL(k_mean_views, dim3((3 * P + 255) / 256), dim3(256), 0, st, V, P, dL_dmeans3D, dL_dmeans3D_mean);
     }
+    if (have_pfw || have_pfg) prof_park_end(st);
     STAGE_CHECK("geometry-backward");
     return 0;
 }
@@ -623,6 +712,90 @@ int sks_backward(int V, int P, int C, int W, int H, const float* viewmatrix, con
                          cov3D_precomp, scale_modifier, flags, radii, geom, binning, bin_capacity, dL_dout_color, dL_dout_invdepth, accum,
                          dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, dL_dfeatures, dL_dmeans3D_mean,
                          stream, BWD_RENDER | BWD_GEOM, -1);
+}
+
+int sks_forward_prefilled(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                          const float* tanfovx, const float* tanfovy, const float* means3D, const float* features,
+                          const float* opacities, const float* scales, const float* rotations, const float* cov3D_precomp,
+                          float scale_modifier, unsigned flags, float* out_color, float* out_invdepth, int* radii, void* geom,
+                          void* binning, size_t bin_capacity, int* num_rendered_dev, float* final_T, uint32_t* n_contrib,
+                          int prefilled_planes, void* stream)
+{
+    return forward_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, means3D, features, opacities, scales, rotations,
+                        cov3D_precomp, scale_modifier, flags, out_color, out_invdepth, radii, geom, binning, bin_capacity,
+                        num_rendered_dev, final_T, n_contrib, stream, nullptr, prefilled_planes);
+}
+
+int sks_backward_prefill(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                         const float* tanfovx, const float* tanfovy, const float* bg, const float* means3D,
+                         const float* features, const float* opacities, const float* scales, const float* rotations,
+                         const float* cov3D_precomp, float scale_modifier, unsigned flags, const int* radii, const void* geom,
+                         const void* binning, size_t bin_capacity, const float* dL_dout_color, const float* dL_dout_invdepth,
+                         void* accum, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dopacity, float* dL_dscales,
+                         float* dL_drotations, float* dL_dcov3D, float* dL_dfeatures, float* dL_dmeans3D_mean,
+                         float* next_color, float* next_invdepth, int planes_wave, int planes_geom, void* stream)
+{
+    if (int rc = check_common(V, P, C, W, H)) return rc;
+    if (planes_wave < 0 || planes_geom < 0 || (long long)planes_wave + planes_geom > (long long)(C + 1) * V)
+        return fail(-1, "sks_backward_prefill: planes_wave=%d planes_geom=%d out of range (the call has %d planes)", planes_wave, planes_geom, (C + 1) * V);
+    const PrefillReq req{ next_color, next_invdepth, planes_wave, planes_geom };
+    if (planes_wave + planes_geom > 0) {
+        // (SKS_NO_NT_STORES is the store kind of the FORWARD's fill role: it has no bearing on these stores, and a backward's recorded
+        // flags may carry it from a forward that has since been re-tuned)
+        if (!prefill_possible(P, W, H, flags & ~SKS_NO_NT_STORES))
+            return fail(-1, "sks_backward_prefill: no prefill for this call (wave-resident small path with 16-byte non-temporal stores only: "
+                            "1 <= P <= 64, W %% 4 == 0 or W %% 4 == 2 with an even H, no SKS_NO_NT_STORES / SKS_DEBUG_SYNC / SKS_FORCE_BINNED)");
+        if (!next_color || !next_invdepth) return fail(-2, "sks_backward_prefill: next_color / next_invdepth must be provided");
+        if (((uintptr_t)next_color | (uintptr_t)next_invdepth) & 15u) return fail(-2, "next_color / next_invdepth must be 16-byte aligned");
+    }
+    return backward_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, bg, means3D, features, opacities, scales, rotations,
+                         cov3D_precomp, scale_modifier, flags, radii, geom, binning, bin_capacity, dL_dout_color, dL_dout_invdepth, accum,
+                         dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, dL_dfeatures, dL_dmeans3D_mean,
+                         stream, BWD_RENDER | BWD_GEOM, -1, planes_wave + planes_geom > 0 ? &req : nullptr);
+}
+
+// The rule: how many of the call's last planes the small-path backward's two launches should zero for the next forward.  A function
+// of the call, like early_fill_planes: BYTES per launch in whole planes, because what the bytes hide under is the launches' latency,
+// not the image.  Together with the early region at most half of the call's planes.
+// It answers 0 / 0 outside what was measured: the constants were swept on the H36M step alone -- 68 (view, Gaussian) pairs, one
+// round of 1088 workgroups of the compositing backward at 4 per CU (the CG <= 20 instantiations without the feature gradient),
+// 16-byte stores on W % 4 == 0 -- and beside a store stream the backward can lengthen by more than the forward shortens.  So:
+// V * P within a quarter of 68 either way (51 .. 85) at 16 workgroups per pair, C <= 20, W % 4 == 0 (not the pair-masked
+// W % 4 == 2 images: 1002 wide); a caller that also asks for the feature gradient (the 1-wave-per-SIMD instantiations) should
+// not prefill either -- the rule cannot see that, rasterizer.Workspace does.  sks_backward_prefill itself carries any count on
+// any shape it can store 16 bytes on: whoever measures a case outside this widens the rule.
+// Constants from the interleaved sweep on the H36M two-call step (planes of 4 MB; MEASUREMENTS.md "Prefill"; us per step):
+// compositing launch alone 0 / 6 / 12 / 18 planes: 62.0 / 60.4 / 58.2 / 57.0; geometry launch alone 0 / 4 / 7: 62.0 / 61.2 / 60.4;
+// both: (12, 4) 57.2, (12, 7) 56.3, (18, 7) 56.1, (20, 7) 56.8; and at 2 passes per block (12, 7) 55.0, (14, 7) 54.9, (16, 7) 55.3,
+// (18, 7) 55.5, (20, 7) 55.8, (18, 5) 56.0, (18, 9) 55.1 -- 56 MB and 28 MB are the smallest sizes beyond which nothing is gained.
+#ifndef SKS_PREFILL_WAVE_BYTES
+#define SKS_PREFILL_WAVE_BYTES 56000000u
+#endif
+#ifndef SKS_PREFILL_GEOM_BYTES
+#define SKS_PREFILL_GEOM_BYTES 28000000u
+#endif
+int sks_prefill_planes(int V, int P, int C, int W, int H, unsigned flags, int* planes_wave, int* planes_geom)
+{
+    if (int rc = check_common(V, P, C, W, H)) return rc;
+    if (!planes_wave || !planes_geom) return fail(-2, "sks_prefill_planes: planes_wave / planes_geom must be provided");
+    *planes_wave = *planes_geom = 0;
+    if (!prefill_possible(P, W, H, flags) || !cover_enabled(P, W, H)) return 0;
+    const int planes = (C + 1) * V;
+    const size_t plane_bytes = (size_t)H * W * 4;
+    const int early = (flags & SKS_NO_EARLY_FILL) ? 0 : early_fill_planes(flags, planes, plane_bytes);
+    int room = planes / 2 - early;
+    if (room <= 0) return 0;
+    if (W % 4 != 0 || C > 20 || V * P < 51 || V * P > 85 || bwd_wave_groups(V, P, flags) != 16) return 0;   // (not measured: see above)
+    long long nw = ((long long)SKS_PREFILL_WAVE_BYTES + plane_bytes / 2) / plane_bytes;
+    long long ng = ((long long)SKS_PREFILL_GEOM_BYTES + plane_bytes / 2) / plane_bytes;
+    if (nw > room) nw = room;
+    if (ng > room - nw) ng = room - nw;
+    PreFill f;   // (what the launches could not index is not promised)
+    if (nw > 0 && !prefill_cut(f, nullptr, nullptr, V, C, W, H, planes - (int)(nw + ng), (int)nw, (long long)P * V, 65535 - BWD_SPLITS)) nw = 0;
+    if (ng > 0 && !prefill_cut(f, nullptr, nullptr, V, C, W, H, planes - (int)ng, (int)ng, 1, (1ll << 31) - 2)) ng = 0;
+    *planes_wave = (int)nw;
+    *planes_geom = (int)ng;
+    return 0;
 }
 
 int sks_forward_backward(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
@@ -1007,6 +1180,7 @@ int sks_prof_enable(int on)
     tl_prof->skip = (on >> 16) & 3;
     tl_prof->recorded = (on >> 18) & 1;
     tl_prof->seen[0] = tl_prof->seen[1] = 0;
+    tl_prof->parked = false;
     return 0;
 }
 
@@ -1024,9 +1198,8 @@ int sks_prof_read(int kind, double* total_ms, long long* launches)
     ProfKind& p = tl_prof->kind[kind];
     double tot = 0;
     for (int i = 0; i < p.n; i++) {
-        HIP_TRY(hipEventSynchronize(p.e[i]));
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, p.b[i], p.e[i]));
+        HIP_TRY(prof_elapsed(p, i, &ms));
         tot += ms;
     }
     *total_ms = tot;
@@ -1043,8 +1216,7 @@ int sks_prof_read_quantiles(int kind, double* q_ms /* 3: p10, p50, p90 */, doubl
     static thread_local float t[PROF_MAX];
     double tot = 0;
     for (int i = 0; i < p.n; i++) {
-        HIP_TRY(hipEventSynchronize(p.e[i]));
-        HIP_TRY(hipEventElapsedTime(&t[i], p.b[i], p.e[i]));
+        HIP_TRY(prof_elapsed(p, i, &t[i]));
         tot += t[i];
     }
     const int n = p.n;

@@ -49,15 +49,41 @@ class Workspace:
     """Reusable outputs and scratch of forward_views / backward_views.  A caller that runs the same shapes every step
     (a training loop: train.py:130-222 renders the same cameras 500 times per frame) passes the same Workspace to every
     call and the calls allocate nothing: a dozen caching-allocator round trips per step are ~20 us of host time next
-    to ~78 us of kernels on the H36M step.  What the calls return are the workspace's tensors: the NEXT call with the same
-    shapes overwrites them (the reference's own outputs are fresh tensors per call; callers that keep results across
-    calls simply do not pass a workspace).  Every kernel writes every element, so nothing is ever cleared."""
+    to ~78 us of kernels on the H36M step.  What the calls return are the workspace's tensors: the NEXT call of the same kind
+    with the same shapes overwrites them (the reference's own outputs are fresh tensors per call; callers that keep results
+    across calls simply do not pass a workspace).
 
-    def __init__(self):
+    What is relied on instead of clearing.  Every element of the scratch, the gradients and the radii is written by every call that
+    returns them.  The image (colour, inverse depth) of a recorded small-path forward whose set is at most 1 GiB lives in TWO sets
+    that the forwards alternate between; every element of the set a forward returns is written either by that forward or, for
+    its LAST planes, by the replayed backward_views in front of it, whose two latency-bound launches store zeros there while
+    HBM would otherwise idle (sks_backward_prefill / sks_forward_prefilled, include/skelsplat_hip.h).  The invariant: `cur` is the
+    set the last forward rendered; a replayed backward_views zeroes the other set's last planes and notes how many and on which
+    stream; nothing else writes the other set; the next replayed forward_views on that stream renders into it with those planes
+    taken as zero, the sets swap and the note is gone.  A forward without a valid note (the first, one on another stream, one
+    after a call that took the validating path, under stream capture) renders into `cur` and fills everything, and
+    forward_backward_views always does.  So the result tuples of successive forwards alternate between two (color, invdepth)
+    pairs -- with the same radii and the same ForwardState object -- and a result stays valid until the next call of the same kind,
+    as ever.  New with the second set: writing into a result that is already dead by that rule can corrupt a LATER image (the dead
+    set may hold planes zeroed for the next forward).  The second set is allocated by the first backward that prefills
+    (H36M: 2 x 288 MB); larger images (all 31 Panoptic views: 5.1 GB) and the binned path keep one set.  A call under stream
+    capture neither prefills nor takes prefilled planes, and from then on the workspace stops for good: a graph replayed later
+    renders into the pointers it captured, behind this object's back.
+
+    prefill: None = the library's rule decides how many planes ride in the backward (sks_prefill_planes), 0 = off (one set,
+    the behaviour before the second set existed), (n_wave, n_geom) = forced plane counts for the compositing / geometry
+    backward's launch (tests and sweeps)."""
+
+    def __init__(self, prefill=None):
         self._t = {}
         self._plans = {}     # "fwd" / "bwd" -> the last call's record (_FwdRecord / _BwdRecord)
         self._aux = {}
         self._pending_join = None     # device whose second stream still holds a forward_backward_views(join=False) backward
+        if prefill is not None and prefill != 0:
+            prefill = (int(prefill[0]), int(prefill[1]))
+        self._prefill = prefill
+        self._pf = None               # the two output sets of the recorded forward (_Prefill), or None: one set
+        self._pf_off = prefill == 0   # no prefill (asked for, or a call was captured into a graph)
 
     def aux_stream(self, dev_index):
         """The second stream forward_backward_views runs the backward on (created on first use, one per device)."""
@@ -120,6 +146,27 @@ class Workspace:
         return t
 
 
+class _Prefill:
+    """The two output sets of a Workspace's recorded forward (see Workspace).  sets[i] = (color, invdepth) (sets[1] None until the
+    first prefilling backward), results[i] = what a forward that rendered set i returns, cur = the set the last forward rendered,
+    note = None or (planes, stream): the other set's last `planes` planes are zero in `stream` order.  fargs = the live block of
+    sks_forward_prefilled (the record's block with `prefilled_planes` in front of the stream; the flags word is copied from the
+    record on every call, bench.py and Workspace.tune write it there), bargs = that of sks_backward_prefill for record `bplan`."""
+    __slots__ = ("shape", "sets", "results", "cur", "note", "fargs", "bplan", "bargs", "rule")
+
+    def __init__(self, shape, color, invdepth, radii, st, args):
+        self.shape = shape      # (V, P, C, W, H)
+        self.sets = [(color, invdepth), None]
+        self.results = [(color, invdepth, radii, st), None]
+        self.cur, self.note = 0, None
+        self.fargs = list(args[:-1]) + [0, None]
+        self.bplan = self.bargs = None
+        self.rule = {}          # forward flags -> (planes_wave, planes_geom)
+
+
+_PREFILL_MAX_SET_BYTES = 1 << 30
+
+
 def _sig(t):
     """What identifies a tensor argument of a recorded call: None (not provided), (pointer, shape) of a contiguous fp32
     ROCm tensor, or False = "take the validating path" (anything else)."""
@@ -146,6 +193,7 @@ _Block = namedtuple("_Block", "args dev_index dev shape")
 _F_V, _F_FLAGS, _F_COLOR, _F_INVDEPTH, _F_RADII, _F_GEOM, _F_NUM_RENDERED = (
     _lib.FWD[n] for n in ("V", "flags", "out_color", "out_invdepth", "radii", "geom", "num_rendered_dev"))
 _B_RADII, _B_GEOM, _B_DL_COLOR, _B_DL_INVDEPTH = (_lib.BWD[n] for n in ("radii", "geom", "dL_dout_color", "dL_dout_invdepth"))
+_B_DFEAT = _lib.BWD["dL_dfeatures"]
 _GRAD_SLOTS = tuple((k, _lib.BWD[n]) for k, n in (      # gradient dictionary key -> sks_backward's slot
     ("means3D", "dL_dmeans3D"), ("means2D", "dL_dmeans2D"), ("opacities", "dL_dopacity"), ("scales", "dL_dscales"),
     ("rotations", "dL_drotations"), ("cov3D", "dL_dcov3D"), ("features", "dL_dfeatures")))
@@ -211,6 +259,14 @@ def forward_views(views: ViewBatch, means3D, features, opacities, scales, rotati
     if key is not None and workspace is not None:
         plan = workspace._plans.get("fwd")
         if plan is not None and plan.key == key:
+            pf = workspace._pf
+            if pf is not None:      # (small path, two output sets)
+                rc = _forward_two_sets(lib, workspace, pf, plan)
+                if rc != 0:
+                    del workspace._plans["fwd"]
+                    workspace._pf = None
+                _lib.check(rc, "sks_forward")
+                return pf.results[pf.cur]
             ticket = _replay_ticket(workspace, plan)
             rc = _replay(lib.sks_forward, plan.args, plan.dev_index)
             if rc != 0:
@@ -219,6 +275,8 @@ def forward_views(views: ViewBatch, means3D, features, opacities, scales, rotati
             if ticket is None or (_arena.finish(ticket) or 0) <= ticket.cap:      # (a lazy ticket is looked at by a later call)
                 return plan.result
             del workspace._plans["fwd"]      # the synchronous check: the arena overflowed, the validating path below grows it and redoes
+    if workspace is not None and workspace._pf is not None:
+        workspace._pf.note = None        # the validating path writes the first set whatever `cur` is: no promise about either survives
     if views.mixed:
         raise RuntimeError("the dense forward writes one (V,C,H,W) tensor: all views of the batch must share the image size")
     if means3D is None or means3D.dim() != 2 or means3D.shape[1] != 3:
@@ -298,7 +356,75 @@ def forward_views(views: ViewBatch, means3D, features, opacities, scales, rotati
         # (the binning buffer needs no clearing between calls: every counter is written before it is read)
         arena = (ticket.key, cap, True if check_capacity is True else "lazy") if binned and check_capacity else None
         workspace._plans["fwd"] = _FwdRecord(key, (views, keep), args, dev.index, (color, invdepth, radii, st), arena)
+        workspace._pf = None
+        if not binned and P and not workspace._pf_off and _lib.HAS_PREFILL and 4 * (C + 1) * V * H * W <= _PREFILL_MAX_SET_BYTES:
+            workspace._pf = _Prefill((V, P, C, W, H), color, invdepth, radii, st, args)
+    else:      # (a captured call: the graph holds these pointers from now on)
+        workspace._pf_off = True
     return color, invdepth, radii, st
+
+
+def _forward_two_sets(lib, workspace, pf, plan):
+    """A replayed small-path forward of a workspace with two output sets: into the other set with its noted planes taken as zero
+    (sks_forward_prefilled; the sets swap), or into `cur` with everything filled (sks_forward).  The record's block keeps pointing
+    at `cur`: forward_backward_views, Workspace.tune and bench.py read it."""
+    note, pf.note = pf.note, None
+    args = plan.args
+    if note is not None:
+        if workspace._pf_off or torch.cuda.is_current_stream_capturing():
+            workspace._pf_off = True
+        elif note[1] == torch._C._cuda_getCurrentRawStream(plan.dev_index):
+            other = 1 - pf.cur
+            color, invdepth = pf.sets[other]
+            fargs = pf.fargs
+            fargs[_F_FLAGS], fargs[_F_COLOR], fargs[_F_INVDEPTH], fargs[-2] = args[_F_FLAGS], color.data_ptr(), invdepth.data_ptr(), note[0]
+            rc = _replay(lib.sks_forward_prefilled, fargs, plan.dev_index)
+            if rc == 0:
+                pf.cur = other
+                args[_F_COLOR], args[_F_INVDEPTH] = fargs[_F_COLOR], fargs[_F_INVDEPTH]
+            return rc
+    elif not workspace._pf_off and torch.cuda.is_current_stream_capturing():
+        workspace._pf_off = True
+    return _replay(lib.sks_forward, args, plan.dev_index)
+
+
+def _backward_prefill(lib, workspace, plan):
+    """A replayed backward of the workspace's recorded small-path forward: sks_backward_prefill zeroing the last planes of the set
+    the next forward renders into (and the note for that forward), or None where this call does not prefill."""
+    pf = workspace._pf
+    if pf is None or workspace._pf_off or plan.key[0] != id(pf.results[0][3]):
+        return None
+    if torch.cuda.is_current_stream_capturing():
+        workspace._pf_off, pf.note = True, None
+        return None
+    fplan = workspace._plans.get("fwd")
+    if fplan is None:
+        return None
+    fflags = fplan.args[_F_FLAGS]
+    n = pf.rule.get(fflags)
+    if n is None:
+        V, P, C, W, H = pf.shape
+        # (the counts are the FORWARD's: its live flags hold the store kind and the early region the rule leaves room for)
+        n = pf.rule[fflags] = _lib.prefill_planes(V, P, C, W, H, fflags) if workspace._prefill is None else workspace._prefill
+    if workspace._prefill is None and plan.args[_B_DFEAT] is not None:
+        return None      # (the feature-gradient instantiations run 1-3 waves per SIMD: not what the rule's constants were measured on)
+    if n[0] + n[1] == 0:
+        return None
+    if pf.sets[1] is None:      # the first prefilling backward allocates the second set
+        color, invdepth, radii, st = pf.results[0]
+        c2 = workspace.get(("fwd", "color2"), color.shape, color.dtype, color.device)
+        i2 = workspace.get(("fwd", "invdepth2"), invdepth.shape, invdepth.dtype, invdepth.device)
+        pf.sets[1], pf.results[1] = (c2, i2), (c2, i2, radii, st)
+    if pf.bplan is not plan:
+        pf.bplan, pf.bargs = plan, list(plan.args[:-1]) + [None, None, 0, 0, None]
+    color, invdepth = pf.sets[1 - pf.cur]
+    bargs = pf.bargs
+    bargs[-5], bargs[-4], bargs[-3], bargs[-2] = color.data_ptr(), invdepth.data_ptr(), n[0], n[1]
+    pf.note = None
+    rc = _replay(lib.sks_backward_prefill, bargs, plan.dev_index)
+    if rc == 0:
+        pf.note = (n[0] + n[1], bargs[-1])
+    return rc
 
 
 def _replay_ticket(workspace, plan):
@@ -436,7 +562,9 @@ def backward_views(st: ForwardState, means3D, features, opacities, scales, rotat
                        want_dfeatures, tune_flags, want_mean, out_means3D, torch._C._cuda_getCurrentRawStream(st.geom.device.index))
         plan = workspace._plans.get("bwd")
         if plan is not None and plan.key == key:
-            rc = _replay(lib.sks_backward, plan.args, plan.dev_index)
+            rc = _backward_prefill(lib, workspace, plan)
+            if rc is None:
+                rc = _replay(lib.sks_backward, plan.args, plan.dev_index)
             if rc != 0:
                 reset_scratch()
                 del workspace._plans["bwd"]
@@ -537,7 +665,10 @@ def forward_backward_views(views: ViewBatch, means3D, features, opacities, scale
                 if not join and not overlap:     # (the gradients were produced on the current stream: aux must see them)
                     aux.wait_stream(torch.cuda.current_stream(dev_index))
                 if ticket is None or (_arena.finish(ticket) or 0) <= ticket.cap:
-                    return fplan.result + (bplan.result,)
+                    # (two output sets: the record's block points at `cur`, the set this call rendered; the other set and a note
+                    # about it are untouched)
+                    pf = workspace._pf
+                    return (fplan.result if pf is None else pf.results[pf.cur]) + (bplan.result,)
                 del workspace._plans["fwd"]     # the arena overflowed (synchronous check): the two calls below grow it and redo the step
                 workspace.settle()
     out = forward_views(views, means3D, features, opacities, scales, rotations, cov3D_precomp, scale_modifier, antialiasing, clamp01,
