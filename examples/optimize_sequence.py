@@ -3,7 +3,7 @@
 other, train.py:74-99) -- but many frames per launch: noisy 2D detections of N frames -> DLT initial guesses -> 500
 iterations of the multi-view loop for every frame (loop.FramePipeline) -> MPJPE per frame.
 python examples/optimize_sequence.py [--frames 64] [--per-launch 16] [--streams 2] [--iters 500] [--init host|device|fuse] [--rigs R]
-    [--report]
+    [--report] [--reject-px PX] [--corrupt K]
 --rigs R: the frames cycle through R jittered ring rigs (SyntheticScene seeds 0 .. R-1), as a dataset whose scenes bring their own
 cameras does; one rigs.RigBank holds them on the device and every batch names its frames' rigs (rig_ids).
 --init host (default): the DLT runs on the host, frame by frame, and its points are uploaded; --init device: the detections
@@ -12,6 +12,10 @@ reference's "metrabs" guess instead of the DLT -- synthetic monocular 3D predict
 noise per view) go to the device once with the detections, and every batch starts from their reprojection-error-weighted mean
 (initial_guess.fuse_predictions through optimize_sequence(None, ..., poses_3d=...)).  The timed region runs from the detections
 (and predictions) to the joints every way.
+--corrupt K: K random (view, joint) detections of every frame are moved by 80-300 px, as an occluded or mis-detected joint is.
+--reject-px PX (with --init device): every batch's triangulation first rejects outlier detections by two-view consensus on the
+device (pipe.set_outlier_rejection(PX), then optimize_sequence(None, ...)); the initial error is printed with and without the rejection, and how many
+detections were rejected.  The heat-maps still draw every detection: the final error shows what the outliers left in them cost.
 --report: the synthetic ground truth goes to the device once and the loops report while they run (report_steps, save_iterations;
 skelsplat_amd/report.py): the mean absolute / root-relative error over the sequence after 0, 1, 5, 25 and the last optimiser
 step -- the reference's convergence curve (train.py:184-213) --, the error at the snapshot of the middle iteration, and
@@ -44,6 +48,8 @@ def main():
     ap.add_argument("--init", choices=("host", "device", "fuse"), default="host")
     ap.add_argument("--rigs", type=int, default=1)
     ap.add_argument("--report", action="store_true")
+    ap.add_argument("--reject-px", type=float, default=None)
+    ap.add_argument("--corrupt", type=int, default=0)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     sc = SyntheticScene(args.dataset, n_views=args.views, seed=0, device=dev)
@@ -55,6 +61,12 @@ def main():
                    for f in range(args.frames)])
     p2d = np.stack([np.stack([project_points(c, gt[f]) + rng.normal(0, 3.0, (sc.n_points, 2)) for c in rigs[rig_of[f]]])
                     for f in range(args.frames)]).astype(np.float32)
+    for f in range(args.frames if args.corrupt else 0):
+        for k in rng.choice(args.views * sc.n_points, size=args.corrupt, replace=False):
+            r, th = rng.uniform(80.0, 300.0), rng.uniform(0.0, 2.0 * np.pi)
+            p2d[f, k // sc.n_points, k % sc.n_points] += (r * np.cos(th), r * np.sin(th))
+    if args.reject_px is not None and args.init != "device":
+        ap.error("--reject-px rejects while triangulating on the device: use it with --init device")
     Pm = [triangulation.projection_matrices(rig) for rig in rigs]
 
     def host_init():
@@ -75,6 +87,7 @@ def main():
         ids = {}
     if args.init == "device":
         p2d_dev = torch.as_tensor(p2d, device=dev)
+        pipe.set_outlier_rejection(args.reject_px)        # (None: off)
         run = lambda: pipe.optimize_sequence(None, p2d_dev, iterations=args.iters, return_initial=True, **ids)
     elif args.init == "fuse":
         sigma = np.linspace(20.0, 50.0, args.views)[:, None, None]
@@ -107,6 +120,13 @@ def main():
           f"({args.frames / dt:.0f} frames/s, {args.per_launch} frames per launch on {args.streams} streams, {args.rigs} rig(s)); "
           f"mean MPJPE {e0:.2f} mm ({'fused predictions on the device' if args.init == 'fuse' else f'DLT on the {args.init}'}) "
           f"-> {e1:.2f} mm")
+    if args.reject_px is not None:
+        plain = host_init()
+        ep = np.mean([io.mpjpe(plain[f], gt[f]) for f in range(args.frames)])
+        rejected = int((~pipe.inliers).sum())
+        fallbacks = int((pipe.n_consensus < 3).sum())
+        print(f"initial joints, {args.corrupt} corrupted detections per frame: mean MPJPE {ep:.2f} mm from all views -> {e0:.2f} mm "
+              f"with reject_px {args.reject_px:g} ({rejected} detections rejected, {fallbacks} joints without a consensus of 3)")
     if args.report:
         from skelsplat_amd.report import evaluate_sequence, pose_errors
         r = pipe.report

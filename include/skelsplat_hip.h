@@ -330,6 +330,25 @@ int sks_triangulate(int N, int V, int J, const double* proj, size_t rig_stride, 
                     const double* poses_2d_f64, const unsigned char* valid, float* xyz, double* xyzw, int* n_used,
                     void* stream);
 
+/* sks_triangulate with outlier rejection: exhaustive two-view consensus (the deterministic form of RANSAC) in front of the
+ * same DLT, two launches on `stream`, nothing synchronises, no atomics, no scratch.  Added to sks_version 14: the number did
+ * not move (a caller that must know looks the symbol up).  Per (frame, joint), in float64, with K = the views kept by `valid`
+ * (all when NULL):  |K| < 2: no solution, NaN, inliers = K, n_consensus = |K|.  |K| == 2: nothing can be tested, the DLT of the
+ * two, inliers = K, n_consensus = 2.  |K| >= 3: every pair a < b of K, in lexicographic order, is a hypothesis X_ab = the DLT
+ * of the four rows of views a and b, normalised to w = 1; view v of K is its inlier iff, with u = P_v X_ab, u[2] > 0 and
+ * e_v = hypot(u[0] / u[2] - x_v, u[1] / u[2] - y_v) <= reject_px (comparisons with NaN are false: a NaN or inf detection is
+ * never an inlier and a hypothesis built on one has none).  The winner has the most inliers; ties go to the smallest sum of the
+ * inliers' e_v (added in ascending view order), then to the first pair.  inliers = the winner's set if it has at least
+ * min_inliers views, else K (no consensus: the result of sks_triangulate); n_consensus = the winner's count in both cases, so
+ * n_consensus < min_inliers marks the fallback.  The joint is then the DLT over `inliers` by k_triangulate itself, bit for bit
+ * sks_triangulate(valid = inliers): one refit, no second inlier pass, no re-weighting; n_used = the views in `inliers`.
+ * Arguments and refusals of sks_triangulate, and: reject_px finite and > 0 (pixels), 2 <= min_inliers <= SKS_MAX_VIEWS,
+ * inliers (N,V,J) bytes REQUIRED (the refit reads it; it may not alias `valid`), n_consensus (N,J) optional.  A joint's outputs
+ * depend on V and its own inputs only, never on N, on its place in the batch or on the stream. */
+int sks_triangulate_robust(int N, int V, int J, const double* proj, size_t rig_stride, const float* poses_2d,
+                           const double* poses_2d_f64, const unsigned char* valid, double reject_px, int min_inliers,
+                           unsigned char* inliers, int* n_consensus, float* xyz, double* xyzw, int* n_used, void* stream);
+
 /* Initial joints of N frames as the reprojection-error-weighted mean of the V views' monocular 3D predictions, one launch
  * (reference: compute_weighted_average_pose, dataset_tools/h36m/compute_initial_guess.py:23-116 and dataset_tools/panoptic/
  * compute_initial_guess_panoptic.py:23-117 -- the configs' initial_guess "metrabs" / "metrabs_occ_3").  Per (frame, joint), with

@@ -19,13 +19,17 @@ _BG_CACHE = {}        # _bg_channels
 def _accum(device, stream, V, P, C):
     """Backward partial-sum scratch (uninitialised is fine): one buffer per (device, stream, shape)."""
     key = (device.index, stream, V, P, C)
-    buf = _accum_cache.get(key)
+    # While a hipGraph is being captured the current stream is torch's capture stream, the same handle for every capture --
+    # and a handle that torch's pool of streams hands out again to eager code.  A cached buffer under that handle would be
+    # baked into every graph captured with this shape, and graphs replayed side by side on different streams (FramePipeline)
+    # would then share their partial sums.  So a capture never takes a buffer from the cache and never leaves one there: its
+    # buffer comes from the graph's private pool, which keeps it alive for its own replays.
+    capturing = torch.cuda.is_current_stream_capturing()
+    buf = None if capturing else _accum_cache.get(key)
     if buf is None:
         _, _, nbytes = _lib.scratch_bytes(V, max(P, 1), C, 16, 16)
         buf = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
-        # a buffer allocated while a hipGraph is being captured belongs to that graph's private pool: the graph keeps it
-        # alive for its own replays, but it must not be handed to other graphs or to eager code on a recycled stream handle
-        if not torch.cuda.is_current_stream_capturing():
+        if not capturing:
             _accum_cache[key] = buf
     return buf
 

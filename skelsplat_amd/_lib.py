@@ -153,6 +153,7 @@ SIGNATURES = {
     "sks_loop_shard_floats": (_sz, [_i, _i, _i]),
     "sks_adam_multi": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp]),
     "sks_triangulate": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sks_triangulate_robust": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sks_fuse_predictions": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     **{name: (_i, [ct for _, ct in params]) for name, params in {**STEP_PARAMS, **DV_PARAMS}.items()},
     "sks_pose_errors": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -114,6 +114,14 @@ class _GroupLoop:
     def _after_replay(self):
         pass
 
+    def set_outlier_rejection(self, reject_px=None, min_inliers=3):
+        """From now on new_scene / new_scenes / optimize_sequence with `points=None` (and without `poses_3d`) reject outlier
+        detections while they triangulate the initial joints: exhaustive two-view consensus within `reject_px` pixels, at least
+        `min_inliers` (2 .. 64) views for a consensus (triangulation.triangulate_sequence's `reject_px`, `min_inliers`).  While
+        it is on, explicit points or `poses_3d` are refused; `reject_px=None` switches it off.  Returns the loop."""
+        self._reject = _rejection(reject_px, min_inliers)
+        return self
+
     def _enqueue(self, iterations, groups_per_graph, graphs=True):
         """run() without its final synchronisation (FramePipeline drives several loops with it).  With use_graph, while every group
         is the same one (all views, acc_steps iterations), G = `groups_per_graph` of them are ONE hipGraph: an eager group warms
@@ -195,6 +203,8 @@ class MultiViewLoop(_GroupLoop):
         # K [R|t] of all V views, float64 on the device: new_scene(points=None) triangulates the initial joints with them
         from .triangulation import device_projection_matrices
         self._proj = device_projection_matrices(cameras, dev)
+        self._reject = None                         # set_outlier_rejection's (reject_px, min_inliers)
+        self.inliers = self.n_consensus = None      # new_scene(points=None) with rejection: (V,J) bool, (J,) int32, allocated once
         P = gaussians._xyz.shape[0]
         self.P = P
         self._init_heatmaps(heatmaps)
@@ -389,9 +399,14 @@ class MultiViewLoop(_GroupLoop):
         triangulation and starts as NaN.
         `poses_3d` (V,J,3), with `points=None`: the initial joints are instead the reprojection-error-weighted mean of the
         views' 3D predictions (initial_guess.fuse_predictions, the reference's "metrabs" guess), under the same conditions; a
-        joint whose views are all dropped starts as NaN.  Together with explicit `points` it is refused."""
+        joint whose views are all dropped starts as NaN.  Together with explicit `points` it is refused.
+        After `set_outlier_rejection(reject_px, min_inliers)` the triangulation first rejects outlier detections by two-view
+        consensus (triangulate_sequence's `reject_px`); the views each joint was solved from are then in `self.inliers` (V,J)
+        bool, the consensus counts in `self.n_consensus` (J,).  It acts with `points=None` and without `poses_3d` only:
+        beside either the call is refused.  The heat-maps are not changed: a rejected detection still draws its plane."""
         from .heatmaps import generate_heatmaps
         gm = self.gm
+        reject_px, min_inliers = _checked_reject(self._reject, points, poses_3d, "new_scene")
         if points is not None:
             if poses_3d is not None:
                 raise ValueError("new_scene: poses_3d are fused into the initial joints when points is None; give one of the two")
@@ -436,7 +451,12 @@ class MultiViewLoop(_GroupLoop):
                         raise ValueError(f"poses_3d must be (V,J,3) = {(self.V, self.P, 3)}, got {tuple(p3d.shape)}")
                     gm.reset_from_points(fuse_predictions(self._proj, p3d, p2d, valid=None if drop is None else ~drop))
                 else:
-                    gm.reset_from_points(triangulate_sequence(self._proj, p2d, valid=None if drop is None else ~drop))
+                    if reject_px is not None and self.inliers is None:
+                        self.inliers = torch.zeros((self.V, self.P), dtype=torch.bool, device=self.device)
+                        self.n_consensus = torch.zeros((self.P,), dtype=torch.int32, device=self.device)
+                    gm.reset_from_points(triangulate_sequence(
+                        self._proj, p2d, valid=None if drop is None else ~drop, reject_px=reject_px, min_inliers=min_inliers,
+                        out_inliers=None if reject_px is None else (self.inliers[None], self.n_consensus[None])))
             for grp in self.size_groups:
                 slots, vb, gt, stats, idx = grp
                 ids = [self.local_ids[k] for k in slots]
@@ -762,6 +782,36 @@ def _sequence_inputs(points, poses_2d):
     return pts, p2d, pts.shape[0]
 
 
+def _rejection(reject_px, min_inliers):
+    """set_outlier_rejection's arguments -> None (off) or the checked (reject_px, min_inliers)."""
+    if reject_px is None:
+        return None
+    from .triangulation import _checked_rejection
+    return _checked_rejection(reject_px, min_inliers)
+
+
+def _checked_reject(reject, points, poses_3d, who):
+    """`reject`: a loop's set_outlier_rejection setting.  It acts on the triangulation of the initial joints alone: refused
+    beside explicit points or poses_3d.  Returns (reject_px or None, min_inliers)."""
+    if reject is None:
+        return None, 3
+    if points is not None:
+        raise ValueError(f"{who}: outlier rejection (set_outlier_rejection) acts while the initial joints are triangulated "
+                         "(points=None); explicit points are taken as they are -- switch it off with set_outlier_rejection(None)")
+    if poses_3d is not None:
+        raise ValueError(f"{who}: outlier rejection (set_outlier_rejection) belongs to the triangulation; fusing poses_3d is a "
+                         "different estimator and takes every kept view -- switch it off with set_outlier_rejection(None)")
+    return reject
+
+
+def _sequence_consensus(loop, reject, N):
+    """optimize_sequence's (inliers (N,V,J) bool, n_consensus (N,J) int32) on the device, None without rejection."""
+    if reject is None:
+        return None
+    return (torch.empty((N, loop.V, loop.P), dtype=torch.bool, device=loop.device),
+            torch.empty((N, loop.P), dtype=torch.int32, device=loop.device))
+
+
 def _sequence_predictions(points, poses_3d, N):
     """optimize_sequence's `poses_3d` -> None or the (N,V,J,3) predictions as a tensor where they are (arrays: on the host)."""
     if poses_3d is None:
@@ -949,6 +999,11 @@ class FrameBatchLoop(_GroupLoop):
         # K [R|t] per view, float64 on the device, built once: new_scenes(points=None) triangulates with them
         from .triangulation import device_projection_matrices
         self._proj = device_projection_matrices(cameras, dev)
+        self._reject = None     # set_outlier_rejection's (reject_px, min_inliers)
+        # new_scenes(points=None) with rejection: the views each joint of the batch was triangulated from, the winners' counts
+        self.inliers = torch.ones((F, V, self.P), dtype=torch.bool, device=dev)
+        self.n_consensus = torch.zeros((F, self.P), dtype=torch.int32, device=dev)
+        self.seq_inliers = self.seq_n_consensus = None     # optimize_sequence with rejection: the same for its N frames
         sizes = [(int(c.image_width), int(c.image_height)) for c in cams_all]
         # factored (default): the pseudo-GT stays in its separable form (rasterizer.HeatmapFactors) -- the fused step
         # evaluates the pixels it needs, the per-view loss constants come from the factors (sks_heatmap_totals), and no
@@ -1006,6 +1061,13 @@ class FrameBatchLoop(_GroupLoop):
         views' 3D predictions (initial_guess.fuse_predictions, the reference's "metrabs" guess), written into `self.xyz` by one
         launch in the same place with the same `valid = ~drop_masks`; a joint whose views are all dropped starts as NaN.
         Together with explicit `points` it is refused.
+        After `set_outlier_rejection(reject_px, min_inliers)`, with `points=None` and without `poses_3d` (refused otherwise): the
+        triangulation first rejects outlier detections by exhaustive two-view consensus (triangulate_sequence's `reject_px`:
+        one more launch in the same place, `valid = ~drop_masks` still the views it starts from).  The views each joint was solved from are
+        then in `self.inliers` (F,V,J) bool and the winners' counts in `self.n_consensus` (F,J) int32, buffers allocated once.
+        The heat-maps are NOT changed: a rejected detection still draws its plane.  A caller who wants it dropped takes two
+        steps, both on the device: `pts, inl, _ = triangulate_sequence(proj, p2d, reject_px=.., return_inliers=True)`, then
+        `new_scenes(pts, p2d, drop_masks=~inl)`.
         `rig_ids` (F,) ints, host or device (a loop over a rig bank): frame f is seen by rig rig_ids[f] -- one gather launch on
         the current stream fills the batch's camera rows, per-view scalars, projection matrices and schedule rows in place, in
         front of the triangulation and the heat-map factors that read them.  Host ids are validated here; ids in a device
@@ -1022,6 +1084,7 @@ class FrameBatchLoop(_GroupLoop):
             raise ValueError("ready heat-map planes need FrameBatchLoop(..., factored=False)")
         if rig_ids is not None and self._sel is None:
             raise ValueError("rig_ids needs a rig bank: FrameBatchLoop(gaussians, rigs=RigBank(rigs, device), frames=F)")
+        reject_px, min_inliers = _checked_reject(self._reject, points, poses_3d, "new_scenes")
         gt_pose, self._gt_next = _checked_gt(self, self._gt_next, F, "new_scenes"), None      # (`gt` below: heat-map planes)
         with torch.no_grad():
             if self._sel is not None:
@@ -1063,7 +1126,9 @@ class FrameBatchLoop(_GroupLoop):
                     from .initial_guess import fuse_predictions
                     fuse_predictions(self._proj, p3d, p2d_dlt, valid=keep, out=self.xyz)
                 else:
-                    triangulate_sequence(self._proj, p2d_dlt, valid=keep, out=self.xyz)
+                    triangulate_sequence(self._proj, p2d_dlt, valid=keep, out=self.xyz, reject_px=reject_px,
+                                         min_inliers=min_inliers,
+                                         out_inliers=None if reject_px is None else (self.inliers, self.n_consensus))
             else:
                 self.xyz.copy_(pts.to(device=self.device, dtype=torch.float32))
             self.scaling.copy_(self._init[0].expand(F, P, 3))
@@ -1211,12 +1276,13 @@ class FrameBatchLoop(_GroupLoop):
         if self._sel is not None:
             self._sel.check()
 
-    def _next_batch(self, pts, p2d, b, initial=None, rig_ids=None, p3d=None, gt=None):
+    def _next_batch(self, pts, p2d, b, initial=None, rig_ids=None, p3d=None, gt=None, consensus=None):
         """new_scenes for the frames b .. b + F of a sequence (a short last batch is filled up by repeating its final
         frame, rig included); `pts` None: triangulated from the detections.  `initial` (N,P,3): receives the batch's initial
         joints.  `rig_ids`: None or the sequence's (N,) ids as _sequence_rig_ids left them.  `p3d`: None or the sequence's
         (N,V,J,3) predictions, fused into the initial joints instead of the triangulation (`pts` None).  `gt`: None or the sequence's
-        (N,P,3) ground truth as _checked_gt left it."""
+        (N,P,3) ground truth as _checked_gt left it.  `consensus`: None or the
+        sequence's (inliers (N,V,J), n_consensus (N,J)), which receive the batch's rows on the current stream."""
         N, F = p2d.shape[0], self.F
         if gt is not None:
             self._gt_next = gt[b:b + F] if b + F <= N else gt[[min(b + i, N - 1) for i in range(F)]]
@@ -1231,6 +1297,9 @@ class FrameBatchLoop(_GroupLoop):
                             poses_3d=None if p3d is None else p3d[idx])
         if initial is not None:
             initial[b:min(b + F, N)] = self.xyz[:min(F, N - b)]
+        if consensus is not None:
+            consensus[0][b:min(b + F, N)] = self.inliers[:min(F, N - b)]
+            consensus[1][b:min(b + F, N)] = self.n_consensus[:min(F, N - b)]
 
     def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, return_initial=False, rig_ids=None,
                           poses_3d=None):
@@ -1243,19 +1312,25 @@ class FrameBatchLoop(_GroupLoop):
         `rig_ids` (N,) ints, host or device (a loop over a rig bank): the rig of every frame, see new_scenes.
         `poses_3d` (N,V,J,3), with `points=None`: every batch's initial joints are fused from the views' 3D predictions
         instead (new_scenes); a device tensor is never copied to the host.
+        After `set_outlier_rejection(reject_px, min_inliers)`, with `points=None` and without `poses_3d` (refused otherwise): every
+        batch's triangulation rejects outlier detections first (new_scenes); afterwards `self.seq_inliers` (N,V,J) bool and `self.seq_n_consensus` (N,J) int32 hold
+        every frame's views and counts on the device (None after a sequence without rejection).
         A loop that reports: the return value is the same, and `self.report` (a report.SequenceReport) holds the loop's traces,
         final errors, snapshots and step counts for all N frames -- the errors against the (N,P,3) ground truth given to
         `set_ground_truth` before this call, NaN without one."""
         pts, p2d, N = _sequence_inputs(points, poses_2d)
         p3d = _sequence_predictions(points, poses_3d, N)
+        _checked_reject(self._reject, points, poses_3d, "optimize_sequence")
         ids = _sequence_rig_ids(self._sel, rig_ids, N)
+        cons = _sequence_consensus(self, self._reject, N)
+        self.seq_inliers, self.seq_n_consensus = cons if cons is not None else (None, None)
         gt, self._gt_next = _checked_gt(self, self._gt_next, N, "optimize_sequence"), None
         self.report = _sequence_report(self, N)
         F = self.F
         out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
         initial = torch.empty_like(out) if return_initial else None
         for b in range(0, N, F):
-            self._next_batch(pts, p2d, b, initial, ids, p3d, gt)
+            self._next_batch(pts, p2d, b, initial, ids, p3d, gt, cons)
             res = self.run(iterations, groups_per_graph)
             out[b:min(b + F, N)] = res[:min(F, N - b)]
             if self.report is not None:
@@ -1285,6 +1360,14 @@ class FramePipeline:
         self.stopped_at = None       # early stopping: (N,) int64 of the last optimize_sequence, 0 = ran to the end
         self.report = None           # loops that report: report.SequenceReport of the last optimize_sequence
         self._gt_next = None         # set_ground_truth's tensor, until the next optimize_sequence takes it
+        self.inliers = self.n_consensus = None     # optimize_sequence with rejection: (N,V,J) bool, (N,J) int32
+
+    def set_outlier_rejection(self, reject_px=None, min_inliers=3):
+        """FrameBatchLoop.set_outlier_rejection of every loop: from now on optimize_sequence(None, detections) rejects outlier
+        detections while it triangulates (None: off again).  Returns the pipeline."""
+        for fb in self.loops:
+            fb.set_outlier_rejection(reject_px, min_inliers)
+        return self
 
     def set_ground_truth(self, gt):
         """The (N,P,3) float32 ground truth, on the device, of the NEXT optimize_sequence (loops with `report_steps`), which takes
@@ -1304,12 +1387,19 @@ class FramePipeline:
         FrameBatchLoop.new_scenes; check_rigs() reports an id a device tensor held outside the bank.
         `poses_3d` (N,V,J,3), with `points=None`: every batch's initial joints are fused from the views' 3D predictions
         instead of triangulated, by one launch in the same place (initial_guess.fuse_predictions).
+        After `set_outlier_rejection(reject_px, min_inliers)`, with `points=None` and without `poses_3d` (refused otherwise): every
+        batch's triangulation rejects outlier detections first (FrameBatchLoop.new_scenes); afterwards `self.inliers` (N,V,J) bool and `self.n_consensus` (N,J) int32
+        hold every frame's views and counts, each batch's rows copied on its own stream (None after a sequence without
+        rejection).
         Loops that report (`report_steps` / `save_iterations`): `self.report` holds traces, final errors, snapshots and step counts
         of all N frames, copied on each batch's own stream -- the errors against the (N,P,3) ground truth given to
         `set_ground_truth` before this call, NaN without one.  The return value is the same."""
         pts, p2d, N = _sequence_inputs(points, poses_2d)
         p3d = _sequence_predictions(points, poses_3d, N)
+        _checked_reject(self.loops[0]._reject, points, poses_3d, "optimize_sequence")
         ids = _sequence_rig_ids(self.loops[0]._sel, rig_ids, N)     # (uploaded on the caller's stream, which every stream waits for)
+        cons = _sequence_consensus(self.loops[0], self.loops[0]._reject, N)
+        self.inliers, self.n_consensus = cons if cons is not None else (None, None)
         gt, self._gt_next = _checked_gt(self.loops[0], self._gt_next, N, "optimize_sequence"), None
         self.report = _sequence_report(self.loops[0], N)
         F, S = self.F, len(self.loops)
@@ -1321,7 +1411,7 @@ class FramePipeline:
             self.stopped_at = torch.zeros(N, dtype=torch.int64, device=self.device)
             for st in self.streams:
                 st.wait_stream(cur)
-            self._sequence_es(pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial, ids, p3d, gt)
+            self._sequence_es(pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial, ids, p3d, gt, cons)
             for st in self.streams:
                 cur.wait_stream(st)
             self.check_rigs()
@@ -1332,7 +1422,7 @@ class FramePipeline:
             active = list(zip(self.loops, self.streams, starts[w:w + S]))
             for fb, st, b in active:
                 with torch.cuda.stream(st):
-                    fb._next_batch(pts, p2d, b, initial, ids, p3d, gt)
+                    fb._next_batch(pts, p2d, b, initial, ids, p3d, gt, cons)
             for k in range(0, iterations, max(int(interleave), 1)):
                 for fb, st, b in active:
                     with torch.cuda.stream(st):
@@ -1353,7 +1443,7 @@ class FramePipeline:
             fb.check_rigs()
 
     def _sequence_es(self, pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial=None, rig_ids=None,
-                     p3d=None, gt=None):
+                     p3d=None, gt=None, cons=None):
         """optimize_sequence with early stopping: every stream keeps its own batch and takes the next one as soon as its
         batch is done -- all frames stopped (seen in the pinned flags, without waiting) or `iterations` enqueued -- instead
         of waiting for the other streams' batches.  Results and stopping iterations are copied on the batch's stream."""
@@ -1365,7 +1455,7 @@ class FramePipeline:
             if b is None:
                 return None
             with torch.cuda.stream(st):
-                fb._next_batch(pts, p2d, b, initial, rig_ids, p3d, gt)
+                fb._next_batch(pts, p2d, b, initial, rig_ids, p3d, gt, cons)
             return [fb, st, b, 0]
 
         step = max(int(interleave), 1)
