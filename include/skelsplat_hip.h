@@ -101,6 +101,32 @@ int sks_version(void);
 int sks_scratch_bytes(int V, int P, int C, int W, int H, size_t bin_capacity,
                       size_t* geom_bytes, size_t* binning_bytes, size_t* accum_bytes);
 
+/* Which launch forms a call of this shape takes (added to sks_version 14).  Host only, no GPU call: the answer comes from the
+ * functions the launchers themselves call, so a test can assert that a shape reaches the branch it was chosen for and fails loudly
+ * when a threshold is retuned.  out: SKS_REGIME_INTS ints, indexed by the names below.  flags as for sks_forward; out_aligned128:
+ * non-zero = out_color and out_invdepth are 128-byte aligned (every torch allocation is), 0 = only 16-byte aligned.
+ * Images beyond the limits of every entry point (W <= 65536, H <= 1048560, V <= SKS_MAX_VIEWS, C <= SKS_MAX_CHANNELS) are
+ * refused here with the same error. */
+#define SKS_REGIME_PATH        0   /* 0 = small path, 1 = binned path */
+#define SKS_REGIME_COVER       1   /* cover rows of the forward's fill role: 0 = none (the rects are tested directly), 1 = a row per
+                                      (view, band), 2 = a row per (view, plane, band) */
+#define SKS_REGIME_CW          2   /* words per cover row */
+#define SKS_REGIME_PPT         3   /* pixels per lane of a fill pass: 4 (16-byte stores) or 1 */
+#define SKS_REGIME_HALF        4   /* 1 = a 16-byte store is two independently masked pairs (W % 4 == 2, even H) */
+#define SKS_REGIME_ROWMODE     5   /* 1 = row-aligned fill blocks, 0 = linear passes */
+#define SKS_REGIME_PB          6   /* passes per fill block (linear) or rows per fill block (row-aligned) */
+#define SKS_REGIME_FSPLIT      7   /* fill blocks per (plane, band) */
+#define SKS_REGIME_W_MAGIC     8   /* 1 = pixel index % W as a multiply-high in the fill blocks, 0 = plain % */
+#define SKS_REGIME_BWD         9   /* compositing backward: 0 = wave-resident, 1 = LDS-list gather, 2 = per tile (binned path) */
+#define SKS_REGIME_GX         10   /* tile columns */
+#define SKS_REGIME_GY         11   /* tile rows (bands) */
+#define SKS_REGIME_BPC        12   /* binned path: tile bands per block of the scan launch (0 on the small path) */
+#define SKS_REGIME_WAVE_GROUPS 13  /* wave-resident backward: workgroups per (view, Gaussian) (0 elsewhere) */
+#define SKS_REGIME_LEAD       14   /* 31 = a band's first fill pass is a short one that ends on a 128-byte line (outputs, plane or band
+                                      stride not whole lines), 0 = every pass is whole lines */
+#define SKS_REGIME_INTS       16
+int sks_launch_regime(int V, int P, int C, int W, int H, unsigned flags, int out_aligned128, int* out);
+
 /* Replaces _C.rasterize_gaussians (DGR/rasterize_points.cu:35-124 -> rasterizer_impl.cu:198-341).
  * features: (P,C) -- the reference reads them from `sh` with M == 1.
  * Outputs: out_color (V,C,H,W), out_invdepth (V,1,H,W), radii (V,P); every element is written

@@ -31,6 +31,9 @@ SKS_EVAL_MAX_GROUPS = 64
 
 
 SKS_NO_EARLY_FILL = 1 << 30
+SKS_BWD_LDS_LIST = 1 << 20     # tests: the LDS-list backward even when P <= 64
+SKS_FILL_LINEAR = 1 << 21      # tuning/tests: forward fill blocks always in linear (pass-major) mode
+SKS_FILL_ROWS = 1 << 22        # tuning/tests: row-aligned fill blocks whenever W % 4 == 0
 
 
 def SKS_EARLY_FILL(n):
@@ -121,6 +124,7 @@ SIGNATURES = {
     "sks_last_error": (C.c_char_p, []),
     "sks_version": (_i, []),
     "sks_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
+    "sks_launch_regime": (_i, [_i, _i, _i, _i, _i, _u, _i, C.POINTER(_i)]),
     "sks_forward": (_i, [ct for _, ct in FORWARD_PARAMS]),
     "sks_backward": (_i, [ct for _, ct in BACKWARD_PARAMS]),
     "sks_forward_backward": (_i, [ct for _, ct in FORWARD_BACKWARD_PARAMS]),
@@ -210,6 +214,23 @@ def scratch_bytes(V, P, C_, W, H, bin_capacity=0):
     g, b, a = _sz(0), _sz(0), _sz(0)
     check(load().sks_scratch_bytes(V, P, C_, W, H, bin_capacity, C.byref(g), C.byref(b), C.byref(a)), "sks_scratch_bytes")
     return g.value, b.value, a.value
+
+
+# sks_launch_regime's record: field name -> index (include/skelsplat_hip.h, SKS_REGIME_*)
+REGIME_FIELDS = ("path", "cover", "cw", "ppt", "half", "rowmode", "pb", "fsplit", "w_magic", "bwd", "gx", "gy", "bpc", "wave_groups",
+                 "lead")
+REGIME_INTS = 16
+PATH_SMALL, PATH_BINNED = 0, 1
+COVER_NONE, COVER_PER_VIEW, COVER_PER_PLANE = 0, 1, 2
+BWD_WAVE, BWD_GATHER, BWD_TILE = 0, 1, 2
+
+
+def launch_regime(V, P, C_, W, H, flags=0, out_aligned128=True):
+    """Which launch forms a call of this shape takes, as a dict over REGIME_FIELDS (the library's own answer, host only:
+    sks_launch_regime)."""
+    out = (_i * REGIME_INTS)()
+    check(load().sks_launch_regime(V, P, C_, W, H, flags, 1 if out_aligned128 else 0, out), "sks_launch_regime")
+    return {name: out[i] for i, name in enumerate(REGIME_FIELDS)}
 
 
 def prefill_planes(V, P, C_, W, H, flags=0):

@@ -183,8 +183,9 @@ __global__ __launch_bounds__(256) void k_render_bwd_gather(BwdArgs a)
         for (int ch = 0; ch < CG; ch++) col[ch] = 0.0f;
         int klast = -1;
         for (int k = 0; k < n; k++) {
-            const int xr = L.xr[k], yr = L.yr[k];
-            if (tx < (xr & 0xffff) || tx >= (xr >> 16) || ty < (yr & 0xffff) || ty >= (yr >> 16)) continue;
+            // (unsigned halves: a rect's upper tile row reaches 65535, bit 31 of the packed word)
+            const unsigned xr = (unsigned)L.xr[k], yr = (unsigned)L.yr[k];
+            if ((unsigned)tx < (xr & 0xffffu) || (unsigned)tx >= (xr >> 16) || (unsigned)ty < (yr & 0xffffu) || (unsigned)ty >= (yr >> 16)) continue;
             const float2 xy = L.xy[k];
             const float4 co = L.co[k];
             const float dx = xy.x - pxf, dy = xy.y - pyf;
@@ -231,8 +232,9 @@ __global__ __launch_bounds__(256) void k_render_bwd_gather(BwdArgs a)
         }
         // back to front down to g (backward.cu:552-636); only g's own terms are kept
         for (int k = klast; k >= kg; k--) {
-            const int xr = L.xr[k], yr = L.yr[k];
-            if (tx < (xr & 0xffff) || tx >= (xr >> 16) || ty < (yr & 0xffff) || ty >= (yr >> 16)) continue;
+            // (unsigned halves: a rect's upper tile row reaches 65535, bit 31 of the packed word)
+            const unsigned xr = (unsigned)L.xr[k], yr = (unsigned)L.yr[k];
+            if ((unsigned)tx < (xr & 0xffffu) || (unsigned)tx >= (xr >> 16) || (unsigned)ty < (yr & 0xffffu) || (unsigned)ty >= (yr >> 16)) continue;
             const float2 xy = L.xy[k];
             const float4 co = L.co[k];
             const float dx = xy.x - pxf, dy = xy.y - pyf;

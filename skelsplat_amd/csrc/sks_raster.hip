@@ -68,14 +68,22 @@ int check_common(int V, int P, int C, int W, int H)
 // float4 is two independently masked pairs, fwd_fill_role<.., HALF>); anything else streams 4 bytes per lane
 inline bool fill_half_mode(const FwdArgs& a) { return a.W % 4 == 2 && a.H % 2 == 0 && !(a.flags & SKS_NO_NT_STORES); }
 
+// FwdArgs::w_magic: ceil(2^32 / W) where the fill blocks take pixel index % W as a multiply-high, 0 where they use plain %
+inline unsigned fill_w_magic(int W) { return (W >= 2 && W < 16384) ? (unsigned)(((1ull << 32) + (unsigned)W - 1) / (unsigned)W) : 0u; }
+// 31: a band's first fill pass is a short one that ends on a 128-byte line of the address (fill_geometry), 0: every pass is whole lines
+inline int fill_lead(const FwdArgs& a)
+{
+    const bool lines = (((uintptr_t)a.out_color | (uintptr_t)a.out_invdepth) & 127u) == 0;
+    return (lines && (long long)a.H * a.W % 32 == 0 && TILE * a.W % 32 == 0) ? 0 : 31;
+}
+
 inline void fill_geometry(const FwdArgs& a, bool have_cover, bool binned, int& fsplit, int& pb)
 {
     const int ppt = (a.W % 4 == 0 || fill_half_mode(a)) ? 4 : 1;
     // (+31: a band that does not start on a 128-byte line begins with a short pass, fwd_fill_role's `shift`, which the
     // kernel derives from the ADDRESS: the plane and band strides must be whole lines and so must the two base pointers --
     // torch allocations are, a direct C-ABI caller's 16-byte aligned sub-buffer need not be)
-    const bool lines = (((uintptr_t)a.out_color | (uintptr_t)a.out_invdepth) & 127u) == 0;
-    const int lead = (lines && (long long)a.H * a.W % 32 == 0 && TILE * a.W % 32 == 0) ? 0 : 31;
+    const int lead = fill_lead(a);
     const int passes = (TILE * a.W + lead + 256 * ppt - 1) / (256 * ppt);
     const int tune = (int)((a.flags >> 8) & 0xff);                    // tuning knob: passes (or rows) per fill block
     const int chunks = (a.W + 1023) / 1024;
@@ -199,6 +207,9 @@ void launch_fwd_binned(const FwdArgs& a, const BinView& bv, int V, int gx, int g
     }
 }
 
+// whole tile bands per block of k_bin_scan (<= SCAN_T * SCAN_IPT tiles)
+inline int bin_scan_bands(int gx) { return gx >= SCAN_T * 8 ? 1 : (SCAN_T * 8) / gx; }
+
 // workgroups of the binned backward: a fixed number per compute unit of the current device, each walking the tile list
 inline int bwd_tile_blocks()
 {
@@ -289,6 +300,9 @@ bool prefill_cut(PreFill& f, float* color, float* invdepth, int V, int C, int W,
     return true;
 }
 
+// small-path backward: the wave-resident variant (k_render_bwd_wave), else the LDS-list one (k_render_bwd_gather; bit 20 forces it, tests)
+inline bool bwd_small_wave(int P, unsigned flags) { return P <= 64 && !(flags & (1u << 20)); }
+
 // pf: the prefill role's arguments (wave-resident variant only), or null
 template <int CG>
 void launch_bwd_small(const BwdArgs& a, const ViewTan& vt, const ViewOff& vo, int V, int gy, bool dfeat, hipStream_t st,
@@ -298,7 +312,7 @@ void launch_bwd_small(const BwdArgs& a, const ViewTan& vt, const ViewOff& vo, in
     // slot index slowest: a (view, Gaussian) only has work for its first ceil(pixels / 256) slots, so the idle workgroups
     // (half of them on the skeleton scenes) come last in dispatch order instead of holding wave slots the working ones
     // wait for (the fused-loss kernel fits 3 workgroups per CU: 768 of H36M's 1 088 at once)
-    if (a.P <= 64 && !(a.flags & (1u << 20))) {  // wave-resident variant (bit 20: force the LDS variant, tests)
+    if (bwd_small_wave(a.P, a.flags)) {
         dim3 grid(a.P, V, bwd_wave_groups(V, a.P, a.flags));
         if (pf) {
             PreFill f = *pf;
@@ -402,6 +416,38 @@ int sks_scratch_bytes(int V, int P, int C, int W, int H, size_t bin_capacity, si
     return 0;
 }
 
+int sks_launch_regime(int V, int P, int C, int W, int H, unsigned flags, int out_aligned128, int* out)
+{
+    if (int rc = check_common(V, P, C, W, H)) return rc;
+    if (!out) return fail(-2, "sks_launch_regime: out must be provided");
+    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
+    const bool small = P <= SKS_SMALL_P && !(flags & SKS_FORCE_BINNED);
+    const bool cover = small && cover_enabled(P, W, H), per_plane = cover && cover_per_plane(P, W, H, C);
+    FwdArgs a{};
+    a.P = P, a.C = C, a.W = W, a.H = H, a.flags = flags;
+    a.out_color = a.out_invdepth = out_aligned128 ? nullptr : (float*)(uintptr_t)16;   // (only the low address bits are looked at)
+    int fsplit = 0, pb = 0;
+    fill_geometry(a, small ? cover : true, !small, fsplit, pb);
+    const int ppt = (W % 4 == 0 || fill_half_mode(a)) ? 4 : 1;
+    memset(out, 0, SKS_REGIME_INTS * sizeof(int));
+    out[SKS_REGIME_PATH] = small ? 0 : 1;
+    out[SKS_REGIME_COVER] = small ? (per_plane ? 2 : cover ? 1 : 0) : 2;
+    out[SKS_REGIME_CW] = cover_cw(W);
+    out[SKS_REGIME_PPT] = ppt;
+    out[SKS_REGIME_HALF] = fill_half_mode(a) ? 1 : 0;
+    out[SKS_REGIME_ROWMODE] = pb < 0 ? 1 : 0;
+    out[SKS_REGIME_PB] = pb < 0 ? -pb : pb;
+    out[SKS_REGIME_FSPLIT] = fsplit;
+    out[SKS_REGIME_W_MAGIC] = fill_w_magic(W) ? 1 : 0;
+    out[SKS_REGIME_BWD] = !small ? 2 : bwd_small_wave(P, flags) ? 0 : 1;
+    out[SKS_REGIME_GX] = gx;
+    out[SKS_REGIME_GY] = gy;
+    out[SKS_REGIME_BPC] = small ? 0 : bin_scan_bands(gx);
+    out[SKS_REGIME_LEAD] = fill_lead(a);
+    out[SKS_REGIME_WAVE_GROUPS] = (small && bwd_small_wave(P, flags)) ? bwd_wave_groups(V, P, flags) : 0;
+    return 0;
+}
+
 }  // extern "C"
 
 namespace {
@@ -448,7 +494,7 @@ int forward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, con
     const int gplanes = (small && g.cover && cover_per_plane(P, W, H, C)) ? C + 1 : 1;     // a block per plane's cover rows
     FwdArgs a{ P, C, W, H, flags, g, features, out_color, out_invdepth, final_T, n_contrib, composite_slots(flags, V, P),
                ((1u << 20) + (unsigned)C) / (unsigned)(C + 1), 0, (!small || (g.cover && cover_per_plane(P, W, H, C))) ? 1 : 0,
-               (W >= 2 && W < 16384) ? (unsigned)(((1ull << 32) + (unsigned)W - 1) / (unsigned)W) : 0u };
+               fill_w_magic(W) };
     const int cg = pick_cg(C);
     // Plain small-path forward with cover rows: the geometry launch zeroes the last `early` planes (launch_geom_fill), the fill +
     // composite launch streams the planes in front of them, and ONE kind-0 scope spans both -- the time in which every byte of the
@@ -517,7 +563,7 @@ int forward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, con
     int vg, ng;
     bin_groups(flags, V, vg, ng);
     {
-        const int bpc = gx >= SCAN_T * 8 ? 1 : (SCAN_T * 8) / gx;   // whole tile bands per scan block (<= SCAN_T * SCAN_IPT tiles)
+        const int bpc = bin_scan_bands(gx);
         const int nchunk_t = (gy + bpc - 1) / bpc, nchunk_g = (P + SCAN_G - 1) / SCAN_G;
         hipLaunchKernelGGL(k_bin_scan, dim3(nchunk_t + nchunk_g, V), dim3(SCAN_T), (size_t)bpc * cw * 4, st, P, gx, gy, cw, bpc,
                            nchunk_t, bin_capacity, b, cover, num_rendered_dev, V, C + 1, vg);

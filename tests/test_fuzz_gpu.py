@@ -83,3 +83,11 @@ def test_random_shapes_through_the_smaller_ops(device, block):
     from tests.fuzz_cases import run_ops_case
     for seed in range(100 + 30 * block, 100 + 30 * (block + 1)):
         run_ops_case(seed, device)
+
+
+@pytest.mark.parametrize("seed", range(400, 412))
+def test_random_shapes_at_the_geometry_boundaries(device, seed):
+    """Shapes drawn around the launch-regime thresholds (tests/geometry_cases.py fuzz_case: +- a tile, +- a pixel, every W mod 4)."""
+    from tests.geometry_cases import run_case as run_geom_case
+    r = run_geom_case(seed, device)
+    assert r["visible"] > 0 and r["grad"] > 0
