@@ -3,7 +3,7 @@
 other, train.py:74-99) -- but many frames per launch: noisy 2D detections of N frames -> DLT initial guesses -> 500
 iterations of the multi-view loop for every frame (loop.FramePipeline) -> MPJPE per frame.
 python examples/optimize_sequence.py [--frames 64] [--per-launch 16] [--streams 2] [--iters 500] [--init host|device|fuse] [--rigs R]
-    [--report] [--reject-px PX] [--corrupt K]
+    [--report] [--uncertainty] [--reject-px PX] [--corrupt K]
 --rigs R: the frames cycle through R jittered ring rigs (SyntheticScene seeds 0 .. R-1), as a dataset whose scenes bring their own
 cameras does; one rigs.RigBank holds them on the device and every batch names its frames' rigs (rig_ids).
 --init host (default): the DLT runs on the host, frame by frame, and its points are uploaded; --init device: the detections
@@ -20,6 +20,10 @@ detections were rejected.  The heat-maps still draw every detection: the final e
 skelsplat_amd/report.py): the mean absolute / root-relative error over the sequence after 0, 1, 5, 25 and the last optimiser
 step -- the reference's convergence curve (train.py:184-213) --, the error at the snapshot of the middle iteration, and
 report.evaluate_sequence over four synthetic "activities" (eval.py:115-142).  Nothing is read back while the loops run.
+--uncertainty (with --report's ground truth): the loops keep every frame's optimised Gaussians (keep_gaussians=True) and the
+covariances are read back as the pose's uncertainty on the device (skelsplat_amd/uncertainty.py): the share of ground-truth joints
+inside the 1 / 2 / 3-sigma ellipsoid overall and per joint (utils/analize_error_confidence_correlation.py's percent_inside_sigmas
+and .._per_joint) and the mean trace of the covariance.
 The curve falls from the reference's default start, --init fuse (21.7 -> 14.3 mm); from the DLT start (--init host / device) it
 RISES from 13.4 to 14.3 mm in the first steps: on this synthetic sequence (3 px of detection noise, exact cameras) the DLT already
 sits below the optimiser's fixed point, and the curve shows it."""
@@ -48,6 +52,7 @@ def main():
     ap.add_argument("--init", choices=("host", "device", "fuse"), default="host")
     ap.add_argument("--rigs", type=int, default=1)
     ap.add_argument("--report", action="store_true")
+    ap.add_argument("--uncertainty", action="store_true")
     ap.add_argument("--reject-px", type=float, default=None)
     ap.add_argument("--corrupt", type=int, default=0)
     args = ap.parse_args()
@@ -65,6 +70,8 @@ def main():
         for k in rng.choice(args.views * sc.n_points, size=args.corrupt, replace=False):
             r, th = rng.uniform(80.0, 300.0), rng.uniform(0.0, 2.0 * np.pi)
             p2d[f, k // sc.n_points, k % sc.n_points] += (r * np.cos(th), r * np.sin(th))
+    if args.uncertainty and not args.report:
+        ap.error("--uncertainty measures against --report's ground truth: use the two together")
     if args.reject_px is not None and args.init != "device":
         ap.error("--reject-px rejects while triangulating on the device: use it with --init device")
     Pm = [triangulation.projection_matrices(rig) for rig in rigs]
@@ -76,6 +83,8 @@ def main():
     gm.training_setup()
     steps = -(-args.iters // args.views)        # optimiser steps of a frame: one per accumulation group
     rep = dict(report_steps=steps + 1, save_iterations=(0, args.iters // 2, args.iters)) if args.report else {}
+    if args.uncertainty:
+        rep["keep_gaussians"] = True
     if args.rigs > 1:
         from skelsplat_amd.rigs import RigBank
         pipe = FramePipeline(gm, rigs=RigBank(rigs, dev), frames=args.per_launch, streams=args.streams, dataset=args.dataset,
@@ -143,6 +152,16 @@ def main():
         print(f"evaluate_sequence: abs MPJPE {float(ev['abs']):.3f} mm, rel {float(ev['rel']):.3f} mm; per activity abs "
               + " ".join(f"{x:.2f}" for x in ev["abs_groups"].tolist()) + " | rel "
               + " ".join(f"{x:.2f}" for x in ev["rel_groups"].tolist()))
+    if args.uncertainty:
+        from skelsplat_amd.uncertainty import calibration
+        unc = pipe.gaussians.uncertainty(gt_dev)
+        cal = calibration(unc.d2, ks=(1, 2, 3))
+        names = [f"joint {j}" for j in range(sc.n_joints)]
+        print(f"uncertainty: mean trace of the covariance {float(unc.trace.double().mean()):.1f} mm^2, mean anisotropy "
+              f"{float(unc.anisotropy.double().mean()):.2f}")
+        print("ground truth inside   1 sigma   2 sigma   3 sigma")
+        for name, row in [("all joints", cal["overall"].tolist())] + list(zip(names, cal["per_joint"].tolist())):
+            print(f"{name:18s} " + " ".join(f"{100.0 * x:8.1f}%" for x in row))
 
 
 if __name__ == "__main__":

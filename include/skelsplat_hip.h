@@ -675,6 +675,51 @@ int sks_loop_report(int frames, int V, int P, const int* counters, const int* es
 int sks_eval_sequence(int N, int P, const float* pred, const float* gt, const int* group_ids, int n_groups,
                       const unsigned char* abs_valid, double* out, void* stream);
 
+/* The optimised Gaussians read back as the pose's uncertainty (csrc/sks_uncertainty.hip; added to sks_version 14: the number did
+ * not move): what the reference's analysis scripts take from the covariance a scene leaves behind
+ * (utils/analize_error_confidence_correlation.py, utils/analize_2D_anisotropy.py).  One launch each on `stream`, nothing
+ * synchronises, no atomics, no scratch.  Everything a (frame, joint) or (view, joint) receives depends on its own inputs only --
+ * never on N, on its place in the batch or on the stream --, so a NaN or inf input poisons those outputs of its own joint that
+ * depend on it and nobody else's.  Bad arguments are refused before any HIP call.  Device memory unless marked HOST.
+ *
+ * sks_joint_uncertainty: scales (N,P,3) ACTIVATED, rotations (N,P,4) raw quaternions, as sks_heatmap_factors takes them; xyz
+ *   (N,P,3) and gt (N,P,3) go together with d2, or gt and d2 are NULL (xyz is then not read).  One thread per (frame, joint).
+ *     cov6 (N,P,6): xx, xy, xz, yy, yz, zz (strip_symmetric, general_utils.py:73-85) of Sigma = L L^T, L = R diag(sd),
+ *       sd_k = scale_modifier * s_k, R from the NORMALISED quaternion -- the float sequence sks_heatmap_factors forms Sigma with
+ *       (one __device__ function, csrc/sks_gauss.h): Sigma[a][b] = (L[a][0] L[b][0] + L[a][1] L[b][1]) + L[a][2] L[b][2].
+ *     spectrum (N,P,6): l1 >= l2 >= l3, trace, det, anisotropy.  Sigma = R S^2 R^T, so its eigenvalues ARE sd_k * sd_k:
+ *       the three float products, sorted (a NaN stays in its slot); no eigen-solver, which on a needle would lose the small ones.
+ *       trace = (xx + yy) + zz of cov6; det = (l1 * l2) * l3; anisotropy = l1 / l3.
+ *     d2 (N,P), with gt: the squared Mahalanobis distance of the ground truth, by whitening: delta = gt - xyz,
+ *       w_k = ((R[0][k] delta[0] + R[1][k] delta[1]) + R[2][k] delta[2]) / sd_k, d2 = (w_0^2 + w_1^2) + w_2^2.  No 3x3 inverse is
+ *       formed (the reference's np.linalg.inv(cov), analize_error_confidence_correlation.py:48-54, is the same number in exact
+ *       arithmetic and worse conditioned).
+ *   N x P <= 2^28 - 1.
+ *
+ * sks_view_footprints: lambdas (V,J,2) = l1 >= l2, the two variances in px^2 of the blob each view's pseudo-GT is drawn with: the
+ *   numbers sks_heatmap_factors forms before its square roots (the reference's own transcription of the EWA projection,
+ *   general_utils.py:212-262, with the 0.3 px^2 low-pass and the max(0.1, .) guard), bit for bit -- the same __device__ function.
+ *   means3D / scales / rotations / scale_modifier / viewmatrix / W / H / frames as sks_heatmap_factors.  The per-view scalars come
+ *   in exactly ONE of two forms: tanfovx, tanfovy HOST arrays of V with view_wh HOST V x {W,H} or NULL (sks_heatmap_factors'), or
+ *   views_dev, the device table of sks_heatmap_factors_dv (then the three host pointers are NULL).  One thread per (view, joint).
+ *   The ratio of analize_2D_anisotropy.py:50 is l1 / l2.
+ *
+ * sks_calibration: d2 (N,P) floats, valid (N) bytes or NULL, k_sigma HOST K floats (1 <= K <= SKS_CALIBRATION_MAX_K, each finite
+ *   and > 0, copied by value) -> counts (1 + P, K + 1) int32.  Row 0 is over all joints, row 1 + j over joint j; column k counts
+ *   the entries with d2 <= k_sigma[k] * k_sigma[k] (the product in float), column K the entries counted at all: a frame with
+ *   valid != 0 (or valid NULL) and a d2 that is not NaN.  The fractions of percent_inside_sigmas / percent_inside_sigmas_per_joint
+ *   (analize_error_confidence_correlation.py:38-60, 86-113) are counts[:, k] / counts[:, K].  One workgroup per row: thread t
+ *   takes frames t, t + 256, ..., then a fixed tree in LDS; integers, so the counts are exact in any order.  N x P <= 2^31 - 1. */
+#define SKS_CALIBRATION_MAX_K 8
+int sks_joint_uncertainty(int N, int P, const float* xyz, const float* scales, const float* rotations, float scale_modifier,
+                          const float* gt, float* cov6, float* spectrum, float* d2, void* stream);
+int sks_view_footprints(int V, int J, int W, int H, const float* means3D, const float* scales, const float* rotations,
+                        float scale_modifier, const float* viewmatrix, const float* tanfovx /*HOST V or NULL*/,
+                        const float* tanfovy /*HOST V or NULL*/, const int* view_wh /*HOST V x {W,H} or NULL*/,
+                        const void* views_dev /*or NULL*/, int frames, float* lambdas, void* stream);
+int sks_calibration(int N, int P, const float* d2, const unsigned char* valid, int K, const float* k_sigma /*HOST K*/, int* counts,
+                    void* stream);
+
 /* Measurement hook used by bench.py (no reference counterpart; state per HOST THREAD, like the error text): while enabled, the dominant kernel of sks_forward
  * (kind 0: forward compositor) and of sks_backward (kind 1: backward compositor) is bracketed by hipEvents recorded
  * on the caller's stream (the small path's kernels carry the pair on their own dispatch, hipExtLaunchKernelGGL).  The low 16

@@ -10,6 +10,7 @@
 
 #include "../../include/skelsplat_hip.h"
 #include "sks_err.h"
+#include "sks_gauss.h"
 #include "sks_math.h"
 
 namespace {
@@ -384,22 +385,11 @@ __global__ __launch_bounds__(256) void k_heatmaps(int W, int H, int J, const flo
 // ewa_lambdas_views + _impulse_response_1d + heatmap_factors, operation for operation: fp32 up to sqrt(lambda), fp64 for
 // the responses).  Note the reference's operand order (R J)^T Sigma^T (R J) -- see heatmaps.py.
 // ------------------------------------------------------------------------------------------------------------
-struct HmTan {
-    float x[SKS_MAX_VIEWS], y[SKS_MAX_VIEWS];
-    int w[SKS_MAX_VIEWS], h[SKS_MAX_VIEWS];   // per-view image size (<= the W, H strides of row / col)
-};
-
-struct HmTanDev {   // the same scalars in device memory (the *_dv entry points: the ViewTan table sks_rig_select fills)
-    const float* x;
-    const float* y;
-    const int* w;
-    const int* h;
-};
-inline HmTanDev hm_tan_dev(const void* views_dev)
-{
-    const HmTan* t = (const HmTan*)views_dev;     // (same layout as the rasterizer's ViewTan; addresses only)
-    return HmTanDev{ t->x, t->y, t->w, t->h };
-}
+// (HmTan: the per-view scalars by value; HmTanDev: read from the device table -- both in sks_gauss.h, with the float sequences of
+// lambda1 / lambda2 this kernel shares with sks_uncertainty.hip)
+using sks::HmTan;
+using sks::HmTanDev;
+using sks::hm_tan_dev;
 
 __device__ __forceinline__ double block_sum_d(double v, double* s_red)
 {
@@ -486,39 +476,9 @@ __global__ __launch_bounds__(256) void k_heatmap_factors(int J, int W, int H, co
         means += fr * J * 3; scales += fr * J * 3; rots += fr * J * 4;
     }
     // ---- lambda1, lambda2 (every thread the same scalars) ----
-    const float q0 = rots[4 * j], q1 = rots[4 * j + 1], q2 = rots[4 * j + 2], q3 = rots[4 * j + 3];
-    const float qn = sqrtf(((q0 * q0 + q1 * q1) + q2 * q2) + q3 * q3);
-    const float r = q0 / qn, x = q1 / qn, y = q2 / qn, z = q3 / qn;
-    const float R[3][3] = { { 1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y) },
-                            { 2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x) },
-                            { 2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y) } };
-    float L[3][3], Sg[3][3];
-    for (int a = 0; a < 3; a++)
-        for (int k = 0; k < 3; k++) L[a][k] = R[a][k] * (scale_modifier * scales[3 * j + k]);
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) Sg[a][b] = (L[a][0] * L[b][0] + L[a][1] * L[b][1]) + L[a][2] * L[b][2];
-    const float* vm = viewmatrix + 16 * v;   // world_view_transform as stored (the matrix transposed): M[i][k] = vm[4k + i]
-    const float px = means[3 * j], py = means[3 * j + 1], pz = means[3 * j + 2];
-    float t[3];
-    for (int i = 0; i < 3; i++) t[i] = ((vm[i] * px + vm[4 + i] * py) + vm[8 + i] * pz) + vm[12 + i] * 1.0f;
-    const float tanx = tan.x[v], tany = tan.y[v];
-    const float fx = (float)W / (2.0f * tanx), fy = (float)H / (2.0f * tany);
-    const float tz = t[2];
-    const float tx = fminf(fmaxf(t[0] / tz, -1.3f * tanx), 1.3f * tanx) * tz;
-    const float ty = fminf(fmaxf(t[1] / tz, -1.3f * tany), 1.3f * tany) * tz;
-    const float Jm[3][3] = { { fx / tz, 0.0f, -(fx * tx) / (tz * tz) }, { 0.0f, fy / tz, -(fy * ty) / (tz * tz) }, { 0.0f, 0.0f, 0.0f } };
-    float T[3][3], A[3][3], cov[2][2];
-    for (int a = 0; a < 3; a++)
-        for (int c = 0; c < 3; c++) T[a][c] = (vm[a] * Jm[0][c] + vm[4 + a] * Jm[1][c]) + vm[8 + a] * Jm[2][c];
-    for (int a = 0; a < 3; a++)      // A = T^T Sigma^T
-        for (int b = 0; b < 3; b++) A[a][b] = (T[0][a] * Sg[b][0] + T[1][a] * Sg[b][1]) + T[2][a] * Sg[b][2];
-    for (int a = 0; a < 2; a++)      // cov = A T
-        for (int c = 0; c < 2; c++) cov[a][c] = (A[a][0] * T[0][c] + A[a][1] * T[1][c]) + A[a][2] * T[2][c];
-    const float cx = cov[0][0] + 0.3f, cy = cov[0][1], cz = cov[1][1] + 0.3f;
-    const float det = cx * cz - cy * cy;
-    const float mid = 0.5f * (cx + cz);
-    const float root = sqrtf(fmaxf(mid * mid - det, 0.1f));
-    const float l1 = mid + root, l2 = mid - root;
+    float R[3][3], sd[3], Sg[3][3], l1, l2;
+    sks::gaussian_sigma(rots + 4 * j, scales + 3 * j, scale_modifier, R, sd, Sg);
+    sks::ewa_lambdas(Sg, viewmatrix + 16 * v, means + 3 * j, W, H, tan.x[v], tan.y[v], l1, l2);
     // ---- responses: sigma1 filters rows (axis 0), sigma2 columns; the impulse sits at the truncated 2D detection ----
     const int xs = min(max((int)poses_2d[2 * vj], 0), W - 1), ys = min(max((int)poses_2d[2 * vj + 1], 0), H - 1);
     float rmin, rmax, kmin, kmax;

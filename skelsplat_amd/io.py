@@ -20,13 +20,27 @@ def attribute_names(n_dc, n_rest, n_scale=3, n_rot=4):
 
 def save_ply(path, gm):
     """gm: object with _xyz (P,3), _features_dc (P,1,C), _features_rest (P,R,C), _opacity (P,1), _scaling, _rotation."""
+    save_ply_arrays(path, gm, gm._xyz, gm._scaling, gm._rotation, gm._opacity)
+
+
+def save_ply_arrays(path, gm, xyz, scaling, rotation, opacity):
+    """The file save_ply writes for a model that holds ONE frame's xyz (P,3), scaling (P,3), rotation (P,4), opacity (P,1) --
+    host arrays or host / device tensors, e.g. a row of a loop's `gaussians` (uncertainty.SequenceGaussians) -- with the features
+    of the template `gm` (the loops' `gaussians` argument: _features_dc (P,1,C), _features_rest (P,R,C)).  Byte for byte
+    save_ply of that model."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    t = lambda x: x.detach().cpu().numpy().astype(np.float32)
-    xyz = t(gm._xyz)
+    t = lambda x: (x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)).astype(np.float32)
+    xyz, scaling, rotation, opacity = t(xyz), t(scaling), t(rotation), t(opacity)
+    P = xyz.shape[0]
+    for name, a, k in (("xyz", xyz, 3), ("scaling", scaling, None), ("rotation", rotation, None), ("opacity", opacity, 1)):
+        if a.ndim != 2 or a.shape[0] != P or (k is not None and a.shape[1] != k):
+            raise ValueError(f"save_ply_arrays: `{name}` must be (P,{k or 'k'}) with P = {P} (one frame), got {a.shape}")
     f_dc = t(gm._features_dc.transpose(1, 2).flatten(start_dim=1))
     f_rest = t(gm._features_rest.transpose(1, 2).flatten(start_dim=1))
-    cols = np.concatenate((xyz, np.zeros_like(xyz), f_dc, f_rest, t(gm._opacity), t(gm._scaling), t(gm._rotation)), axis=1)
-    names = attribute_names(f_dc.shape[1], f_rest.shape[1], gm._scaling.shape[1], gm._rotation.shape[1])
+    if f_dc.shape[0] != P:
+        raise ValueError(f"save_ply_arrays: the template model has {f_dc.shape[0]} Gaussians, the frame {P}")
+    cols = np.concatenate((xyz, np.zeros_like(xyz), f_dc, f_rest, opacity, scaling, rotation), axis=1)
+    names = attribute_names(f_dc.shape[1], f_rest.shape[1], scaling.shape[1], rotation.shape[1])
     assert cols.shape[1] == len(names)
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {xyz.shape[0]}"]
     header += [f"property float {n}" for n in names] + ["end_header"]

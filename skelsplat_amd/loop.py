@@ -874,6 +874,14 @@ def _sequence_report(loop, N):
     return SequenceReport(loop, N)
 
 
+def _sequence_gaussians(loop, out):
+    """optimize_sequence's `gaussians` around the joints `out` it returns: None for a loop that does not keep them."""
+    if not loop.keep_gaussians:
+        return None
+    from .uncertainty import SequenceGaussians
+    return SequenceGaussians(out)
+
+
 def _frame_criterion(early_stopping):
     """FrameBatchLoop's `early_stopping` -> None (off) or (window, tolerance) of the reference's criterion, which the frame
     batch runs per frame on the device; anything else is refused."""
@@ -923,11 +931,15 @@ class FrameBatchLoop(_GroupLoop):
     entry points -- nothing of a rig is baked into a captured graph, so `_graph` / `_multi` are replayed as they are for a batch
     with other rigs.  `gaussians.opt_cfg` supplies every hyper-parameter except the spatial scale of the xyz learning rate,
     which is each frame's own rig's `cameras_extent` (build the bank with the same `opt`).  A frame's trajectory is bit-identical
-    to FrameBatchLoop(cameras=that rig) running it alone.  The image size of a view slot stays fixed across rigs."""
+    to FrameBatchLoop(cameras=that rig) running it alone.  The image size of a view slot stays fixed across rigs.
+
+    `keep_gaussians=True`: `optimize_sequence` keeps every frame's scaling, rotation and opacity next to its joints
+    (`self.gaussians`, an uncertainty.SequenceGaussians) -- the Gaussian per joint the reference saves per scene, and what
+    skelsplat_amd/uncertainty.py reads back as the pose's uncertainty.  Off (default): nothing is allocated or enqueued for it."""
 
     def __init__(self, gaussians, cameras=None, frames=None, dataset="h36m", accumulation_steps=4, lambda_consistency=1e-5,
                  antialiasing=False, use_graph=False, factored=True, early_stopping="no_stopping", rigs=None, report_steps=0,
-                 save_iterations=()):
+                 save_iterations=(), keep_gaussians=False):
         from .report import check_report_args
         check_report_args(report_steps, save_iterations)
         if (cameras is None) == (rigs is None):
@@ -983,6 +995,10 @@ class FrameBatchLoop(_GroupLoop):
             from .report import LoopReport
             self._report = LoopReport(F, V, P, report_steps, save_iterations, dev)
         self.report = None      # optimize_sequence's report.SequenceReport of the last sequence
+        # keep_gaussians: optimize_sequence keeps every frame's scaling / rotation / opacity next to its joints
+        # (uncertainty.SequenceGaussians in `gaussians`); off: nothing is allocated and nothing more is enqueued
+        self.keep_gaussians = bool(keep_gaussians)
+        self.gaussians = None
         self._gt_next = None    # set_ground_truth's tensor, until the next new_scenes / optimize_sequence takes it
         self._sched, self._lrs, self._adam, self._limb = _optimiser_arrays(gm.opt_cfg, dataset, self.lambda_consistency)
         cams_all = [cameras[k % V] for k in range(F * V)]
@@ -1317,7 +1333,10 @@ class FrameBatchLoop(_GroupLoop):
         every frame's views and counts on the device (None after a sequence without rejection).
         A loop that reports: the return value is the same, and `self.report` (a report.SequenceReport) holds the loop's traces,
         final errors, snapshots and step counts for all N frames -- the errors against the (N,P,3) ground truth given to
-        `set_ground_truth` before this call, NaN without one."""
+        `set_ground_truth` before this call, NaN without one.
+        A loop built with keep_gaussians=True: afterwards `self.gaussians` (an uncertainty.SequenceGaussians) holds every frame's
+        xyz -- the tensor returned --, scaling, rotation and opacity as the frame ended, what scene.save_h36m writes
+        (io.save_ply_arrays) and uncertainty.joint_uncertainty reads; None otherwise."""
         pts, p2d, N = _sequence_inputs(points, poses_2d)
         p3d = _sequence_predictions(points, poses_3d, N)
         _checked_reject(self._reject, points, poses_3d, "optimize_sequence")
@@ -1329,10 +1348,13 @@ class FrameBatchLoop(_GroupLoop):
         F = self.F
         out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
         initial = torch.empty_like(out) if return_initial else None
+        self.gaussians = _sequence_gaussians(self, out)
         for b in range(0, N, F):
             self._next_batch(pts, p2d, b, initial, ids, p3d, gt, cons)
             res = self.run(iterations, groups_per_graph)
             out[b:min(b + F, N)] = res[:min(F, N - b)]
+            if self.gaussians is not None:
+                self.gaussians.take(self, b, min(F, N - b))
             if self.report is not None:
                 self.report.take(self, b, min(F, N - b))
         self.check_rigs()
@@ -1359,6 +1381,7 @@ class FramePipeline:
         self.F, self.P = self.loops[0].F, self.loops[0].P
         self.stopped_at = None       # early stopping: (N,) int64 of the last optimize_sequence, 0 = ran to the end
         self.report = None           # loops that report: report.SequenceReport of the last optimize_sequence
+        self.gaussians = None        # keep_gaussians=True: uncertainty.SequenceGaussians of the last optimize_sequence
         self._gt_next = None         # set_ground_truth's tensor, until the next optimize_sequence takes it
         self.inliers = self.n_consensus = None     # optimize_sequence with rejection: (N,V,J) bool, (N,J) int32
 
@@ -1393,7 +1416,9 @@ class FramePipeline:
         rejection).
         Loops that report (`report_steps` / `save_iterations`): `self.report` holds traces, final errors, snapshots and step counts
         of all N frames, copied on each batch's own stream -- the errors against the (N,P,3) ground truth given to
-        `set_ground_truth` before this call, NaN without one.  The return value is the same."""
+        `set_ground_truth` before this call, NaN without one.  The return value is the same.
+        Loops built with keep_gaussians=True: `self.gaussians` (an uncertainty.SequenceGaussians) holds every frame's scaling,
+        rotation and opacity next to the joints returned, copied on each batch's own stream; None otherwise."""
         pts, p2d, N = _sequence_inputs(points, poses_2d)
         p3d = _sequence_predictions(points, poses_3d, N)
         _checked_reject(self.loops[0]._reject, points, poses_3d, "optimize_sequence")
@@ -1405,6 +1430,7 @@ class FramePipeline:
         F, S = self.F, len(self.loops)
         out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
         initial = torch.empty_like(out) if return_initial else None
+        self.gaussians = _sequence_gaussians(self.loops[0], out)
         cur = torch.cuda.current_stream(self.device)
         starts = list(range(0, N, F))
         if self.loops[0]._es is not None:
@@ -1430,6 +1456,8 @@ class FramePipeline:
             for fb, st, b in active:
                 with torch.cuda.stream(st):
                     out[b:min(b + F, N)] = fb.xyz[:min(F, N - b)]
+                    if self.gaussians is not None:
+                        self.gaussians.take(fb, b, min(F, N - b))
                     if self.report is not None:
                         self.report.take(fb, b, min(F, N - b))
         for st in self.streams:
@@ -1472,6 +1500,8 @@ class FramePipeline:
                         n = min(F, N - b)
                         out[b:b + n] = fb.xyz[:n]
                         self.stopped_at[b:b + n] = fb._es_state[:n, 1]      # (0: the frame ran to the end)
+                        if self.gaussians is not None:
+                            self.gaussians.take(fb, b, n)
                         if self.report is not None:
                             self.report.take(fb, b, n)
                         slot = take(fb, st)

@@ -17,6 +17,8 @@ save_iterations=), set_ground_truth(gt)): the H36M pipeline (S streams of F fram
   off          as it ran before: the launch sequence of a group is unchanged;
   on           errors and losses at every optimiser step, three snapshots: one more launch of F wavefronts per group;
   parent_off   (--parent DIR, a built checkout of the commit to compare with) that tree's pipeline, reporting unknown to it.
+bench_frames.py --report --keep [...]: the same three-way comparison for FramePipeline(keep_gaussians=True) (case `keep`: every
+frame's scaling / rotation / opacity copied next to its joints, three small device copies per batch) in place of `on`.
 Every tree is measured by a worker process of its own that stays warm; the driver asks them for one repetition of one case at a
 time, round-robin, N times, so drift hits all cases alike.  Prints median, min and max per case and the ratios of the medians."""
 import os, sys, time
@@ -107,10 +109,11 @@ def bench_rigs(argv):
 
 
 def report_worker(argv):
-    """One tree's pipeline(s), warm; per line on stdin ("off" / "on") one timed sequence, its frames/s on stdout."""
+    """One tree's pipeline(s), warm; per line on stdin ("off" / "on" / "keep") one timed sequence, its frames/s on stdout."""
     import inspect
     from skelsplat_amd.loop import FramePipeline
     F, S = int(argv[0]), int(argv[1])
+    keep = len(argv) > 2 and argv[2] == "keep"
     iters = int(os.environ.get("ITERS", "500"))
     N = S * F * 4
     sc = SyntheticScene("h36m", n_views=4, seed=0, device=dev)
@@ -124,7 +127,10 @@ def report_worker(argv):
         gm.training_setup()
         return gm
     pipes = {"off": (FramePipeline(model(), sc.cameras, frames=F, streams=S, dataset="h36m"), None)}
-    if "report_steps" in inspect.signature(FrameBatchLoop.__init__).parameters:
+    if keep:
+        if "keep_gaussians" in inspect.signature(FrameBatchLoop.__init__).parameters:
+            pipes["keep"] = (FramePipeline(model(), sc.cameras, frames=F, streams=S, dataset="h36m", keep_gaussians=True), None)
+    elif "report_steps" in inspect.signature(FrameBatchLoop.__init__).parameters:
         pipes["on"] = (FramePipeline(model(), sc.cameras, frames=F, streams=S, dataset="h36m", report_steps=iters // 4 + 1,
                                      save_iterations=(0, iters // 2, iters)), gt)
     for pipe, truth in pipes.values():
@@ -147,6 +153,7 @@ def bench_report(argv):
     import argparse, statistics, subprocess
     ap = argparse.ArgumentParser()
     ap.add_argument("--report", action="store_true")
+    ap.add_argument("--keep", action="store_true")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--streams", type=int, default=2)
@@ -157,7 +164,8 @@ def bench_report(argv):
 
     def worker(root):
         env = dict(os.environ, SKS_BENCH_ROOT=os.path.abspath(root))
-        w = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--report-worker", str(a.frames), str(a.streams)],
+        w = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--report-worker", str(a.frames), str(a.streams),
+                              "keep" if a.keep else "report"],
                              stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env=env, cwd=root)
         head = w.stdout.readline().split()
         if not head or head[0] != "ready":
@@ -186,8 +194,9 @@ def bench_report(argv):
         print(f"report {c:10s}: median {med[c]:7.0f} frames/s  min {min(v):7.0f}  max {max(v):7.0f}  ({a.streams} streams x "
               f"{a.frames} frames, {N} frames, {os.environ.get('ITERS', '500')} iterations, {a.reps} interleaved repetitions)  all: "
               + " ".join(f"{x:.0f}" for x in v))
-    if "on" in med:
-        print(f"report on / off = {med['on'] / med['off']:.4f}")
+    for c in ("on", "keep"):
+        if c in med:
+            print(f"report {c} / off = {med[c] / med['off']:.4f}")
     if "parent_off" in med:
         lo, hi = min(rates["parent_off"]), max(rates["parent_off"])
         print(f"report off / parent_off = {med['off'] / med['parent_off']:.4f}; median of off "
