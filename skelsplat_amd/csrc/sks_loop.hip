@@ -145,10 +145,9 @@ int sks_loop_adam_step(int V, int P, const float* grads, float* slots, unsigned 
 {
     if (V < 1 || V > SKS_MAX_VIEWS || P < 1 || P > SKS_SMALL_P) return fail3(-1, "loop_adam: V or P out of range");
     AdamArgs a;
-    if (const char* err = sksloop::fill_adam_args(a, V, P, grads, slots, group_mask, last_view, xyz, scaling, rotation, opacity,
-                                                  exp_avg, exp_avg_sq, counters, acc_steps, lr_sched, lrs, adam,
-                                                  lambda_consistency, limb, shard_world))
-        return fail3(-2, err);
+    sksloop::Optimiser opt;
+    SKS_TAKE_OPTIMISER(opt, lr_sched);
+    if (const char* err = sksloop::fill_adam_args(a, V, P, grads, opt, shard_world)) return fail3(-2, err);
     hipLaunchKernelGGL(k_loop_adam, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail3((int)e, hipGetErrorString(e));
@@ -166,10 +165,9 @@ int sks_loop_adam_step_es(int V, int P, const float* grads, float* slots, unsign
     if (es_window < 1 || es_window > sksloop::ES_MAX_WINDOW) return fail3(-1, "loop_adam_es: window out of range [1, 16]");
     if (shard_world == 1 && !loss_sums) return fail3(-2, "loop_adam_es: loss_sums is required on one rank");
     AdamArgs a;
-    if (const char* err = sksloop::fill_adam_args(a, V, P, grads, slots, group_mask, last_view, xyz, scaling, rotation, opacity,
-                                                  exp_avg, exp_avg_sq, counters, acc_steps, lr_sched, lrs, adam,
-                                                  lambda_consistency, limb, shard_world))
-        return fail3(-2, err);
+    sksloop::Optimiser opt;
+    SKS_TAKE_OPTIMISER(opt, lr_sched);
+    if (const char* err = sksloop::fill_adam_args(a, V, P, grads, opt, shard_world)) return fail3(-2, err);
     a.es_state = es_state; a.es_window = es_window; a.es_tol = es_tolerance; a.es_sums = loss_sums; a.es_host_flag = es_host_flag;
     if (shard_world > 1 && !loss_sums) a.rank_stride = sksloop::es_tail_offset(a.vmax, P) + 4ll * a.vmax;
     hipLaunchKernelGGL(k_loop_adam, dim3(1), dim3(256), 0, (hipStream_t)stream, a);

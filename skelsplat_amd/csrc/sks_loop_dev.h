@@ -310,34 +310,42 @@ __device__ __forceinline__ void adam_block_finish(const AdamArgs& a, float* s_xy
 }
 
 
-// host: fills AdamArgs from the C ABI's argument lists; returns nullptr or an error text
-inline const char* fill_adam_args(AdamArgs& a, int V, int P, const float* grads, float* slots, unsigned long long group_mask,
-                                  int last_view, float* xyz, float* scaling, float* rotation, float* opacity, float* exp_avg,
-                                  float* exp_avg_sq, int* counters, int acc_steps, const double* lr_sched, const double* lrs,
-                                  const double* adam, float lambda_consistency, const int* limb, int shard_world = 1)
+// host: the optimiser block of the step entry points (sks_loop_adam_step*, sks_loop_fused_step*) under the names of
+// skelsplat_amd/_lib.py's OPTIMISER_PARAMS; SKS_TAKE_OPTIMISER fills one from an entry point's parameters of the same names
+struct Optimiser {   // lr_sched, lrs, adam, limb are HOST arrays: 5 {init, final, delay_mult, delay_steps, max_steps}, 3, 3 {beta1, beta2, eps}, 8 or NULL
+    float* slots; unsigned long long group_mask; int last_view; float *xyz, *scaling, *rotation, *opacity, *exp_avg, *exp_avg_sq;
+    int* counters; int acc_steps; const double *lr_sched, *lrs, *adam; float lambda_consistency; const int* limb;
+};
+#define SKS_TAKE_OPTIMISER(o, sched)                                                                                                          \
+    ((o).slots = slots, (o).group_mask = group_mask, (o).last_view = last_view, (o).xyz = xyz, (o).scaling = scaling, (o).rotation = rotation, \
+     (o).opacity = opacity, (o).exp_avg = exp_avg, (o).exp_avg_sq = exp_avg_sq, (o).counters = counters, (o).acc_steps = acc_steps,           \
+     (o).lr_sched = (sched), (o).lrs = lrs, (o).adam = adam, (o).lambda_consistency = lambda_consistency, (o).limb = limb)
+
+// host: fills AdamArgs from the block; returns nullptr or an error text
+inline const char* fill_adam_args(AdamArgs& a, int V, int P, const float* grads, const Optimiser& o, int shard_world = 1)
 {
     if (shard_world < 1) return "loop_adam: shard_world must be >= 1";
     a.world = shard_world;
     a.vmax = (V + shard_world - 1) / shard_world;
     a.rank_stride = (long long)a.vmax * P * 11;
     a.es_state = nullptr; a.es_window = 0; a.es_tol = 0.0f; a.es_sums = nullptr; a.es_host_flag = nullptr;
-    if (!grads || !slots || !xyz || !scaling || !rotation || !opacity || !exp_avg || !exp_avg_sq || !counters || !lr_sched || !lrs || !adam)
+    if (!grads || !o.slots || !o.xyz || !o.scaling || !o.rotation || !o.opacity || !o.exp_avg || !o.exp_avg_sq || !o.counters || !o.lr_sched || !o.lrs || !o.adam)
         return "loop_adam: missing pointer";
-    if (last_view < 0 || last_view >= V) return "loop_adam: last_view out of range";
-    a.V = V; a.P = P; a.grads = grads; a.slots = slots; a.group_mask = group_mask; a.last_view = last_view;
-    a.xyz = xyz; a.scaling = scaling; a.rotation = rotation; a.opacity = opacity; a.m = exp_avg; a.vv = exp_avg_sq;
-    a.counters = counters; a.acc_steps = acc_steps;
-    a.lr_init = lr_sched[0]; a.lr_final = lr_sched[1]; a.lr_delay_mult = lr_sched[2];
+    if (o.last_view < 0 || o.last_view >= V) return "loop_adam: last_view out of range";
+    a.V = V; a.P = P; a.grads = grads; a.slots = o.slots; a.group_mask = o.group_mask; a.last_view = o.last_view;
+    a.xyz = o.xyz; a.scaling = o.scaling; a.rotation = o.rotation; a.opacity = o.opacity; a.m = o.exp_avg; a.vv = o.exp_avg_sq;
+    a.counters = o.counters; a.acc_steps = o.acc_steps;
+    a.lr_init = o.lr_sched[0]; a.lr_final = o.lr_sched[1]; a.lr_delay_mult = o.lr_sched[2];
     // (log(0) = -inf like np.log in the reference, general_utils.py:66: a schedule with one zero end point is 0 where that end
     // point has weight and NaN where its weight is exactly 0; an all-zero schedule is switched off before it gets here)
-    a.log_lr_init = log(lr_sched[0]);
-    a.log_lr_final = log(lr_sched[1]);
-    a.lr_delay_steps = (int)lr_sched[3]; a.lr_max_steps = (int)lr_sched[4];
-    a.lr_scaling = lrs[0]; a.lr_rotation = lrs[1]; a.lr_opacity = lrs[2];
-    a.beta1 = adam[0]; a.beta2 = adam[1]; a.eps = adam[2];
-    a.lambda_consistency = lambda_consistency;
-    for (int i = 0; i < 8; i++) a.limb[i] = limb ? limb[i] : -1;
-    if (limb) for (int i = 0; i < 8; i++) if (limb[i] < 0 || limb[i] >= P) return "loop_adam: limb index out of range";
+    a.log_lr_init = log(o.lr_sched[0]);
+    a.log_lr_final = log(o.lr_sched[1]);
+    a.lr_delay_steps = (int)o.lr_sched[3]; a.lr_max_steps = (int)o.lr_sched[4];
+    a.lr_scaling = o.lrs[0]; a.lr_rotation = o.lrs[1]; a.lr_opacity = o.lrs[2];
+    a.beta1 = o.adam[0]; a.beta2 = o.adam[1]; a.eps = o.adam[2];
+    a.lambda_consistency = o.lambda_consistency;
+    for (int i = 0; i < 8; i++) a.limb[i] = o.limb ? o.limb[i] : -1;
+    if (o.limb) for (int i = 0; i < 8; i++) if (o.limb[i] < 0 || o.limb[i] >= P) return "loop_adam: limb index out of range";
     a.n_joints = P;
     return nullptr;
 }

@@ -20,13 +20,20 @@
 //   sks_bwd_small.inc  backward cores, k_render_bwd_gather / k_render_bwd_wave (+ fused loss), k_gt_tile_stats
 //   sks_geom_bwd.inc   k_geom_bwd, k_step_tail (geometry backward + Adam + next geometry in one workgroup)
 //   sks_binned.inc     k_bin_*, k_render_fwd_binned, k_render_bwd_binned
-// followed here by the launchers and the extern "C" entry points of include/skelsplat_hip.h.
+// followed here by the host layer:
+//   helpers         with_cg (the one channel-group dispatch), is_small / TileGrid, the call records (Cameras, Gaussians, ForwardIO,
+//                   Upstream, Grads -> FwdCall, BwdCall; StepRender, sksloop::Optimiser, StepHeatmaps, EarlyStop -> StepCall: the
+//                   blocks of skelsplat_amd/_lib.py under the same names), the argument checks that more than one entry point makes
+//   launchers       fill geometry, launch_fwd_small / _binned, launch_geom_fill / launch_geom_fwd, launch_bwd_small / _loss, prefill
+//   implementations forward_impl(FwdCall), backward_impl(BwdCall), loop_fused_step_impl(StepCall)
+//   extern "C"      the entry points of include/skelsplat_hip.h: each fills its record by name (SKS_TAKE_*) and calls one of the three
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdarg.h>
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
+#include <initializer_list>
 #include <type_traits>
 
 #include "../../include/skelsplat_hip.h"
@@ -48,6 +55,60 @@ namespace {
 // host side
 // ------------------------------------------------------------------------------------------------------------
 inline int pick_cg(int C) { return C <= 4 ? 4 : C <= 16 ? 16 : C <= 20 ? 20 : 32; }
+// the channel group of C as a compile-time constant: f(std::integral_constant<int, CG>) -- the launchers stay templates on CG
+template <class F>
+inline void with_cg(int C, F&& f)
+{
+    switch (pick_cg(C)) {
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 16: f(std::integral_constant<int, 16>{}); break;
+        case 20: f(std::integral_constant<int, 20>{}); break;
+        default: f(std::integral_constant<int, 32>{}); break;
+    }
+}
+
+// which path a call takes, and its tile grid
+inline bool is_small(int P, unsigned flags) { return P <= SKS_SMALL_P && !(flags & SKS_FORCE_BINNED); }
+struct TileGrid {
+    int gx, gy, NT;
+    TileGrid(int W, int H) : gx((W + TILE - 1) / TILE), gy((H + TILE - 1) / TILE), NT(gx * gy) {}
+};
+
+// ---- call records: the blocks of the C ABI's argument lists under the names skelsplat_amd/_lib.py gives them ----
+// An entry point fills its record BY NAME from its parameters (the SKS_TAKE_* macros in front of the entry points, one per
+// block) and hands it on by const reference: nothing below an entry point counts commas.
+// _CAMERAS (the tangents: HOST, V each; NO_TAN from the _dv entries, whose cameras' scalars are in StepCall::views_dev)
+struct Cameras { int V, P, C, W, H; const float *viewmatrix, *projmatrix, *tanfovx, *tanfovy; };
+// _GAUSSIANS
+struct Gaussians { const float *means3D, *features, *opacities, *scales, *rotations, *cov3D_precomp; float scale_modifier; unsigned flags; };
+// _FORWARD_IO
+struct ForwardIO { float *out_color, *out_invdepth; int* radii; void *geom, *binning; size_t bin_capacity; int* num_rendered_dev; };
+// _UPSTREAM
+struct Upstream { const float *dL_dout_color, *dL_dout_invdepth; void* accum; };
+// _GRADS
+struct Grads { float *dL_dmeans3D, *dL_dmeans2D, *dL_dopacity, *dL_dscales, *dL_drotations, *dL_dcov3D, *dL_dfeatures, *dL_dmeans3D_mean; };
+// FORWARD_PARAMS
+struct FwdCall { Cameras cam; Gaussians g; ForwardIO io; float* final_T; uint32_t* n_contrib; hipStream_t stream; };
+// BACKWARD_PARAMS
+struct BwdCall {
+    Cameras cam; const float* bg; Gaussians g; const int* radii; const void *geom, *binning; size_t bin_capacity;
+    Upstream up; Grads grads; hipStream_t stream;
+};
+// _STEP_RENDER
+struct StepRender {
+    const float* features; float scale_modifier; unsigned flags; int* radii; void* geom; const float* gt; const double* gt_totals;
+    void* accum; double* loss_sums; float* packed;
+};
+// _STEP_HEATMAPS (view_wh: HOST, V x {W, H}, or null; gt_offsets: HOST, V, or null; hm_factors: HOST row of 4 device pointers, or null)
+struct StepHeatmaps { const int* view_wh; const size_t* gt_offsets; int frames; const float* const* hm_factors; };
+// _ES + the per-frame host flags; es_state == null: the step without a criterion
+struct EarlyStop { int* es_state; int es_window; float es_tolerance; int* es_host_flags; };
+// LOOP_FUSED_STEP{,_ES,_DV,_ES_DV}_PARAMS.  views_dev: the _dv entries' device view table, else null; opt: OPTIMISER_PARAMS (_dv:
+// opt.lr_sched is NO_SCHED and every frame's schedule row is read in the kernel from lr_sched_dev)
+struct StepCall {
+    Cameras cam; const void* views_dev; StepRender r; sksloop::Optimiser opt; const double* lr_sched_dev; StepHeatmaps hm; EarlyStop es;
+    hipStream_t stream;
+};
 
 int check_common(int V, int P, int C, int W, int H)
 {
@@ -57,6 +118,25 @@ int check_common(int V, int P, int C, int W, int H)
     if (W < 1 || H < 1 || W > 4096 * TILE || H > 65535 * TILE) return fail(-1, "image %dx%d out of range", W, H);
     return 0;
 }
+inline int check_common(const Cameras& c) { return check_common(c.V, c.P, c.C, c.W, c.H); }
+// the argument checks more than one entry point makes, one owner each
+inline int require(std::initializer_list<const void*> ptrs)
+{
+    for (const void* p : ptrs)
+        if (!p) return fail(-2, "missing required pointer");
+    return 0;
+}
+inline int need_cov(const float* scales, const float* rotations, const float* cov3D_precomp)
+{
+    return (!cov3D_precomp && (!scales || !rotations)) ? fail(-2, "need scales+rotations or cov3D_precomp") : 0;
+}
+inline int check_frames(int V, int frames) { return (frames < 1 || V % frames) ? fail(-1, "frames must divide the number of views (V = %d, frames = %d)", V, frames) : 0; }
+inline int check_hm_factors(const float* const* hm) { return (hm && (!hm[0] || !hm[1] || !hm[2] || !hm[3])) ? fail(-2, "hm_factors: row, col, cmin, den must all be given") : 0; }
+inline int check_wh_offsets(const float* const* hm_factors, const int* view_wh, const size_t* gt_offsets)
+{
+    return (!hm_factors && (view_wh != nullptr) != (gt_offsets != nullptr)) ? fail(-2, "view_wh and gt_offsets go together") : 0;
+}
+inline int bad_view_wh() { return fail(-1, "view_wh: every view's size must be within [1, W] x [1, H] (pass the largest as W, H)"); }   // (fill_views said no)
 
 // Fill-block geometry shared by the two forward launchers.  Row-aligned mode when the image width keeps >= 90% of
 // the lanes of a 1024-pixel chunk busy AND a row is a whole number of 128-byte lines (1920, 2048 ... wide images;
@@ -71,11 +151,13 @@ inline bool fill_half_mode(const FwdArgs& a) { return a.W % 4 == 2 && a.H % 2 ==
 // FwdArgs::w_magic: ceil(2^32 / W) where the fill blocks take pixel index % W as a multiply-high, 0 where they use plain %
 inline unsigned fill_w_magic(int W) { return (W >= 2 && W < 16384) ? (unsigned)(((1ull << 32) + (unsigned)W - 1) / (unsigned)W) : 0u; }
 // 31: a band's first fill pass is a short one that ends on a 128-byte line of the address (fill_geometry), 0: every pass is whole lines
-inline int fill_lead(const FwdArgs& a)
+// (a null set: a rule asks -- it is answered for the worst alignment a 16-byte aligned set can have, so that what it promises the call accepts)
+inline int fill_lead(const float* color, const float* invdepth, int W, int H)
 {
-    const bool lines = (((uintptr_t)a.out_color | (uintptr_t)a.out_invdepth) & 127u) == 0;
-    return (lines && (long long)a.H * a.W % 32 == 0 && TILE * a.W % 32 == 0) ? 0 : 31;
+    const bool lines = color && invdepth && (((uintptr_t)color | (uintptr_t)invdepth) & 127u) == 0;
+    return (lines && (long long)H * W % 32 == 0 && TILE * W % 32 == 0) ? 0 : 31;
 }
+inline int fill_lead(const FwdArgs& a) { return fill_lead(a.out_color, a.out_invdepth, a.W, a.H); }
 
 inline void fill_geometry(const FwdArgs& a, bool have_cover, bool binned, int& fsplit, int& pb)
 {
@@ -169,24 +251,42 @@ bool early_fill_cut(const FwdArgs& a_in, int V, int gy, int gplanes, int zid0, i
     return fsplit >= 1 && pb >= 1 && nfill * rows < (1ll << 32) && (long long)V * gplanes + nfill < (1ll << 31);
 }
 
-void launch_geom_fill(const FwdArgs& a, int V, int gy, int gplanes, int zid0, int zid1, int fsplit, int pb, const ViewTan& vt,
-                      const float* viewmatrix, const float* projmatrix, const float* means3D, const float* opacities,
-                      const float* scales, const float* rotations, const float* cov3D_precomp, float smod, int* radii,
-                      hipStream_t st, ProfScope& prof)
+void launch_geom_fill(const FwdArgs& a, const FwdCall& c, int gy, int gplanes, int zid0, int zid1, int fsplit, int pb, const ViewTan& vt,
+                      ProfScope& prof)
 {
+    const hipStream_t st = c.stream;
     const long long rows = (long long)fsplit * gy, nfill = rows * (zid1 - zid0);
-    const int ngeom = V * gplanes;
+    const int ngeom = c.cam.V * gplanes;
     const EarlyFill f{ a.out_color, a.out_invdepth, a.C, a.W, a.H, gy, gplanes, ngeom, zid0, fsplit, pb, a.cp1_magic,
                        rows > 1 ? magic32((unsigned)rows) : 0u, fsplit > 1 ? magic32((unsigned)fsplit) : 0u };   // (0: divisor 1)
     const dim3 grid((unsigned)(ngeom + nfill));
     const size_t lds = (size_t)gy * cover_cw(a.W) * 4;   // one plane's cover rows (<= COVER_MAX_WORDS words: cover_enabled)
     const bool nt = !(a.flags & SKS_NO_NT_STORES);   // (fill_half_mode implies it)
     const int ppt = (a.W % 4 == 0 || fill_half_mode(a)) ? 4 : 1;
-#define SKS_GF_ARGS f, a.P, vt, viewmatrix, projmatrix, means3D, opacities, scales, rotations, cov3D_precomp, smod, a.flags, a.g, radii, a.features, a.cover_planes
+#define SKS_GF_ARGS f, a.P, vt, c.cam.viewmatrix, c.cam.projmatrix, c.g.means3D, c.g.opacities, c.g.scales, c.g.rotations, c.g.cov3D_precomp, \
+                    c.g.scale_modifier, a.flags, a.g, c.io.radii, a.features, a.cover_planes
     if (ppt == 4 && nt) SKS_LAUNCH_FIRST(prof, (k_geom_fwd_fill<4, true>), grid, dim3(256), lds, st, SKS_GF_ARGS);
     else if (ppt == 4) SKS_LAUNCH_FIRST(prof, (k_geom_fwd_fill<4, false>), grid, dim3(256), lds, st, SKS_GF_ARGS);
     else SKS_LAUNCH_FIRST(prof, (k_geom_fwd_fill<1, false>), grid, dim3(256), lds, st, SKS_GF_ARGS);
 #undef SKS_GF_ARGS
+}
+
+#ifndef SKS_GEOM_BINNED_THREADS
+#define SKS_GEOM_BINNED_THREADS 256
+#endif
+// The plain geometry launch of a forward.  b: the binned path's scratch (all null on the small path); done: the event that rides on
+// the kernel's own dispatch (sks_forward_backward's small path: no marker packet), or null.
+void launch_geom_fwd(const FwdCall& c, const ViewTan& vt, const Geom& g, const Bin& b, bool small, int gplanes, hipEvent_t done)
+{
+    const Cameras& cam = c.cam;
+    const int gthreads = small ? 256 : SKS_GEOM_BINNED_THREADS;
+    const dim3 grid((cam.P + gthreads - 1) / gthreads, cam.V, gplanes);
+#define SKS_G_ARGS cam.P, cam.W, cam.H, vt, cam.viewmatrix, cam.projmatrix, c.g.means3D, c.g.opacities, c.g.scales, c.g.rotations, c.g.cov3D_precomp, \
+                   c.g.scale_modifier, c.g.flags, g, c.io.radii, 0, b.count, b.touched, c.g.features, cam.C, b.fmask, b.hdr,                          \
+                   (small && cover_per_plane(cam.P, cam.W, cam.H, cam.C)) ? 1 : 0
+    if (done) hipExtLaunchKernelGGL(k_geom_fwd, grid, dim3(gthreads), 0, c.stream, nullptr, done, 0, SKS_G_ARGS);
+    else hipLaunchKernelGGL(k_geom_fwd, grid, dim3(gthreads), 0, c.stream, SKS_G_ARGS);
+#undef SKS_G_ARGS
 }
 
 template <int CG>
@@ -239,23 +339,12 @@ inline int bwd_wave_groups(int V, int P, unsigned flags)
 // the fused-loss variant of the wave-resident backward: heat-maps as planes or (a.hm_row) as separable factors;
 // ES: the per-frame early-stopping instantiations (sks_loop_fused_step_es, a.es_stop set)
 template <bool ES = false>
-inline void launch_bwd_loss(const BwdArgs& a, const ViewTan& vt, const ViewOff& vo, dim3 grid, int cg, hipStream_t st)
+inline void launch_bwd_loss(const BwdArgs& a, const ViewTan& vt, const ViewOff& vo, int V, hipStream_t st)
 {
-    if (a.hm_row) {
-        switch (cg) {
-            case 4: hipLaunchKernelGGL((k_render_bwd_wave<4, false, true, true, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
-            case 16: hipLaunchKernelGGL((k_render_bwd_wave<16, false, true, true, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
-            case 20: hipLaunchKernelGGL((k_render_bwd_wave<20, false, true, true, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
-            default: hipLaunchKernelGGL((k_render_bwd_wave<32, false, true, true, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
-        }
-        return;
-    }
-    switch (cg) {
-        case 4: hipLaunchKernelGGL((k_render_bwd_wave<4, false, true, false, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
-        case 16: hipLaunchKernelGGL((k_render_bwd_wave<16, false, true, false, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
-        case 20: hipLaunchKernelGGL((k_render_bwd_wave<20, false, true, false, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
-        default: hipLaunchKernelGGL((k_render_bwd_wave<32, false, true, false, ES>), grid, dim3(256), 0, st, a, vt, vo); break;
-    }
+    const dim3 grid(a.P, V, bwd_wave_groups(V, a.P, a.flags));   // see launch_bwd_small
+    // (two dispatches, not one with the test inside: the instantiations keep the order the device code was always emitted in)
+    if (a.hm_row) with_cg(a.C, [&](auto cg) { hipLaunchKernelGGL((k_render_bwd_wave<decltype(cg)::value, false, true, true, ES>), grid, dim3(256), 0, st, a, vt, vo); });
+    else with_cg(a.C, [&](auto cg) { hipLaunchKernelGGL((k_render_bwd_wave<decltype(cg)::value, false, true, false, ES>), grid, dim3(256), 0, st, a, vt, vo); });
 }
 
 // ---- prefill: the small-path backward's two launches zero the last planes of the NEXT forward's output set ----
@@ -278,7 +367,7 @@ inline int prefill_passes()
 // 16-byte non-temporal stores on the wave-resident small path, or nothing
 inline bool prefill_possible(int P, int W, int H, unsigned flags)
 {
-    return P >= 1 && P <= 64 && P <= SKS_SMALL_P && !(flags & (SKS_FORCE_BINNED | SKS_NO_NT_STORES | SKS_DEBUG_SYNC | (1u << 20))) &&
+    return P >= 1 && P <= 64 && is_small(P, flags) && !(flags & (SKS_NO_NT_STORES | SKS_DEBUG_SYNC | SKS_BWD_LDS_LIST)) &&
            (W % 4 == 0 || (W % 4 == 2 && H % 2 == 0));
 }
 // The role's arguments for the planes [zid0, zid0 + nz) of the set (color, invdepth); false where the kernel's index arithmetic
@@ -286,11 +375,8 @@ inline bool prefill_possible(int P, int W, int H, unsigned flags)
 // k_render_bwd_wave, or 1).
 bool prefill_cut(PreFill& f, float* color, float* invdepth, int V, int C, int W, int H, int zid0, int nz, long long per_unit, long long max_units)
 {
-    const int gy = (H + TILE - 1) / TILE;
-    // (null set: the rule asks -- it answers for the worst alignment a 16-byte aligned set can have, so that what it promises the call accepts)
-    const bool lines = color && invdepth && (((uintptr_t)color | (uintptr_t)invdepth) & 127u) == 0;
-    const int lead = (lines && (long long)H * W % 32 == 0 && TILE * W % 32 == 0) ? 0 : 31;   // (fill_geometry)
-    const int passes = (TILE * W + lead + 1023) / 1024;
+    const int gy = TileGrid(W, H).gy;
+    const int passes = (TILE * W + fill_lead(color, invdepth, W, H) + 1023) / 1024;
     const int pb = prefill_passes();
     const int fsplit = (passes + pb - 1) / pb;
     const long long rows = (long long)fsplit * gy, nfill = rows * nz;
@@ -300,15 +386,14 @@ bool prefill_cut(PreFill& f, float* color, float* invdepth, int V, int C, int W,
     return true;
 }
 
-// small-path backward: the wave-resident variant (k_render_bwd_wave), else the LDS-list one (k_render_bwd_gather; bit 20 forces it, tests)
-inline bool bwd_small_wave(int P, unsigned flags) { return P <= 64 && !(flags & (1u << 20)); }
+// small-path backward: the wave-resident variant (k_render_bwd_wave), else the LDS-list one (k_render_bwd_gather; SKS_BWD_LDS_LIST forces it, tests)
+inline bool bwd_small_wave(int P, unsigned flags) { return P <= 64 && !(flags & SKS_BWD_LDS_LIST); }
 
 // pf: the prefill role's arguments (wave-resident variant only), or null
 template <int CG>
-void launch_bwd_small(const BwdArgs& a, const ViewTan& vt, const ViewOff& vo, int V, int gy, bool dfeat, hipStream_t st,
-                      const ProfScope& prof, const PreFill* pf = nullptr)
+void launch_bwd_small(const BwdArgs& a, const ViewTan& vt, const ViewOff& vo, int V, bool dfeat, hipStream_t st, const ProfScope& prof,
+                      const PreFill* pf = nullptr)
 {
-    (void)gy;
     // slot index slowest: a (view, Gaussian) only has work for its first ceil(pixels / 256) slots, so the idle workgroups
     // (half of them on the skeleton scenes) come last in dispatch order instead of holding wave slots the working ones
     // wait for (the fused-loss kernel fits 3 workgroups per CU: 768 of H36M's 1 088 at once)
@@ -393,10 +478,6 @@ int fb_events(int ngroups, FbEvents*& out)
 
 }  // namespace
 
-#ifndef SKS_GEOM_BINNED_THREADS
-#define SKS_GEOM_BINNED_THREADS 256
-#endif
-
 extern "C" {
 
 const char* sks_last_error(void) { return g_err; }
@@ -409,9 +490,9 @@ int sks_version(void) { return 14; }
 int sks_scratch_bytes(int V, int P, int C, int W, int H, size_t bin_capacity, size_t* geom, size_t* binning, size_t* accum)
 {
     if (int rc = check_common(V, P, C, W, H)) return rc;
-    const int NT = ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
+    const TileGrid t(W, H);
     if (geom) *geom = geom_bytes(V, P > 0 ? P : 1, W, H, C);
-    if (binning) *binning = bin_bytes(V, P, NT, bin_capacity, C + 1, (size_t)((H + TILE - 1) / TILE) * cover_cw(W));
+    if (binning) *binning = bin_bytes(V, P, t.NT, bin_capacity, C + 1, (size_t)t.gy * cover_cw(W));
     if (accum) *accum = (size_t)V * (P > 0 ? P : 1) * BWD_SPLITS * (NACC + C) * sizeof(float);
     return 0;
 }
@@ -420,12 +501,12 @@ int sks_launch_regime(int V, int P, int C, int W, int H, unsigned flags, int out
 {
     if (int rc = check_common(V, P, C, W, H)) return rc;
     if (!out) return fail(-2, "sks_launch_regime: out must be provided");
-    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-    const bool small = P <= SKS_SMALL_P && !(flags & SKS_FORCE_BINNED);
+    const TileGrid t(W, H);
+    const bool small = is_small(P, flags);
     const bool cover = small && cover_enabled(P, W, H), per_plane = cover && cover_per_plane(P, W, H, C);
     FwdArgs a{};
     a.P = P, a.C = C, a.W = W, a.H = H, a.flags = flags;
-    a.out_color = a.out_invdepth = out_aligned128 ? nullptr : (float*)(uintptr_t)16;   // (only the low address bits are looked at)
+    a.out_color = a.out_invdepth = (float*)(uintptr_t)(out_aligned128 ? 128 : 16);   // (only the low address bits are looked at)
     int fsplit = 0, pb = 0;
     fill_geometry(a, small ? cover : true, !small, fsplit, pb);
     const int ppt = (W % 4 == 0 || fill_half_mode(a)) ? 4 : 1;
@@ -440,9 +521,9 @@ int sks_launch_regime(int V, int P, int C, int W, int H, unsigned flags, int out
     out[SKS_REGIME_FSPLIT] = fsplit;
     out[SKS_REGIME_W_MAGIC] = fill_w_magic(W) ? 1 : 0;
     out[SKS_REGIME_BWD] = !small ? 2 : bwd_small_wave(P, flags) ? 0 : 1;
-    out[SKS_REGIME_GX] = gx;
-    out[SKS_REGIME_GY] = gy;
-    out[SKS_REGIME_BPC] = small ? 0 : bin_scan_bands(gx);
+    out[SKS_REGIME_GX] = t.gx;
+    out[SKS_REGIME_GY] = t.gy;
+    out[SKS_REGIME_BPC] = small ? 0 : bin_scan_bands(t.gx);
     out[SKS_REGIME_LEAD] = fill_lead(a);
     out[SKS_REGIME_WAVE_GROUPS] = (small && bwd_small_wave(P, flags)) ? bwd_wave_groups(V, P, flags) : 0;
     return 0;
@@ -452,50 +533,48 @@ int sks_launch_regime(int V, int P, int C, int W, int H, unsigned flags, int out
 
 namespace {
 
-int forward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
-                 const float* tanfovx, const float* tanfovy, const float* means3D, const float* features,
-                 const float* opacities, const float* scales, const float* rotations, const float* cov3D_precomp,
-                 float scale_modifier, unsigned flags, float* out_color, float* out_invdepth, int* radii, void* geom,
-                 void* binning, size_t bin_capacity, int* num_rendered_dev, float* final_T, uint32_t* n_contrib,
-                 void* stream, const FwdHook* hook, int prefilled = 0)
+int forward_impl(const FwdCall& c, const FwdHook* hook, int prefilled)
 {
-    if (int rc = check_common(V, P, C, W, H)) return rc;
-    hipStream_t st = (hipStream_t)stream;
+    const Cameras& cam = c.cam;
+    const int V = cam.V, P = cam.P, C = cam.C, W = cam.W, H = cam.H;
+    const unsigned flags = c.g.flags;
+    const size_t bin_capacity = c.io.bin_capacity;
+    if (int rc = check_common(cam)) return rc;
+    const hipStream_t st = c.stream;
     if (prefilled < 0 || prefilled > (C + 1) * V) return fail(-1, "prefilled_planes=%d out of range [0,%d]", prefilled, (C + 1) * V);
-    if (!out_color || !out_invdepth) return fail(-2, "out_color / out_invdepth must be provided");
-    if (((uintptr_t)out_color | (uintptr_t)out_invdepth) & 15u)
+    if (!c.io.out_color || !c.io.out_invdepth) return fail(-2, "out_color / out_invdepth must be provided");
+    if (((uintptr_t)c.io.out_color | (uintptr_t)c.io.out_invdepth) & 15u)
         return fail(-2, "out_color / out_invdepth must be 16-byte aligned (the planes are written with 16-byte stores)");
     const size_t HW = (size_t)H * W;
     if (P == 0) {  // rasterize_points.cu:88: nothing rendered, outputs stay zero
-        HIP_TRY(hipMemsetAsync(out_color, 0, (size_t)V * C * HW * 4, st));
-        HIP_TRY(hipMemsetAsync(out_invdepth, 0, (size_t)V * HW * 4, st));
-        if (final_T) return fail(-2, "final_T not available for P == 0");
+        HIP_TRY(hipMemsetAsync(c.io.out_color, 0, (size_t)V * C * HW * 4, st));
+        HIP_TRY(hipMemsetAsync(c.io.out_invdepth, 0, (size_t)V * HW * 4, st));
+        if (c.final_T) return fail(-2, "final_T not available for P == 0");
         return 0;
     }
-    if (!viewmatrix || !projmatrix || !tanfovx || !tanfovy || !means3D || !features || !opacities || !radii || !geom)
-        return fail(-2, "missing required pointer");
-    if (!cov3D_precomp && (!scales || !rotations)) return fail(-2, "need scales+rotations or cov3D_precomp");
+    if (int rc = require({ cam.viewmatrix, cam.projmatrix, cam.tanfovx, cam.tanfovy, c.g.means3D, c.g.features, c.g.opacities, c.io.radii, c.io.geom }))
+        return rc;
+    if (int rc = need_cov(c.g.scales, c.g.rotations, c.g.cov3D_precomp)) return rc;
     ViewTan vt;
     ViewOff vo;
-    fill_views(vt, &vo, V, C, W, H, tanfovx, tanfovy, nullptr, nullptr);
-    Geom g = geom_from(geom, V, P, W, H);
-    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE, NT = gx * gy;
+    fill_views(vt, &vo, V, C, W, H, cam.tanfovx, cam.tanfovy, nullptr, nullptr);
+    Geom g = geom_from(c.io.geom, V, P, W, H);
+    const TileGrid t(W, H);
+    const int gx = t.gx, gy = t.gy, NT = t.NT;
 
-    const bool small = P <= SKS_SMALL_P && !(flags & SKS_FORCE_BINNED);
+    const bool small = is_small(P, flags);
     Bin b{};
     if (!small) {
-        if (!binning) return fail(-2, "binned path needs a binning buffer");
+        if (!c.io.binning) return fail(-2, "binned path needs a binning buffer");
         if (bin_capacity < 1) return fail(-1, "binned path needs bin_capacity >= 1");
-        b = bin_from(binning, V, P, NT, bin_capacity);
+        b = bin_from(c.io.binning, V, P, NT, bin_capacity);
         // (nothing to clear: k_geom_fwd zeroes the header, k_bin_band_count writes every tile's count)
     }
     if (!small) g.cover = nullptr;   // (the binned path's cover rows are per plane: Bin::coverp, k_bin_scan + k_bin_sort_long)
-    const int gthreads = small ? 256 : SKS_GEOM_BINNED_THREADS;
     const int gplanes = (small && g.cover && cover_per_plane(P, W, H, C)) ? C + 1 : 1;     // a block per plane's cover rows
-    FwdArgs a{ P, C, W, H, flags, g, features, out_color, out_invdepth, final_T, n_contrib, composite_slots(flags, V, P),
+    FwdArgs a{ P, C, W, H, flags, g, c.g.features, c.io.out_color, c.io.out_invdepth, c.final_T, c.n_contrib, composite_slots(flags, V, P),
                ((1u << 20) + (unsigned)C) / (unsigned)(C + 1), 0, (!small || (g.cover && cover_per_plane(P, W, H, C))) ? 1 : 0,
                fill_w_magic(W) };
-    const int cg = pick_cg(C);
     // Plain small-path forward with cover rows: the geometry launch zeroes the last `early` planes (launch_geom_fill), the fill +
     // composite launch streams the planes in front of them, and ONE kind-0 scope spans both -- the time in which every byte of the
     // output was written.  Not for sks_forward_backward (its geom_done event fires when the geometry records exist, not when
@@ -506,39 +585,24 @@ int forward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, con
     // the small path, and where this launch is a kind-0 sample whose prefilling launches were not bracketed (the hook was enabled
     // in between): a sample is the time in which EVERY byte of the output was written.
     int pre = 0;
-    if (prefilled > 0 && small && !hook && !final_T && !n_contrib && !(flags & SKS_DEBUG_SYNC) &&
+    if (prefilled > 0 && small && !hook && !c.final_T && !c.n_contrib && !(flags & SKS_DEBUG_SYNC) &&
         !(prof_next_forward_sampled() && !prof_has_parked(st)))
         pre = prefilled;
     const int zp = planes - pre;
     int early = 0;
-    if (small && !hook && g.cover && !final_T && !n_contrib && !(flags & (SKS_DEBUG_SYNC | SKS_NO_EARLY_FILL))) {
+    if (small && !hook && g.cover && !c.final_T && !c.n_contrib && !(flags & (SKS_DEBUG_SYNC | SKS_NO_EARLY_FILL))) {
         early = early_fill_planes(flags, planes, HW * 4);
         if (early > zp) early = zp;
     }
     int efs = 0, epb = 0;
     if (early > 0 && early_fill_cut(a, V, gy, gplanes, zp - early, zp, efs, epb)) {
         ProfScope prof(0, st, true, pre > 0);
-        launch_geom_fill(a, V, gy, gplanes, zp - early, zp, efs, epb, vt, viewmatrix, projmatrix, means3D, opacities, scales, rotations,
-                         cov3D_precomp, scale_modifier, radii, st, prof);
-        switch (cg) {
-            case 4: launch_fwd_small<4>(a, V, gy, zp - early, st, prof); break;
-            case 16: launch_fwd_small<16>(a, V, gy, zp - early, st, prof); break;
-            case 20: launch_fwd_small<20>(a, V, gy, zp - early, st, prof); break;
-            default: launch_fwd_small<32>(a, V, gy, zp - early, st, prof); break;
-        }
+        launch_geom_fill(a, c, gy, gplanes, zp - early, zp, efs, epb, vt, prof);
+        with_cg(C, [&](auto cg) { launch_fwd_small<decltype(cg)::value>(a, V, gy, zp - early, st, prof); });
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    if (hook && small && hook->geom_done)
-        hipExtLaunchKernelGGL(k_geom_fwd, dim3((P + gthreads - 1) / gthreads, V, gplanes), dim3(gthreads), 0, st, nullptr, hook->geom_done, 0,
-                              P, W, H, vt, viewmatrix, projmatrix, means3D, opacities, scales, rotations, cov3D_precomp, scale_modifier,
-                              flags, g, radii, 0, (uint32_t*)nullptr, (uint32_t*)nullptr, features, C, (uint2*)nullptr, (uint32_t*)nullptr,
-                              cover_per_plane(P, W, H, C) ? 1 : 0);
-    else
-    hipLaunchKernelGGL(k_geom_fwd, dim3((P + gthreads - 1) / gthreads, V, gplanes), dim3(gthreads), 0, st, P, W, H, vt, viewmatrix, projmatrix,
-                       means3D, opacities, scales, rotations, cov3D_precomp, scale_modifier, flags, g, radii, 0,
-                       small ? (uint32_t*)nullptr : b.count, small ? (uint32_t*)nullptr : b.touched, features, C,
-                       small ? (uint2*)nullptr : b.fmask, small ? (uint32_t*)nullptr : b.hdr, (small && cover_per_plane(P, W, H, C)) ? 1 : 0);
+    launch_geom_fwd(c, vt, g, b, small, gplanes, (hook && small) ? hook->geom_done : nullptr);
     STAGE_CHECK("geometry");
     if (hook && small && hook->after_geom) {   // (sks_forward_backward: the backward behind the geometry, on its own stream)
         if (int rc = hook->after_geom(hook->ctx)) return rc;
@@ -547,12 +611,7 @@ int forward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, con
     if (small) {
         {
             ProfScope prof(0, st, true, pre > 0);
-            switch (cg) {
-                case 4: launch_fwd_small<4>(a, V, gy, zp, st, prof); break;
-                case 16: launch_fwd_small<16>(a, V, gy, zp, st, prof); break;
-                case 20: launch_fwd_small<20>(a, V, gy, zp, st, prof); break;
-                default: launch_fwd_small<32>(a, V, gy, zp, st, prof); break;
-            }
+            with_cg(C, [&](auto cg) { launch_fwd_small<decltype(cg)::value>(a, V, gy, zp, st, prof); });
         }
         STAGE_CHECK("render(small)");
         return 0;
@@ -566,7 +625,7 @@ int forward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, con
         const int bpc = bin_scan_bands(gx);
         const int nchunk_t = (gy + bpc - 1) / bpc, nchunk_g = (P + SCAN_G - 1) / SCAN_G;
         hipLaunchKernelGGL(k_bin_scan, dim3(nchunk_t + nchunk_g, V), dim3(SCAN_T), (size_t)bpc * cw * 4, st, P, gx, gy, cw, bpc,
-                           nchunk_t, bin_capacity, b, cover, num_rendered_dev, V, C + 1, vg);
+                           nchunk_t, bin_capacity, b, cover, c.io.num_rendered_dev, V, C + 1, vg);
     }
     hipLaunchKernelGGL(k_bin_band_scatter, dim3(gy, V), dim3(BAND_TS), (size_t)2 * gx * 4, st, P, gx, bin_capacity, g, b, C, cw);
     STAGE_CHECK("binning");
@@ -592,12 +651,7 @@ int forward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, con
             bv.e_ids += (size_t)v0 * bin_capacity;
             bv.part += (size_t)v0 * bin_capacity * BIN_ROWS * NACC;
             const uint32_t* cov_g = cover + (size_t)v0 * (C + 1) * gy * cw;
-            switch (cg) {
-                case 4: launch_fwd_binned<4>(ag, bv, nv, gx, gy, cov_g, st); break;
-                case 16: launch_fwd_binned<16>(ag, bv, nv, gx, gy, cov_g, st); break;
-                case 20: launch_fwd_binned<20>(ag, bv, nv, gx, gy, cov_g, st); break;
-                default: launch_fwd_binned<32>(ag, bv, nv, gx, gy, cov_g, st); break;
-            }
+            with_cg(C, [&](auto cg) { launch_fwd_binned<decltype(cg)::value>(ag, bv, nv, gx, gy, cov_g, st); });
             if (hook && hook->after_group)
                 if (int rc = hook->after_group(hook->ctx, gi, v0, nv)) return rc;
         }
@@ -606,60 +660,37 @@ int forward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, con
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int sks_forward(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
-                const float* tanfovx, const float* tanfovy, const float* means3D, const float* features,
-                const float* opacities, const float* scales, const float* rotations, const float* cov3D_precomp,
-                float scale_modifier, unsigned flags, float* out_color, float* out_invdepth, int* radii, void* geom,
-                void* binning, size_t bin_capacity, int* num_rendered_dev, float* final_T, uint32_t* n_contrib,
-                void* stream)
-{
-    return forward_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, means3D, features, opacities, scales, rotations,
-                        cov3D_precomp, scale_modifier, flags, out_color, out_invdepth, radii, geom, binning, bin_capacity,
-                        num_rendered_dev, final_T, n_contrib, stream, nullptr);
-}
-
-}  // extern "C"
-
-namespace {
-
 // sks_backward in two phases, so that sks_forward_backward can place them: BWD_RENDER = the compositing backward (binned path:
 // of view group `group`, or of every group in turn when group < 0), BWD_GEOM = the geometry backward behind it (binned path: of
 // view group `group`'s views, or of all views when group < 0).
 constexpr unsigned BWD_RENDER = 1u, BWD_GEOM = 2u;
-int backward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
-                  const float* tanfovx, const float* tanfovy, const float* bg, const float* means3D,
-                  const float* features, const float* opacities, const float* scales, const float* rotations,
-                  const float* cov3D_precomp, float scale_modifier, unsigned flags, const int* radii, const void* geom,
-                  const void* binning, size_t bin_capacity, const float* dL_dout_color, const float* dL_dout_invdepth,
-                  void* accum, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dopacity, float* dL_dscales,
-                  float* dL_drotations, float* dL_dcov3D, float* dL_dfeatures, float* dL_dmeans3D_mean, void* stream,
-                  unsigned phases, int group, const PrefillReq* pre = nullptr)
+int backward_impl(const BwdCall& c, unsigned phases, int group, const PrefillReq* pre)
 {
-    if (int rc = check_common(V, P, C, W, H)) return rc;
+    const Cameras& cam = c.cam;
+    const int V = cam.V, P = cam.P, C = cam.C, W = cam.W, H = cam.H;
+    const unsigned flags = c.g.flags;
+    const Grads& gr = c.grads;
+    if (int rc = check_common(cam)) return rc;
     if (P == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (!viewmatrix || !projmatrix || !tanfovx || !tanfovy || !means3D || !features || !opacities || !radii ||
-        !geom || !dL_dout_color || !accum || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacity)
-        return fail(-2, "missing required pointer");
-    if (!cov3D_precomp && (!scales || !rotations)) return fail(-2, "need scales+rotations or cov3D_precomp");
+    const hipStream_t st = c.stream;
+    if (int rc = require({ cam.viewmatrix, cam.projmatrix, cam.tanfovx, cam.tanfovy, c.g.means3D, c.g.features, c.g.opacities, c.radii, c.geom,
+                           c.up.dL_dout_color, c.up.accum, gr.dL_dmeans3D, gr.dL_dmeans2D, gr.dL_dopacity }))
+        return rc;
+    if (int rc = need_cov(c.g.scales, c.g.rotations, c.g.cov3D_precomp)) return rc;
     ViewTan vt;
     ViewOff vo;
-    fill_views(vt, &vo, V, C, W, H, tanfovx, tanfovy, nullptr, nullptr);
-    Geom g = geom_from(const_cast<void*>(geom), V, P, W, H);
-    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE, NT = gx * gy;
-    BwdArgs a{ P, C, W, H, flags, g, features, bg, dL_dout_color, dL_dout_invdepth, (float*)accum, nullptr, nullptr };
-    const int cg = pick_cg(C);
-    const bool dfeat = dL_dfeatures != nullptr;
-    const bool small = P <= SKS_SMALL_P && !(flags & SKS_FORCE_BINNED);
+    fill_views(vt, &vo, V, C, W, H, cam.tanfovx, cam.tanfovy, nullptr, nullptr);
+    Geom g = geom_from(const_cast<void*>(c.geom), V, P, W, H);
+    const TileGrid t(W, H);
+    const int gx = t.gx, NT = t.NT;
+    BwdArgs a{ P, C, W, H, flags, g, c.g.features, c.bg, c.up.dL_dout_color, c.up.dL_dout_invdepth, (float*)c.up.accum, nullptr, nullptr };
+    const bool dfeat = gr.dL_dfeatures != nullptr;
+    const bool small = is_small(P, flags);
     int vg = V, ng = 1;
     if (!small) bin_groups(flags, V, vg, ng);
     if (group >= ng) return fail(-1, "view group %d of %d", group, ng);
     // the geometry backward of all views in one workgroup (with the mean over the views): the launch that can carry planes_geom
-    const bool geom_all = dL_dmeans3D_mean && V * P <= 256 && small;
+    const bool geom_all = gr.dL_dmeans3D_mean && V * P <= 256 && small;
     PreFill pfw{}, pfg{};
     bool have_pfw = false, have_pfg = false;
     if (pre && pre->planes_wave + pre->planes_geom > 0) {
@@ -683,23 +714,18 @@ int backward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, co
     if ((phases & BWD_RENDER) && small) {
         ProfScope prof(1, st, true);
         const PreFill* pf = have_pfw ? &pfw : nullptr;
-        switch (cg) {
-            case 4: launch_bwd_small<4>(a, vt, vo, V, gy, dfeat, st, prof, pf); break;
-            case 16: launch_bwd_small<16>(a, vt, vo, V, gy, dfeat, st, prof, pf); break;
-            case 20: launch_bwd_small<20>(a, vt, vo, V, gy, dfeat, st, prof, pf); break;
-            default: launch_bwd_small<32>(a, vt, vo, V, gy, dfeat, st, prof, pf); break;
-        }
+        with_cg(C, [&](auto cg) { launch_bwd_small<decltype(cg)::value>(a, vt, vo, V, dfeat, st, prof, pf); });
         STAGE_CHECK("render-backward(small)");
     } else if (phases & BWD_RENDER) {
-        if (!binning) return fail(-2, "binned path needs the forward's binning buffer");
-        Bin b = bin_from(const_cast<void*>(binning), V, P, NT, bin_capacity);
-        BinView bv = bin_view(b, NT, bin_capacity);
+        if (!c.binning) return fail(-2, "binned path needs the forward's binning buffer");
+        Bin b = bin_from(const_cast<void*>(c.binning), V, P, NT, c.bin_capacity);
+        BinView bv = bin_view(b, NT, c.bin_capacity);
         // the per-Gaussian sums go through the slot rows of the binning scratch (plain stores, every row written); only the
         // feature gradient, when wanted, is accumulated with atomics
-        if (dfeat && group <= 0) HIP_TRY(hipMemsetAsync(accum, 0, (size_t)V * P * (NACC + C) * sizeof(float), st));
+        if (dfeat && group <= 0) HIP_TRY(hipMemsetAsync(c.up.accum, 0, (size_t)V * P * (NACC + C) * sizeof(float), st));
         dim3 grid(bwd_tile_blocks());
-        const unsigned magic_nt = (unsigned)(((1ull << 32) + (unsigned)NT - 1) / (unsigned)NT), magic_gx = (unsigned)(((1ull << 32) + (unsigned)gx - 1) / (unsigned)gx);
-        const bool extra = bg != nullptr || dL_dout_invdepth != nullptr;
+        const unsigned magic_nt = magic32((unsigned)NT), magic_gx = magic32((unsigned)gx);
+        const bool extra = c.bg != nullptr || c.up.dL_dout_invdepth != nullptr;
         for (int gi = group < 0 ? 0 : group; gi < (group < 0 ? ng : group + 1); gi++) {
             // a view group's tiles: its stretch of every class's descriptor region, its class counters (k_bin_scan)
             const uint4* tl = b.tlist + (size_t)gi * vg * NT;
@@ -712,20 +738,20 @@ int backward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, co
         STAGE_CHECK("render-backward(binned)");
     }
     if (!(phases & BWD_GEOM)) return 0;
-    GeomBwdArgs ga{ P, C, W, H, flags, viewmatrix, projmatrix, means3D, opacities, scales, rotations, cov3D_precomp,
-                    scale_modifier, radii, (const float*)accum, small ? BWD_SPLITS : 0, nullptr, nullptr, nullptr, dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dscales,
-                    dL_drotations, dL_dcov3D, dL_dfeatures };
+    GeomBwdArgs ga{ P, C, W, H, flags, cam.viewmatrix, cam.projmatrix, c.g.means3D, c.g.opacities, c.g.scales, c.g.rotations, c.g.cov3D_precomp,
+                    c.g.scale_modifier, c.radii, (const float*)c.up.accum, small ? BWD_SPLITS : 0, nullptr, nullptr, nullptr, gr.dL_dmeans3D, gr.dL_dmeans2D,
+                    gr.dL_dopacity, gr.dL_dscales, gr.dL_drotations, gr.dL_dcov3D, gr.dL_dfeatures };
     if (!small) {
-        Bin b = bin_from(const_cast<void*>(binning), V, P, NT, bin_capacity);
+        Bin b = bin_from(const_cast<void*>(c.binning), V, P, NT, c.bin_capacity);
         ga.rect = g.rect;
         ga.goff = b.goff;
         ga.part = b.part;
-        ga.cap = bin_capacity;
+        ga.cap = c.bin_capacity;
         ga.bin_hdr = b.hdr;
     }
     if (geom_all) {   // (the binned path's k_geom_bwd also re-arms the work cursors)
-        if (have_pfg) hipLaunchKernelGGL((k_geom_bwd_all<PreFill>), dim3(1u + pfg.nfill), dim3(256), 0, st, ga, vt, V, dL_dmeans3D_mean, pfg);
-        else hipLaunchKernelGGL((k_geom_bwd_all<>), dim3(1), dim3(256), 0, st, ga, vt, V, dL_dmeans3D_mean);
+        if (have_pfg) hipLaunchKernelGGL((k_geom_bwd_all<PreFill>), dim3(1u + pfg.nfill), dim3(256), 0, st, ga, vt, V, gr.dL_dmeans3D_mean, pfg);
+        else hipLaunchKernelGGL((k_geom_bwd_all<>), dim3(1), dim3(256), 0, st, ga, vt, V, gr.dL_dmeans3D_mean);
     } else {
         if (small) hipLaunchKernelGGL(k_geom_bwd, dim3((P + 255) / 256, V), dim3(256), 0, st, ga, vt);
         else {
@@ -734,17 +760,112 @@ int backward_impl(int V, int P, int C, int W, int H, const float* viewmatrix, co
             hipLaunchKernelGGL(k_geom_bwd_binned, dim3((P + GEOMB_G - 1) / GEOMB_G, nv), dim3(256), 0, st, ga, vt);
         }
         // (the mean over the views wants every view's gradients: with view groups, behind the last group's geometry backward)
-        if (dL_dmeans3D_mean && (small || group < 0 || group == ng - 1))
-            hipLaunchKernelGGL(k_mean_views, dim3((3 * P + 255) / 256), dim3(256), 0, st, V, P, dL_dmeans3D, dL_dmeans3D_mean);
+        if (gr.dL_dmeans3D_mean && (small || group < 0 || group == ng - 1))
+            hipLaunchKernelGGL(k_mean_views, dim3((3 * P + 255) / 256), dim3(256), 0, st, V, P, gr.dL_dmeans3D, gr.dL_dmeans3D_mean);
     }
     if (have_pfw || have_pfg) prof_park_end(st);
     STAGE_CHECK("geometry-backward");
     return 0;
 }
 
+// What the _dv entries of the fused step put where the host arrays of the plain ones stand:
+const float NO_TAN[SKS_MAX_VIEWS] = {};                  // the by-value record carries the sizes only
+const double NO_SCHED[5] = { 1.0, 1.0, 1.0, 0.0, 1.0 };  // every frame's schedule is read in the kernel
+// sks_loop_fused_step{,_es,_dv,_es_dv}: the same two launches; with a criterion (c.es.es_state) in the early-stopping instantiations
+// of both kernels.  c.views_dev (the _dv entries): the tail reads the per-view scalars from that device table and frame f's LR
+// schedule from row f of c.lr_sched_dev; the compositing backward reads only the views' SIZES, which stay in its argument
+// segment (view_wh: fixed per view slot)
+int loop_fused_step_impl(const StepCall& c)
+{
+    const Cameras& cam = c.cam;
+    const sksloop::Optimiser& opt = c.opt;
+    const int V = cam.V, P = cam.P, C = cam.C, W = cam.W, H = cam.H, frames = c.hm.frames;
+    const float* const* const hm_factors = c.hm.hm_factors;
+    if (int rc = check_common(cam)) return rc;
+    if (P < 1 || P > 64) return fail(-1, "fused step needs 1 <= P <= 64 (got %d)", P);
+    if (int rc = check_frames(V, frames)) return rc;
+    const int Vf = V / frames;   // views of one frame: the optimiser's V (slots, group mask, last_view are per frame)
+    if (int rc = require({ cam.viewmatrix, cam.projmatrix, cam.tanfovx, cam.tanfovy, c.r.features, c.r.radii, c.r.geom,
+                           c.r.gt ? (const void*)c.r.gt : (const void*)hm_factors, c.r.gt_totals, c.r.accum, c.r.loss_sums, c.r.packed }))
+        return rc;
+    if (int rc = check_hm_factors(hm_factors)) return rc;
+    const hipStream_t st = c.stream;
+    ViewTan vt;
+    ViewOff vo;
+    if (!fill_views(vt, &vo, V, C, W, H, cam.tanfovx, cam.tanfovy, c.hm.view_wh, c.hm.gt_offsets)) return bad_view_wh();
+    if (int rc = check_wh_offsets(hm_factors, c.hm.view_wh, c.hm.gt_offsets)) return rc;
+    const unsigned flags = c.r.flags | SKS_RAW_PARAMS | SKS_CLAMP01;
+    sksloop::AdamArgs aa;
+    if (const char* err = sksloop::fill_adam_args(aa, Vf, P, c.r.packed, opt)) return fail(-2, "%s", err);
+    const bool es = c.es.es_state != nullptr;
+    if (es) { aa.es_state = c.es.es_state; aa.es_window = c.es.es_window; aa.es_tol = c.es.es_tolerance; aa.es_host_flag = c.es.es_host_flags; }
+    Geom g = geom_from(c.r.geom, V, P, W, H);
+    g.cover = nullptr;   // no forward render on this path
+    BwdArgs a{ P, C, W, H, flags, g, c.r.features, nullptr, c.r.gt, nullptr, (float*)c.r.accum, nullptr, nullptr };
+    if (hm_factors) { a.hm_row = hm_factors[0]; a.hm_col = hm_factors[1]; a.hm_cmin = hm_factors[2]; a.hm_den = hm_factors[3]; }
+    if (es) { a.es_stop = c.es.es_state + 1; a.es_stride = 2 + 2 * c.es.es_window; a.es_views = Vf; }
+    {
+        ProfScope prof(1, st);
+        if (!es) launch_bwd_loss(a, vt, vo, V, st);
+        else launch_bwd_loss<true>(a, vt, vo, V, st);
+    }
+    STAGE_CHECK("render-backward(fused loss)");
+    GeomBwdArgs ga{ P, C, W, H, flags, cam.viewmatrix, cam.projmatrix, opt.xyz, opt.opacity, opt.scaling, opt.rotation, nullptr, c.r.scale_modifier,
+                    c.r.radii, (const float*)c.r.accum, BWD_SPLITS, c.r.gt_totals, c.r.loss_sums, c.r.packed, nullptr, nullptr, nullptr, nullptr,
+                    nullptr, nullptr, nullptr };
+    if (c.views_dev) {
+        const ViewTanDev vd = views_dev_from(c.views_dev, c.lr_sched_dev);
+        if (es) hipLaunchKernelGGL((k_step_tail<true, ViewTanDev>), dim3(frames), dim3(256), 0, st, ga, vd, aa, Vf, g, c.r.radii);
+        else hipLaunchKernelGGL((k_step_tail<false, ViewTanDev>), dim3(frames), dim3(256), 0, st, ga, vd, aa, Vf, g, c.r.radii);
+    } else if (es) hipLaunchKernelGGL(k_step_tail<true>, dim3(frames), dim3(256), 0, st, ga, vt, aa, Vf, g, c.r.radii);
+    else hipLaunchKernelGGL(k_step_tail<false>, dim3(frames), dim3(256), 0, st, ga, vt, aa, Vf, g, c.r.radii);
+    STAGE_CHECK("step tail");
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+// An entry point's parameters carry the names of include/skelsplat_hip.h, and so do the records' fields: each macro fills one
+// block from the parameters of the SAME NAME (a parameter that is missing or misnamed does not compile).
+#define SKS_TAKE_CAMERAS(r)                                                                                                                    \
+    ((r).V = V, (r).P = P, (r).C = C, (r).W = W, (r).H = H, (r).viewmatrix = viewmatrix, (r).projmatrix = projmatrix, (r).tanfovx = tanfovx, (r).tanfovy = tanfovy)
+#define SKS_TAKE_GAUSSIANS(r)                                                                                                                  \
+    ((r).means3D = means3D, (r).features = features, (r).opacities = opacities, (r).scales = scales, (r).rotations = rotations,                \
+     (r).cov3D_precomp = cov3D_precomp, (r).scale_modifier = scale_modifier, (r).flags = flags)
+#define SKS_TAKE_FORWARD_IO(r)                                                                                                                 \
+    ((r).out_color = out_color, (r).out_invdepth = out_invdepth, (r).radii = radii, (r).geom = geom, (r).binning = binning,                    \
+     (r).bin_capacity = bin_capacity, (r).num_rendered_dev = num_rendered_dev)
+#define SKS_TAKE_UPSTREAM(r) ((r).dL_dout_color = dL_dout_color, (r).dL_dout_invdepth = dL_dout_invdepth, (r).accum = accum)
+#define SKS_TAKE_GRADS(r)                                                                                                                      \
+    ((r).dL_dmeans3D = dL_dmeans3D, (r).dL_dmeans2D = dL_dmeans2D, (r).dL_dopacity = dL_dopacity, (r).dL_dscales = dL_dscales,                 \
+     (r).dL_drotations = dL_drotations, (r).dL_dcov3D = dL_dcov3D, (r).dL_dfeatures = dL_dfeatures, (r).dL_dmeans3D_mean = dL_dmeans3D_mean)
+// (ft, nc: final_T / n_contrib, which sks_forward_backward does not have)
+#define SKS_TAKE_FWD_CALL(c, ft, nc) \
+    (SKS_TAKE_CAMERAS((c).cam), SKS_TAKE_GAUSSIANS((c).g), SKS_TAKE_FORWARD_IO((c).io), (c).final_T = (ft), (c).n_contrib = (nc), (c).stream = (hipStream_t)stream)
+#define SKS_TAKE_BWD_CALL(c)                                                                                                                   \
+    (SKS_TAKE_CAMERAS((c).cam), (c).bg = bg, SKS_TAKE_GAUSSIANS((c).g), (c).radii = radii, (c).geom = geom, (c).binning = binning,             \
+     (c).bin_capacity = bin_capacity, SKS_TAKE_UPSTREAM((c).up), SKS_TAKE_GRADS((c).grads), (c).stream = (hipStream_t)stream)
+// (the fused step; the _dv entries: tanfovx = tanfovy = NO_TAN, sched = NO_SCHED, views_dev / lr_sched_dev set beside the macro)
+#define SKS_TAKE_STEP_CALL(c, sched)                                                                                                           \
+    (SKS_TAKE_CAMERAS((c).cam), (c).r.features = features, (c).r.scale_modifier = scale_modifier, (c).r.flags = flags, (c).r.radii = radii,    \
+     (c).r.geom = geom, (c).r.gt = gt, (c).r.gt_totals = gt_totals, (c).r.accum = accum, (c).r.loss_sums = loss_sums, (c).r.packed = packed,   \
+     SKS_TAKE_OPTIMISER((c).opt, sched), (c).hm.view_wh = view_wh, (c).hm.gt_offsets = gt_offsets, (c).hm.frames = frames,                     \
+     (c).hm.hm_factors = hm_factors, (c).stream = (hipStream_t)stream)
+#define SKS_TAKE_ES(r) ((r).es_state = es_state, (r).es_window = es_window, (r).es_tolerance = es_tolerance, (r).es_host_flags = es_host_flags)
+
+int sks_forward(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                const float* tanfovx, const float* tanfovy, const float* means3D, const float* features,
+                const float* opacities, const float* scales, const float* rotations, const float* cov3D_precomp,
+                float scale_modifier, unsigned flags, float* out_color, float* out_invdepth, int* radii, void* geom,
+                void* binning, size_t bin_capacity, int* num_rendered_dev, float* final_T, uint32_t* n_contrib,
+                void* stream)
+{
+    FwdCall c;
+    SKS_TAKE_FWD_CALL(c, final_T, n_contrib);
+    return forward_impl(c, nullptr, 0);
+}
 
 int sks_backward(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
                  const float* tanfovx, const float* tanfovy, const float* bg, const float* means3D,
@@ -754,10 +875,9 @@ int sks_backward(int V, int P, int C, int W, int H, const float* viewmatrix, con
                  void* accum, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dopacity, float* dL_dscales,
                  float* dL_drotations, float* dL_dcov3D, float* dL_dfeatures, float* dL_dmeans3D_mean, void* stream)
 {
-    return backward_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, bg, means3D, features, opacities, scales, rotations,
-                         cov3D_precomp, scale_modifier, flags, radii, geom, binning, bin_capacity, dL_dout_color, dL_dout_invdepth, accum,
-                         dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, dL_dfeatures, dL_dmeans3D_mean,
-                         stream, BWD_RENDER | BWD_GEOM, -1);
+    BwdCall c;
+    SKS_TAKE_BWD_CALL(c);
+    return backward_impl(c, BWD_RENDER | BWD_GEOM, -1, nullptr);
 }
 
 int sks_forward_prefilled(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
@@ -767,9 +887,9 @@ int sks_forward_prefilled(int V, int P, int C, int W, int H, const float* viewma
                           void* binning, size_t bin_capacity, int* num_rendered_dev, float* final_T, uint32_t* n_contrib,
                           int prefilled_planes, void* stream)
 {
-    return forward_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, means3D, features, opacities, scales, rotations,
-                        cov3D_precomp, scale_modifier, flags, out_color, out_invdepth, radii, geom, binning, bin_capacity,
-                        num_rendered_dev, final_T, n_contrib, stream, nullptr, prefilled_planes);
+    FwdCall c;
+    SKS_TAKE_FWD_CALL(c, final_T, n_contrib);
+    return forward_impl(c, nullptr, prefilled_planes);
 }
 
 int sks_backward_prefill(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
@@ -794,10 +914,9 @@ int sks_backward_prefill(int V, int P, int C, int W, int H, const float* viewmat
         if (!next_color || !next_invdepth) return fail(-2, "sks_backward_prefill: next_color / next_invdepth must be provided");
         if (((uintptr_t)next_color | (uintptr_t)next_invdepth) & 15u) return fail(-2, "next_color / next_invdepth must be 16-byte aligned");
     }
-    return backward_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, bg, means3D, features, opacities, scales, rotations,
-                         cov3D_precomp, scale_modifier, flags, radii, geom, binning, bin_capacity, dL_dout_color, dL_dout_invdepth, accum,
-                         dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, dL_dfeatures, dL_dmeans3D_mean,
-                         stream, BWD_RENDER | BWD_GEOM, -1, planes_wave + planes_geom > 0 ? &req : nullptr);
+    BwdCall c;
+    SKS_TAKE_BWD_CALL(c);
+    return backward_impl(c, BWD_RENDER | BWD_GEOM, -1, planes_wave + planes_geom > 0 ? &req : nullptr);
 }
 
 // The rule: how many of the call's last planes the small-path backward's two launches should zero for the next forward.  A function
@@ -853,34 +972,22 @@ int sks_forward_backward(int V, int P, int C, int W, int H, const float* viewmat
                          float* dL_dmeans2D, float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
                          float* dL_dfeatures, float* dL_dmeans3D_mean, void* stream, void* aux_stream, unsigned fb_flags)
 {
-    const bool small = P <= SKS_SMALL_P && !(flags & SKS_FORCE_BINNED);
+    const bool small = is_small(P, flags);
     // the binned path overlaps by VIEW GROUPS (the backward of a group starts from what the forward's compositor left per pixel of
     // ITS views); how many: bin_groups, as for sks_forward / sks_backward (the flags stay the caller's)
     int vg = V, ng = 1;
     if (!small && V >= 1) bin_groups(flags, V, vg, ng);
+    const hipStream_t st = (hipStream_t)stream, aux = (hipStream_t)aux_stream;
+    FwdCall fwd;
+    SKS_TAKE_FWD_CALL(fwd, nullptr, nullptr);
+    BwdCall bwd;
+    SKS_TAKE_BWD_CALL(bwd);
     struct Ctx {
-        int V, P, C, W, H;
-        const float *vm, *pm, *tx, *ty, *bg, *means, *feat, *opac, *scales, *rots, *cov;
-        float smod;
-        unsigned flags;
-        const int* radii;
-        const void *geom, *binning;
-        size_t cap;
-        const float *dL, *dLinv;
-        void* accum;
-        float *m3, *m2, *op, *sc, *rot, *dcov, *dfeat, *mean;
-        hipStream_t s, aux;
+        const BwdCall& bwd;   // the call's backward on the second stream
+        hipStream_t s;
         bool ext, handed;     // handed: the second stream holds work of this call
         int rc_aux;
-        int backward(unsigned phases, int group) const
-        {
-            return backward_impl(V, P, C, W, H, vm, pm, tx, ty, bg, means, feat, opac, scales, rots, cov, smod, flags, radii, geom, binning, cap,
-                                 dL, dLinv, accum, m3, m2, op, sc, rot, dcov, dfeat, mean, aux, phases, group);
-        }
-    } c{ V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, bg, means3D, features, opacities, scales, rotations, cov3D_precomp,
-         scale_modifier, flags, radii, geom, binning, bin_capacity, dL_dout_color, dL_dout_invdepth, accum, dL_dmeans3D, dL_dmeans2D,
-         dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, dL_dfeatures, dL_dmeans3D_mean, (hipStream_t)stream, (hipStream_t)aux_stream,
-         true, false, 0 };
+    } c{ bwd, st, true, false, 0 };
     {
         static const bool ext_off = [] { const char* e = getenv("SKS_FB_EXT"); return e && atoi(e) == 0; }();   // tuning
         if (ext_off) c.ext = false;
@@ -895,28 +1002,23 @@ int sks_forward_backward(int V, int P, int C, int W, int H, const float* viewmat
     if (!aux_stream || aux_stream == stream || P == 0 || (flags & SKS_DEBUG_SYNC) || (!small && ng < 2) || crowded) {
         // nothing to run side by side: one after the other on the caller's stream (the one-call form keeps its launch layout on
         // every route: no early fill)
-        if (int rc = forward_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, means3D, features, opacities, scales, rotations,
-                                  cov3D_precomp, scale_modifier, flags | SKS_NO_EARLY_FILL, out_color, out_invdepth, radii, geom, binning, bin_capacity,
-                                  num_rendered_dev, nullptr, nullptr, stream, nullptr))
-            return rc;
-        if (int rc = backward_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, bg, means3D, features, opacities, scales,
-                                   rotations, cov3D_precomp, scale_modifier, flags, radii, geom, binning, bin_capacity, dL_dout_color,
-                                   dL_dout_invdepth, accum, dL_dmeans3D, dL_dmeans2D, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D,
-                                   dL_dfeatures, dL_dmeans3D_mean, stream, BWD_RENDER | BWD_GEOM, -1))
-            return rc;
+        fwd.g.flags |= SKS_NO_EARLY_FILL;
+        if (int rc = forward_impl(fwd, nullptr, 0)) return rc;
+        if (int rc = backward_impl(bwd, BWD_RENDER | BWD_GEOM, -1, nullptr)) return rc;
         // SKS_FB_NO_JOIN: the caller enqueues what follows the gradients on aux_stream -- they must be ordered THERE on this branch
         // as on the overlapped ones (aux_stream waits for everything the call put on `stream`)
         if (no_join && aux_stream && aux_stream != stream) {
             FbEvents* ev = nullptr;
             if (int rc = fb_events(0, ev)) return rc;
-            HIP_TRY(hipEventRecord(ev->done, (hipStream_t)stream));
-            HIP_TRY(hipStreamWaitEvent((hipStream_t)aux_stream, ev->done, 0));
+            HIP_TRY(hipEventRecord(ev->done, st));
+            HIP_TRY(hipStreamWaitEvent(aux, ev->done, 0));
         }
         return 0;
     }
     FbEvents* evp = nullptr;
     if (int rc = fb_events(small ? 0 : ng, evp)) return rc;
     FbEvents& ev = *evp;
+    bwd.stream = aux;
     struct Run {
         // small path: behind the geometry kernel, i.e. behind everything the caller enqueued -- the whole backward
         static int after_geom(void* p)
@@ -924,9 +1026,9 @@ int sks_forward_backward(int V, int P, int C, int W, int H, const float* viewmat
             Ctx& k = *(Ctx*)p;
             FbEvents& e = tl_fb_events;
             if (!k.ext) HIP_TRY(hipEventRecord(e.geom, k.s));   // (else it rode on k_geom_fwd's dispatch)
-            HIP_TRY(hipStreamWaitEvent(k.aux, e.geom, 0));
+            HIP_TRY(hipStreamWaitEvent(k.bwd.stream, e.geom, 0));
             k.handed = true;
-            return k.rc_aux = k.backward(BWD_RENDER | BWD_GEOM, -1);
+            return k.rc_aux = backward_impl(k.bwd, BWD_RENDER | BWD_GEOM, -1, nullptr);
         }
         // binned path: view group g's forward is enqueued -- its compositing and geometry backward go to the second stream, where
         // they run beside the forward of group g + 1
@@ -935,22 +1037,20 @@ int sks_forward_backward(int V, int P, int C, int W, int H, const float* viewmat
             Ctx& k = *(Ctx*)p;
             FbEvents& e = tl_fb_events;
             HIP_TRY(hipEventRecord(e.grp[g], k.s));
-            HIP_TRY(hipStreamWaitEvent(k.aux, e.grp[g], 0));
+            HIP_TRY(hipStreamWaitEvent(k.bwd.stream, e.grp[g], 0));
             k.handed = true;
-            return k.rc_aux = k.backward(BWD_RENDER | BWD_GEOM, g);
+            return k.rc_aux = backward_impl(k.bwd, BWD_RENDER | BWD_GEOM, g, nullptr);
         }
     };
     const FwdHook hook{ (small && c.ext) ? ev.geom : nullptr, small ? &Run::after_geom : nullptr, small ? nullptr : &Run::after_group, &c };
-    int rc = forward_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, means3D, features, opacities, scales, rotations,
-                          cov3D_precomp, scale_modifier, flags, out_color, out_invdepth, radii, geom, binning, bin_capacity,
-                          num_rendered_dev, nullptr, nullptr, stream, &hook);
+    int rc = forward_impl(fwd, &hook, 0);
     if (rc == 0 && !c.handed) rc = fail(-3, "sks_forward_backward: the forward did not reach the point the backward starts from");
     // The gradients are the caller's in stream order -- unless the caller has more to enqueue behind the backward on aux_stream
     // (a view-sharded step's collective: hidden under the forward as well) and joins the two streams itself.  After an ERROR
     // behind the hand-over the join is made whatever the caller asked for: what the second stream already holds reads `geom` and
     // writes the gradient tensors, and the caller's stream must not run ahead of it.
     if (c.handed && (!no_join || rc != 0)) {
-        const hipError_t e1 = hipEventRecord(ev.done, c.aux);
+        const hipError_t e1 = hipEventRecord(ev.done, aux);
         const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(c.s, ev.done, 0) : e1;
         if (rc == 0 && e2 != hipSuccess) rc = fail((int)e2, "sks_forward_backward: joining the two streams: %s", hipGetErrorString(e2));
     }
@@ -973,7 +1073,7 @@ int sks_gt_tile_stats(int V, int C, int W, int H, const float* gt, float* tile_S
     if (!gt || !totals) return fail(-2, "gt_tile_stats: missing pointer");
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(totals, 0, (size_t)V * 2 * sizeof(double), st));
-    dim3 grid((H + TILE - 1) / TILE, C, V);
+    dim3 grid(TileGrid(W, H).gy, C, V);
     hipLaunchKernelGGL(k_gt_tile_stats, grid, dim3(256), 0, st, C, W, H, gt, tile_S, tile_N, totals);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -992,24 +1092,21 @@ int sks_backward_fused_loss(int V, int P, int C, int W, int H, const float* view
     if (int rc = check_common(V, P, C, W, H)) return rc;
     if (P < 1 || P > 64) return fail(-1, "fused-loss backward needs 1 <= P <= 64 (got %d)", P);
     hipStream_t st = (hipStream_t)stream;
-    if (!viewmatrix || !projmatrix || !tanfovx || !tanfovy || !means3D || !features || !opacities || !radii || !geom ||
-        (!gt && !hm_factors) || !gt_totals || !accum || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacity || !loss_sums)
-        return fail(-2, "missing required pointer");
-    if (hm_factors && (!hm_factors[0] || !hm_factors[1] || !hm_factors[2] || !hm_factors[3]))
-        return fail(-2, "hm_factors: row, col, cmin, den must all be given");
-    if (!cov3D_precomp && (!scales || !rotations)) return fail(-2, "need scales+rotations or cov3D_precomp");
+    if (int rc = require({ viewmatrix, projmatrix, tanfovx, tanfovy, means3D, features, opacities, radii, geom,
+                           gt ? (const void*)gt : (const void*)hm_factors, gt_totals, accum, dL_dmeans3D, dL_dmeans2D, dL_dopacity, loss_sums }))
+        return rc;
+    if (int rc = check_hm_factors(hm_factors)) return rc;
+    if (int rc = need_cov(scales, rotations, cov3D_precomp)) return rc;
     ViewTan vt;
     ViewOff vo;
-    if (!fill_views(vt, &vo, V, C, W, H, tanfovx, tanfovy, view_wh, gt_offsets))
-        return fail(-1, "view_wh: every view's size must be within [1, W] x [1, H] (pass the largest as W, H)");
-    if (!hm_factors && (view_wh != nullptr) != (gt_offsets != nullptr)) return fail(-2, "view_wh and gt_offsets go together");
+    if (!fill_views(vt, &vo, V, C, W, H, tanfovx, tanfovy, view_wh, gt_offsets)) return bad_view_wh();
+    if (int rc = check_wh_offsets(hm_factors, view_wh, gt_offsets)) return rc;
     Geom g = geom_from(const_cast<void*>(geom), V, P, W, H);
     BwdArgs a{ P, C, W, H, flags | SKS_CLAMP01, g, features, bg, gt, nullptr, (float*)accum, tile_S, tile_N };
     if (hm_factors) { a.hm_row = hm_factors[0]; a.hm_col = hm_factors[1]; a.hm_cmin = hm_factors[2]; a.hm_den = hm_factors[3]; }
-    dim3 grid(P, V, bwd_wave_groups(V, P, flags));   // see launch_bwd_small
     {
         ProfScope prof(1, st);
-        launch_bwd_loss(a, vt, vo, grid, pick_cg(C), st);
+        launch_bwd_loss(a, vt, vo, V, st);
     }
     STAGE_CHECK("fused loss + render-backward");
     GeomBwdArgs ga{ P, C, W, H, flags, viewmatrix, projmatrix, means3D, opacities, scales, rotations, cov3D_precomp,
@@ -1027,14 +1124,12 @@ int sks_geometry(int V, int P, int C, int W, int H, const float* viewmatrix, con
 {
     if (int rc = check_common(V, P, C, W, H)) return rc;
     if (P < 1) return fail(-1, "P must be positive");
-    if (frames < 1 || V % frames) return fail(-1, "frames must divide the number of views (V = %d, frames = %d)", V, frames);
-    if (!viewmatrix || !projmatrix || !tanfovx || !tanfovy || !means3D || !opacities || !radii || !geom)
-        return fail(-2, "missing required pointer");
-    if (!cov3D_precomp && (!scales || !rotations)) return fail(-2, "need scales+rotations or cov3D_precomp");
+    if (int rc = check_frames(V, frames)) return rc;
+    if (int rc = require({ viewmatrix, projmatrix, tanfovx, tanfovy, means3D, opacities, radii, geom })) return rc;
+    if (int rc = need_cov(scales, rotations, cov3D_precomp)) return rc;
     hipStream_t st = (hipStream_t)stream;
     ViewTan vt;
-    if (!fill_views(vt, nullptr, V, C, W, H, tanfovx, tanfovy, view_wh, nullptr))
-        return fail(-1, "view_wh: every view's size must be within [1, W] x [1, H] (pass the largest as W, H)");
+    if (!fill_views(vt, nullptr, V, C, W, H, tanfovx, tanfovy, view_wh, nullptr)) return bad_view_wh();
     Geom g = geom_from(geom, V, P, W, H);
     g.cover = nullptr;   // (the cover rows serve the dense forward: sks_forward makes its own)
     hipLaunchKernelGGL(k_geom_fwd, dim3((P + 255) / 256, V), dim3(256), 0, st, P, W, H, vt, viewmatrix, projmatrix,
@@ -1051,10 +1146,9 @@ int sks_geometry_dv(int V, int P, int C, int W, int H, const float* viewmatrix, 
 {
     if (int rc = check_common(V, P, C, W, H)) return rc;
     if (P < 1) return fail(-1, "P must be positive");
-    if (frames < 1 || V % frames) return fail(-1, "frames must divide the number of views (V = %d, frames = %d)", V, frames);
-    if (!viewmatrix || !projmatrix || !views_dev || !means3D || !opacities || !radii || !geom)
-        return fail(-2, "missing required pointer");
-    if (!cov3D_precomp && (!scales || !rotations)) return fail(-2, "need scales+rotations or cov3D_precomp");
+    if (int rc = check_frames(V, frames)) return rc;
+    if (int rc = require({ viewmatrix, projmatrix, views_dev, means3D, opacities, radii, geom })) return rc;
+    if (int rc = need_cov(scales, rotations, cov3D_precomp)) return rc;
     hipStream_t st = (hipStream_t)stream;
     Geom g = geom_from(geom, V, P, W, H);
     g.cover = nullptr;
@@ -1065,72 +1159,7 @@ int sks_geometry_dv(int V, int P, int C, int W, int H, const float* viewmatrix, 
     return 0;
 }
 
-// sks_loop_fused_step and (es_state != nullptr) sks_loop_fused_step_es: the same two launches, the latter in the early-stopping
-// instantiations of both kernels.  views_dev != nullptr (the _dv entries): the tail reads the per-view scalars from that device
-// table and frame f's LR schedule from row f of lr_sched_dev; the compositing backward reads only the views' SIZES, which stay
-// in its argument segment (view_wh: fixed per view slot)
-static int loop_fused_step_impl(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
-                                const float* tanfovx, const float* tanfovy, const float* features, float scale_modifier,
-                                unsigned flags, int* radii, void* geom, const float* gt, const double* gt_totals, void* accum,
-                                double* loss_sums, float* packed, float* slots, unsigned long long group_mask, int last_view,
-                                float* xyz, float* scaling, float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq,
-                                int* counters, int acc_steps, const double* lr_sched, const double* lrs, const double* adam,
-                                float lambda_consistency, const int* limb, const int* view_wh, const size_t* gt_offsets,
-                                int frames, const float* const* hm_factors, int* es_state, int es_window, float es_tolerance,
-                                int* es_host_flags, void* stream, const void* views_dev = nullptr,
-                                const double* lr_sched_dev = nullptr)
-{
-    if (int rc = check_common(V, P, C, W, H)) return rc;
-    if (P < 1 || P > 64) return fail(-1, "fused step needs 1 <= P <= 64 (got %d)", P);
-    static const float no_tan[SKS_MAX_VIEWS] = {};                  // _dv: the by-value record carries the sizes only
-    static const double no_sched[5] = { 1.0, 1.0, 1.0, 0.0, 1.0 };  // _dv: every frame's schedule is read in the kernel
-    if (views_dev) { tanfovx = tanfovy = no_tan; lr_sched = no_sched; }
-    if (frames < 1 || V % frames) return fail(-1, "frames must divide the number of views (V = %d, frames = %d)", V, frames);
-    const int Vf = V / frames;   // views of one frame: the optimiser's V (slots, group mask, last_view are per frame)
-    if (!viewmatrix || !projmatrix || !tanfovx || !tanfovy || !features || !radii || !geom || (!gt && !hm_factors) || !gt_totals ||
-        !accum || !loss_sums || !packed)
-        return fail(-2, "missing required pointer");
-    if (hm_factors && (!hm_factors[0] || !hm_factors[1] || !hm_factors[2] || !hm_factors[3]))
-        return fail(-2, "hm_factors: row, col, cmin, den must all be given");
-    hipStream_t st = (hipStream_t)stream;
-    ViewTan vt;
-    ViewOff vo;
-    if (!fill_views(vt, &vo, V, C, W, H, tanfovx, tanfovy, view_wh, gt_offsets))
-        return fail(-1, "view_wh: every view's size must be within [1, W] x [1, H] (pass the largest as W, H)");
-    if (!hm_factors && (view_wh != nullptr) != (gt_offsets != nullptr)) return fail(-2, "view_wh and gt_offsets go together");
-    flags |= SKS_RAW_PARAMS | SKS_CLAMP01;
-    sksloop::AdamArgs aa;
-    if (const char* err = sksloop::fill_adam_args(aa, Vf, P, packed, slots, group_mask, last_view, xyz, scaling, rotation, opacity,
-                                                  exp_avg, exp_avg_sq, counters, acc_steps, lr_sched, lrs, adam,
-                                                  lambda_consistency, limb))
-        return fail(-2, "%s", err);
-    const bool es = es_state != nullptr;
-    if (es) { aa.es_state = es_state; aa.es_window = es_window; aa.es_tol = es_tolerance; aa.es_host_flag = es_host_flags; }
-    Geom g = geom_from(geom, V, P, W, H);
-    g.cover = nullptr;   // no forward render on this path
-    BwdArgs a{ P, C, W, H, flags, g, features, nullptr, gt, nullptr, (float*)accum, nullptr, nullptr };
-    if (hm_factors) { a.hm_row = hm_factors[0]; a.hm_col = hm_factors[1]; a.hm_cmin = hm_factors[2]; a.hm_den = hm_factors[3]; }
-    if (es) { a.es_stop = es_state + 1; a.es_stride = 2 + 2 * es_window; a.es_views = Vf; }
-    dim3 grid(P, V, bwd_wave_groups(V, P, flags));   // see launch_bwd_small
-    {
-        ProfScope prof(1, st);
-        if (es) launch_bwd_loss<true>(a, vt, vo, grid, pick_cg(C), st);
-        else launch_bwd_loss(a, vt, vo, grid, pick_cg(C), st);
-    }
-    STAGE_CHECK("render-backward(fused loss)");
-    GeomBwdArgs ga{ P, C, W, H, flags, viewmatrix, projmatrix, xyz, opacity, scaling, rotation, nullptr, scale_modifier, radii,
-                    (const float*)accum, BWD_SPLITS, gt_totals, loss_sums, packed, nullptr, nullptr, nullptr, nullptr, nullptr,
-                    nullptr, nullptr };
-    if (views_dev) {
-        const ViewTanDev vd = views_dev_from(views_dev, lr_sched_dev);
-        if (es) hipLaunchKernelGGL((k_step_tail<true, ViewTanDev>), dim3(frames), dim3(256), 0, st, ga, vd, aa, Vf, g, radii);
-        else hipLaunchKernelGGL((k_step_tail<false, ViewTanDev>), dim3(frames), dim3(256), 0, st, ga, vd, aa, Vf, g, radii);
-    } else if (es) hipLaunchKernelGGL(k_step_tail<true>, dim3(frames), dim3(256), 0, st, ga, vt, aa, Vf, g, radii);
-    else hipLaunchKernelGGL(k_step_tail<false>, dim3(frames), dim3(256), 0, st, ga, vt, aa, Vf, g, radii);
-    STAGE_CHECK("step tail");
-    return 0;
-}
-
+// The four forms of the fused step (loop_fused_step_impl): each fills the StepCall from its parameters
 int sks_loop_fused_step(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
                         const float* tanfovx, const float* tanfovy, const float* features, float scale_modifier,
                         unsigned flags, int* radii, void* geom, const float* gt, const double* gt_totals, void* accum,
@@ -1140,11 +1169,9 @@ int sks_loop_fused_step(int V, int P, int C, int W, int H, const float* viewmatr
                         float lambda_consistency, const int* limb, const int* view_wh, const size_t* gt_offsets, int frames,
                         const float* const* hm_factors, void* stream)
 {
-    return loop_fused_step_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, features, scale_modifier, flags, radii,
-                                geom, gt, gt_totals, accum, loss_sums, packed, slots, group_mask, last_view, xyz, scaling,
-                                rotation, opacity, exp_avg, exp_avg_sq, counters, acc_steps, lr_sched, lrs, adam,
-                                lambda_consistency, limb, view_wh, gt_offsets, frames, hm_factors, nullptr, 0, 0.0f, nullptr,
-                                stream);
+    StepCall c{};
+    SKS_TAKE_STEP_CALL(c, lr_sched);
+    return loop_fused_step_impl(c);
 }
 
 int sks_loop_fused_step_es(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
@@ -1161,11 +1188,10 @@ int sks_loop_fused_step_es(int V, int P, int C, int W, int H, const float* viewm
         return fail(-2, "loop_fused_step_es: es_state is required (sks_loop_fused_step is the step without a criterion)");
     if (es_window < 1 || es_window > sksloop::ES_MAX_WINDOW)
         return fail(-1, "loop_fused_step_es: window %d out of range [1, %d]", es_window, sksloop::ES_MAX_WINDOW);
-    return loop_fused_step_impl(V, P, C, W, H, viewmatrix, projmatrix, tanfovx, tanfovy, features, scale_modifier, flags, radii,
-                                geom, gt, gt_totals, accum, loss_sums, packed, slots, group_mask, last_view, xyz, scaling,
-                                rotation, opacity, exp_avg, exp_avg_sq, counters, acc_steps, lr_sched, lrs, adam,
-                                lambda_consistency, limb, view_wh, gt_offsets, frames, hm_factors, es_state, es_window,
-                                es_tolerance, es_host_flags, stream);
+    StepCall c{};
+    SKS_TAKE_STEP_CALL(c, lr_sched);
+    SKS_TAKE_ES(c.es);
+    return loop_fused_step_impl(c);
 }
 
 int sks_loop_fused_step_dv(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
@@ -1178,11 +1204,11 @@ int sks_loop_fused_step_dv(int V, int P, int C, int W, int H, const float* viewm
                            const float* const* hm_factors, void* stream)
 {
     if (!views_dev || !lr_sched_dev) return fail(-2, "loop_fused_step_dv: views_dev and lr_sched_dev are required");
-    return loop_fused_step_impl(V, P, C, W, H, viewmatrix, projmatrix, nullptr, nullptr, features, scale_modifier, flags, radii,
-                                geom, gt, gt_totals, accum, loss_sums, packed, slots, group_mask, last_view, xyz, scaling,
-                                rotation, opacity, exp_avg, exp_avg_sq, counters, acc_steps, nullptr, lrs, adam,
-                                lambda_consistency, limb, view_wh, gt_offsets, frames, hm_factors, nullptr, 0, 0.0f, nullptr,
-                                stream, views_dev, lr_sched_dev);
+    const float *const tanfovx = NO_TAN, *const tanfovy = NO_TAN;
+    StepCall c{};
+    SKS_TAKE_STEP_CALL(c, NO_SCHED);
+    c.views_dev = views_dev, c.lr_sched_dev = lr_sched_dev;
+    return loop_fused_step_impl(c);
 }
 
 int sks_loop_fused_step_es_dv(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
@@ -1200,11 +1226,12 @@ int sks_loop_fused_step_es_dv(int V, int P, int C, int W, int H, const float* vi
         return fail(-2, "loop_fused_step_es_dv: es_state is required (sks_loop_fused_step_dv is the step without a criterion)");
     if (es_window < 1 || es_window > sksloop::ES_MAX_WINDOW)
         return fail(-1, "loop_fused_step_es_dv: window %d out of range [1, %d]", es_window, sksloop::ES_MAX_WINDOW);
-    return loop_fused_step_impl(V, P, C, W, H, viewmatrix, projmatrix, nullptr, nullptr, features, scale_modifier, flags, radii,
-                                geom, gt, gt_totals, accum, loss_sums, packed, slots, group_mask, last_view, xyz, scaling,
-                                rotation, opacity, exp_avg, exp_avg_sq, counters, acc_steps, nullptr, lrs, adam,
-                                lambda_consistency, limb, view_wh, gt_offsets, frames, hm_factors, es_state, es_window,
-                                es_tolerance, es_host_flags, stream, views_dev, lr_sched_dev);
+    const float *const tanfovx = NO_TAN, *const tanfovy = NO_TAN;
+    StepCall c{};
+    SKS_TAKE_STEP_CALL(c, NO_SCHED);
+    c.views_dev = views_dev, c.lr_sched_dev = lr_sched_dev;
+    SKS_TAKE_ES(c.es);
+    return loop_fused_step_impl(c);
 }
 
 int sks_prof_spin(double microseconds, void* stream)
@@ -1287,7 +1314,7 @@ int sks_mark_visible(int P, const float* means3D, const float* viewmatrix, const
     (void)projmatrix;  // in_frustum only uses the view-space depth (auxiliary.h:166)
     if (P < 0) return fail(-1, "P negative");
     if (P == 0) return 0;
-    if (!means3D || !viewmatrix || !present) return fail(-2, "missing required pointer");
+    if (int rc = require({ means3D, viewmatrix, present })) return rc;
     hipLaunchKernelGGL(k_mark_visible, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, P, means3D, viewmatrix, present);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1296,8 +1323,8 @@ int sks_mark_visible(int P, const float* means3D, const float* viewmatrix, const
 int sks_export_lists(int V, int W, int H, const void* binning, size_t bin_capacity, uint32_t* point_list,
                      uint32_t* ranges, void* stream)
 {
-    if (!binning || !point_list || !ranges) return fail(-2, "missing required pointer");
-    const int NT = ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
+    if (int rc = require({ binning, point_list, ranges })) return rc;
+    const int NT = TileGrid(W, H).NT;
     Bin b = bin_from(const_cast<void*>(binning), V, 1, NT, bin_capacity);   // (nothing per Gaussian is read: its arrays come last)
     const size_t m = bin_capacity > (size_t)NT ? bin_capacity : (size_t)NT;
     hipLaunchKernelGGL(k_export_lists, dim3((unsigned)((m + 255) / 256), V), dim3(256), 0, (hipStream_t)stream, NT,
