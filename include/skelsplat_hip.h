@@ -286,6 +286,10 @@ int sks_export_lists(int V, int W, int H, const void* binning, size_t bin_capaci
  * parameter gradients by 1 / N_v instead of re-reading the image.  sums: V x {S_v, N_v} doubles (zeroed by the call). */
 int sks_masked_l2(int V, size_t n_per_view, const float* render, const float* gt, float* dL_unscaled, double* sums,
                   void* stream);
+/* What sks_masked_l2 launches for views of n_per_view elements: out[0] = workgroups per view, out[1] = threads per workgroup
+ * (both 0 for n_per_view == 0, where nothing is launched).  Host only, no GPU call, like sks_launch_regime: from these and n the
+ * tests work out which of the kernel's loops a shape reaches (tests/masked_l2_cases.py). */
+int sks_masked_l2_launch(size_t n_per_view, int* out /* blocks, threads */);
 /* The same as a criterion: additionally loss[v] = S_v / N_v and scale[v] = 1 / N_v (mean != 0; an empty mask gives NaN like the
  * reference's `error[mask].mean()`), or S_v and 1 (mean == 0): what `l2_loss_gaussian(..., reduction="mean" / "sum")` returns
  * and what its backward scales dL_unscaled by -- formed on the device by one more tiny launch instead of five tensor ops. */

@@ -136,6 +136,7 @@ SIGNATURES = {
     "sks_mean_views": (_i, [_i, _i, _vp, _i, _vp, _vp]),
     "sks_export_lists": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "sks_masked_l2": (_i, [_i, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "sks_masked_l2_launch": (_i, [_sz, C.POINTER(_i)]),
     "sks_masked_l2_loss": (_i, [_i, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "sks_fused_ssim_fwd": (_i, [_i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sks_fused_ssim_bwd": (_i, [_i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -235,6 +236,14 @@ def launch_regime(V, P, C_, W, H, flags=0, out_aligned128=True):
     out = (_i * REGIME_INTS)()
     check(load().sks_launch_regime(V, P, C_, W, H, flags, 1 if out_aligned128 else 0, out), "sks_launch_regime")
     return {name: out[i] for i, name in enumerate(REGIME_FIELDS)}
+
+
+def masked_l2_launch(n_per_view):
+    """(workgroups per view, threads per workgroup) of sks_masked_l2 for views of n_per_view elements (host only:
+    sks_masked_l2_launch)."""
+    out = (_i * 2)()
+    check(load().sks_masked_l2_launch(n_per_view, out), "sks_masked_l2_launch")
+    return out[0], out[1]
 
 
 def prefill_planes(V, P, C_, W, H, flags=0):

@@ -604,9 +604,26 @@ __global__ void k_masked_l2_finish(int V, const double* __restrict__ sums, float
     scale[v] = (float)sc;
 }
 
+// workgroups per view of k_masked_l2: one per L2_THREADS 16-byte groups, at most L2_BLOCKS, at least one (the scalar tail)
+unsigned masked_l2_blocks(size_t n_per_view)
+{
+    size_t blocks = (n_per_view / 4 + L2_THREADS - 1) / L2_THREADS;
+    if (blocks > L2_BLOCKS) blocks = L2_BLOCKS;
+    if (blocks < 1) blocks = 1;
+    return (unsigned)blocks;
+}
+
 }  // namespace
 
 extern "C" {
+
+int sks_masked_l2_launch(size_t n_per_view, int* out)
+{
+    if (!out) return fail2(-2, "masked_l2_launch: missing pointer");
+    out[0] = n_per_view ? (int)masked_l2_blocks(n_per_view) : 0;
+    out[1] = n_per_view ? L2_THREADS : 0;
+    return 0;
+}
 
 int sks_masked_l2(int V, size_t n_per_view, const float* render, const float* gt, float* dL_unscaled, double* sums,
                   void* stream)
@@ -615,10 +632,8 @@ int sks_masked_l2(int V, size_t n_per_view, const float* render, const float* gt
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY2(hipMemsetAsync(sums, 0, (size_t)V * 2 * sizeof(double), st));
     if (n_per_view == 0) return 0;
-    size_t blocks = (n_per_view / 4 + L2_THREADS - 1) / L2_THREADS;
-    if (blocks > L2_BLOCKS) blocks = L2_BLOCKS;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(k_masked_l2, dim3((unsigned)blocks, V), dim3(L2_THREADS), 0, st, n_per_view, render, gt, dL_unscaled, sums);
+    const unsigned blocks = masked_l2_blocks(n_per_view);
+    hipLaunchKernelGGL(k_masked_l2, dim3(blocks, V), dim3(L2_THREADS), 0, st, n_per_view, render, gt, dL_unscaled, sums);
     HIP_TRY2(hipGetLastError());
     return 0;
 }

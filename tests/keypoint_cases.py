@@ -17,6 +17,9 @@ elements per workgroup, 16-byte groups):
   op      (2,15,48,64)    Occlusion-Person's; plane (0,7) is all zero
 Each in two regimes: `peak1` (peak 0.9 .. 1.0: at beta = 100 the background's weights underflow) and `peak002` (peak
 0.015 .. 0.02: the background dominates and the keypoint is pulled towards the image centre, as in the reference).
+
+Beside the case set, and not part of the fixture: wide_image(), (1,5,1097,1003), 68 chunks per plane -- the one shape at which a
+lane of the merge kernel takes a second chunk record.
 """
 import numpy as np
 
@@ -52,6 +55,45 @@ def make_image(name, regime):
                 plane += amp * np.outer(np.exp(-(rows - by) ** 2 / (2 * sigma ** 2)), np.exp(-(cols - bx) ** 2 / (2 * sigma ** 2)))
             img[v, c] = plane.astype(np.float32)
     return img
+
+
+# ---- more than 64 chunks per plane: k_softargmax_merge's second trip ---------------------------------------------------------
+# One wave merges a plane's chunk records, lane L taking chunks L, L + 64, ...: only a plane of more than 64 chunks makes a lane
+# take a second one.  wide_image() is NOT an entry of SHAPES / CASES: those are bound to the golden fixture and to the measured
+# REF_FP32_DEV_* constants.  SA_CHUNK restates csrc/sks_keypoint.hip's constant; tests/test_keypoints_cpu.py holds it to the
+# library's own sks_softargmax_scratch_bytes.
+SA_CHUNK = 16384
+MERGE_LANES = 64
+WIDE_SHAPE = (1, 5, 1097, 1003)     # H * W = 1 100 291: 68 chunks; H * W % 4 == 3, so the planes start at phases 0, 3, 2, 1, 0;
+#                                     rows from 1046 on lie wholly in chunks 64 and above
+# plane -> (amplitude, sigma, [(cx, cy), ...], chunk(s) of the maximum); plane 4 is all zero (uniform softmax, the exact centre)
+WIDE_PLANES = {0: (0.95, 3.0, [(700.3, 1080.4)], [66]),                 # peak1: the maximum on the second trip
+               1: (0.018, 2.5, [(200.7, 300.2)], [18]),                 # peak002: maximum on the first trip, background everywhere
+               2: (0.017, 3.5, [(500.6, 1075.3)], [65]),                # peak002: the maximum on the second trip
+               3: (0.93, 3.0, [(100.0, 50.0), (900.0, 1085.0)], [3, 66])}    # two equal maxima, one on each trip
+WIDE_ZERO_PLANE = 4
+
+
+def wide_image():
+    """The WIDE_SHAPE float32 image: sums of blobs evaluated in float64 and rounded to float32, like make_image."""
+    V, C, H, W = WIDE_SHAPE
+    img = np.zeros(WIDE_SHAPE, dtype=np.float32)
+    cols, rows = np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64)
+    for c, (amp, sigma, centres, _) in WIDE_PLANES.items():
+        plane = np.zeros((H, W))
+        for bx, by in centres:
+            plane += amp * np.outer(np.exp(-(rows - by) ** 2 / (2 * sigma ** 2)), np.exp(-(cols - bx) ** 2 / (2 * sigma ** 2)))
+        img[0, c] = plane.astype(np.float32)
+    return img
+
+
+def bwd_stores_16_bytes(img_phase, grad_phase):
+    """k_softargmax_bwd's `vec_store` for base pointers img_phase / grad_phase floats past a 16-byte boundary.  A chunk of plane p
+    starts at the same element offset e from both bases; its scalar head takes (4 - (img_phase + e)) % 4 elements, so the first
+    group's gradient lies (grad_phase + e + (4 - (img_phase + e)) % 4) % 4 = (grad_phase - img_phase) % 4 floats past a boundary,
+    whatever the plane and the chunk: 16-byte stores where the two phases agree, element by element for the other 12 of the 16
+    pairs."""
+    return (grad_phase - img_phase) % 4 == 0
 
 
 def checksum(img):

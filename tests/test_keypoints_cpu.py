@@ -145,6 +145,83 @@ def test_entry_points_report_bad_arguments():
         _lib.check(lib.sks_softargmax_bwd(1, 65536, 65536, 100.0, None, None, None, None, None), "sks_softargmax_bwd")
 
 
+def _keypoint_of_first(flat, W, count, beta=100.0):
+    """Float64 [E col, E row] under softmax(beta x) over the FIRST `count` elements of a plane of width W."""
+    z = beta * flat[:count].astype(np.float64)
+    e = np.exp(z - z.max())
+    k = np.arange(count)
+    return np.array([(e * (k % W)).sum(), (e * (k // W)).sum()]) / e.sum()
+
+
+def test_wide_image_reaches_the_second_trip_of_the_merge():
+    """keypoint_cases.wide_image(), on the reference alone: more than 64 chunks per plane, every plane's maximum in the chunk its
+    table states, and a merge that ignored the chunks from 64 on -- a wave's second trip -- would move every keypoint by more than
+    100 bars (at least 25 px against a bar of about 0.1 px)."""
+    from skelsplat_amd import _lib
+    COORD_BAR = kr.DEVICE_FACTOR * kr.REF_FP32_DEV_COORD                                 # test_keypoints_gpu.py's, of the extent
+    V, C, H, W = kc.WIDE_SHAPE
+    n = H * W
+    nchunks = _lib.load().sks_softargmax_scratch_bytes(V * C, W, H) // (V * C * 32)      # 4 doubles per (plane, chunk)
+    assert nchunks == -(-n // kc.SA_CHUNK) == 68 > kc.MERGE_LANES
+    assert n % 4 == 3 and [(c * n) % 4 for c in range(C)] == [0, 3, 2, 1, 0]
+    assert 1046 * W >= kc.MERGE_LANES * kc.SA_CHUNK > 1045 * W
+    img = kc.wide_image()
+    assert img.shape == kc.WIDE_SHAPE and img.dtype == np.float32
+    flat = img.reshape(C, n)
+    for c, (_, _, centres, chunks) in kc.WIDE_PLANES.items():
+        at = np.flatnonzero(flat[c] == flat[c].max())
+        assert (at // kc.SA_CHUNK).tolist() == chunks, c
+        assert at.tolist() == sorted(round(cy) * W + round(cx) for cx, cy in centres), c
+    assert len(kc.WIDE_PLANES[3][3]) == 2                                # plane 3: exactly two equal maximal floats
+    assert not flat[kc.WIDE_ZERO_PLANE].any()
+    xy64 = kr.softargmax2d(torch.from_numpy(img)).numpy()[0]
+    np.testing.assert_allclose(xy64[kc.WIDE_ZERO_PLANE], [(W - 1) / 2, (H - 1) / 2], rtol=1e-13)
+    np.testing.assert_allclose(xy64[3], np.mean(kc.WIDE_PLANES[3][2], axis=0), rtol=1e-9)
+    for c in range(C):
+        np.testing.assert_allclose(_keypoint_of_first(flat[c], W, n), xy64[c], rtol=1e-12)
+        cut = _keypoint_of_first(flat[c], W, kc.MERGE_LANES * kc.SA_CHUNK)
+        moved = np.abs(cut - xy64[c])
+        print(f"plane {c}: without chunks 64.. the keypoint moves by ({moved[0]:.1f}, {moved[1]:.1f}) px; "
+              f"the bar is ({COORD_BAR * (W - 1):.3f}, {COORD_BAR * (H - 1):.3f}) px")
+        assert max(moved[0] / (W - 1), moved[1] / (H - 1)) > 100 * COORD_BAR, c
+        assert moved.max() >= 25.0, c
+
+
+def test_backward_store_branch_and_what_a_slip_in_it_looks_like():
+    """Host arithmetic and numpy only.  k_softargmax_bwd stores 16 bytes at a time for the 4 of the 16 (image phase, gradient phase)
+    pairs where the phases agree and element by element for the other 12 (keypoint_cases.bwd_stores_16_bytes); and the checks
+    test_keypoints_gpu.py applies to its guarded gradient buffers fail when a range is written one element off, in either
+    direction, or keeps a sentinel."""
+    from tests import guarded
+    pairs = [(i, g) for i in guarded.PHASES for g in guarded.PHASES]
+    assert sum(not kc.bwd_stores_16_bytes(i, g) for i, g in pairs) == 12
+    # the rule, spelled out per chunk for the two images the GPU test uses
+    for name in ("odd", "chunks"):
+        V, C, H, W = kc.SHAPES[name]
+        n = H * W
+        for i, g in pairs:
+            for p in range(V * C):
+                for begin in range(0, n, kc.SA_CHUNK):
+                    head = min(min(kc.SA_CHUNK, n - begin), (4 - (i + p * n + begin)) % 4)
+                    assert ((g + p * n + begin + head) % 4 == 0) == kc.bwd_stores_16_bytes(i, g)
+    n = 6 * 37 * 53
+    want = (np.arange(n, dtype=np.float32) + 1.0).view(np.int32)
+    for phase in guarded.PHASES:
+        buf = np.full(guarded.buffer_floats(n), guarded.SENTINEL, dtype=np.int32)
+        buf[guarded.interior(phase, n)] = want
+        guarded.check("in place", buf, phase, n, want)
+        for shift, text in ((1, "guard after"), (-1, "guard before")):
+            off = np.full(guarded.buffer_floats(n), guarded.SENTINEL, dtype=np.int32)
+            off[guarded.GUARD + phase + shift:guarded.GUARD + phase + shift + n] = want
+            with pytest.raises(AssertionError, match=text):
+                guarded.check("one off", off, phase, n, want)
+        one = buf.copy()                                     # one group's elements written one further on, inside the range
+        one[guarded.GUARD + phase + 401:guarded.GUARD + phase + 405] = want[400:404]
+        one[guarded.GUARD + phase + 400] = guarded.SENTINEL
+        with pytest.raises(AssertionError, match="never written"):
+            guarded.check("group one off", one, phase, n, want)
+
+
 def test_losses_holds_the_reference_keys_that_exist():
     from skelsplat_amd import keypoints, ops
     assert set(keypoints.losses) == {"l2", "l2_sqrt", "huber", "cauchy", "l2_gaussian"}

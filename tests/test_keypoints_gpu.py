@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import guarded
 from tests import keypoint_cases as kc
 from tests import keypoint_ref as kr
 from tests import util
@@ -136,6 +137,96 @@ def test_result_does_not_depend_on_the_batching(device, name):
         xy1, g1 = run(base.view(V * C, H, W)[p], cot.view(V * C, 2)[p])
         assert xy1.shape == (2,)
         assert torch.equal(xy1, xy3[p]) and torch.equal(g1, g3[p]), p
+
+
+_WIDE = {}
+
+
+def wide_reference():
+    """Float64 keypoints and image gradient of keypoint_cases.wide_image() under cotangent((1, 5)), computed once."""
+    if not _WIDE:
+        img = kc.wide_image()
+        x = torch.from_numpy(img).double().requires_grad_(True)
+        xy = kr.softargmax2d(x)
+        cot = torch.from_numpy(kc.cotangent(img.shape[:2]))
+        (g,) = torch.autograd.grad((xy * cot).sum(), x)
+        _WIDE.update(img=img, xy=xy.detach().numpy(), cot=cot, g_xy=g.numpy())
+    return _WIDE
+
+
+def test_more_than_64_chunks_per_plane(device):
+    """keypoint_cases.wide_image(): 68 chunks per plane, so four lanes of k_softargmax_merge take a second record each -- the walk
+    `k += 64`, the maximum over both trips and the fp64 rescale of the later records.  test_keypoints_cpu.py shows that dropping
+    those records moves every plane's keypoint by 25 px or more.  Forward and backward against float64, the all-zero plane and the
+    plane with two equal maxima (one on each trip) at their closed forms, two runs and one plane at a time bit for bit."""
+    from skelsplat_amd.keypoints import softargmax2d
+    ref = wide_reference()
+    V, C, H, W = kc.WIDE_SHAPE
+    cot = ref["cot"].float().to(device)
+    base = torch.from_numpy(ref["img"]).to(device)
+
+    def run(view, g):
+        x = view.detach().requires_grad_(True)
+        xy = softargmax2d(x)
+        (xy * g).sum().backward()
+        return xy.detach(), x.grad
+
+    xy, g = run(base, cot)
+    got = xy.cpu().numpy()
+    dev = coord_dev(got, ref["xy"], W, H)
+    print(f"wide: coordinates off by {dev:.3e} of the extent (bar {COORD_BAR:.3e})")
+    assert got.shape == (V, C, 2) and dev <= COORD_BAR
+    util.assert_close("d softargmax2d / d image", g.cpu().numpy(), ref["g_xy"], rtol=1e-3, atol_scale=1e-4)
+    np.testing.assert_allclose(got[0, kc.WIDE_ZERO_PLANE], [(W - 1) / 2, (H - 1) / 2], rtol=1e-6)
+    centre = np.mean(kc.WIDE_PLANES[3][2], axis=0)
+    assert coord_dev(got[0, 3], centre, W, H) <= COORD_BAR
+    xy2, g2 = run(base, cot)
+    assert torch.equal(xy, xy2) and torch.equal(g, g2)
+    for p in range(C):          # the same memory: plane p starts (p * H * W) % 4 floats past a 16-byte boundary either way
+        xy1, g1 = run(base.view(C, H, W)[p], cot.view(C, 2)[p])
+        assert torch.equal(xy1, xy[0, p]) and torch.equal(g1, g[0, p]), p
+
+
+@pytest.mark.parametrize("name", ["odd", "chunks"])
+def test_backward_stores_at_every_phase_of_image_and_gradient(device, name):
+    """sks_softargmax_bwd with `img` and `dL_dimg` at all 16 pairs of 4-byte phases.  The kernel stores the gradient 16 bytes at a
+    time only where it is as aligned as the image, which keypoint_cases.bwd_stores_16_bytes works out from the two phases alone:
+    4 of the 16 pairs; the other 12 take the element-wise stores.  ONE stats buffer, from one forward on the aligned image: given
+    the stats every element's gradient is a function of that element alone, so whatever the grouping into head, 16-byte groups
+    and tail, the interior equals the (0, 0) result bit for bit, holds no sentinel, and both guards stay untouched
+    (tests/guarded.py)."""
+    from skelsplat_amd import _lib, keypoints
+    ref = reference(name, "peak002")
+    V, C, H, W = ref["img"].shape
+    planes, total = V * C, ref["img"].size
+    size = guarded.buffer_floats(total)
+    lib = _lib.load()
+    flat = torch.from_numpy(ref["img"].reshape(-1)).to(device)
+    _, stats = keypoints._fwd(flat.view(V, C, H, W), 100.0)
+    cot = ref["cot"].float().to(device).reshape(planes, 2).contiguous()
+    imgs = {}
+    for p in guarded.PHASES:
+        imgs[p] = torch.zeros(size, dtype=torch.float32, device=device)
+        imgs[p][guarded.interior(p, total)] = flat
+    sentinel = torch.full((size,), int(guarded.SENTINEL), dtype=torch.int32, device=device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    want, scalar = None, 0
+    for pi in guarded.PHASES:
+        for pg in guarded.PHASES:
+            out = sentinel.clone()
+            assert imgs[pi].data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
+            with torch.cuda.device(device):
+                rc = lib.sks_softargmax_bwd(planes, W, H, 100.0, imgs[pi].data_ptr() + 4 * (guarded.GUARD + pi), stats.data_ptr(),
+                                            cot.data_ptr(), out.data_ptr() + 4 * (guarded.GUARD + pg), stream)
+            _lib.check(rc, "sks_softargmax_bwd")
+            bits = out.cpu().numpy()
+            if want is None:            # (0, 0): held to float64 like every other gradient, then the yardstick of the other 15
+                want = bits[guarded.interior(0, total)].copy()
+                util.assert_close("d softargmax2d / d image", want.view(np.float32).reshape(ref["img"].shape), ref["g_xy"],
+                                  rtol=1e-3, atol_scale=1e-4)
+            guarded.check(f"{name} image phase {pi}, gradient phase {pg}", bits, pg, total, want)
+            scalar += not kc.bwd_stores_16_bytes(pi, pg)
+    assert scalar == 12
 
 
 def test_non_default_stream_is_honoured(device):

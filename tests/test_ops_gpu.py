@@ -702,6 +702,43 @@ def test_knn_grid_equals_allpairs(device, P, kind):
         assert torch.equal(distCUDA2(pts), b)
 
 
+@pytest.mark.parametrize("kind", ["uniform", "clustered"])
+def test_knn_box_pass_takes_a_second_trip(device, kind):
+    """k_knn_bbox runs at most 256 workgroups of 256 threads, so its grid-stride loop takes a second trip only for P > 65 536;
+    here P = 70 001 and the smallest and the largest coordinate of every axis sit at indices >= 65 536, where only that trip
+    reads them.  The grid search, the automatic choice and the all-pairs sweep agree bit for bit, and on 512 sampled rows (the
+    extreme points among them) all equal the float32 brute force of test_knn_matches_bruteforce.  The cap of 160 cells per
+    axis, reached above 8 million points, stays out of scope."""
+    from skelsplat_amd.ops import distCUDA2
+    P, first_trip = 70001, 256 * 256
+    g = torch.Generator().manual_seed(P + len(kind))
+    if kind == "uniform":
+        pts = torch.rand(P, 3, generator=g) * 1000
+    else:
+        centres = torch.rand(5, 3, generator=g) * 1e4
+        pts = centres[torch.randint(0, 5, (P,), generator=g)] + torch.randn(P, 3, generator=g)
+    p = pts.numpy().astype(np.float32)
+    ext = np.unique(np.concatenate([p.argmin(axis=0), p.argmax(axis=0)]))
+    early = ext[ext < first_trip]
+    free = np.setdiff1d(np.arange(first_trip, P), ext)[:early.size]
+    p[np.concatenate([early, free])] = p[np.concatenate([free, early])]          # swap the early extremes behind the first trip
+    ext = np.unique(np.concatenate([p.argmin(axis=0), p.argmax(axis=0)]))
+    assert ext.min() >= first_trip and np.all(p[:first_trip].min(axis=0) > p.min(axis=0)) \
+        and np.all(p[:first_trip].max(axis=0) < p.max(axis=0))
+    dev_pts = torch.from_numpy(p).to(device)
+    b = distCUDA2(dev_pts, method="grid")
+    assert torch.equal(distCUDA2(dev_pts), b) and torch.equal(distCUDA2(dev_pts, method="allpairs"), b)
+    rng = np.random.default_rng(len(kind))
+    rows = np.concatenate([ext, rng.choice(np.setdiff1d(np.arange(P), ext), 512 - ext.size, replace=False)])
+    d = p[rows, None, :] - p[None, :, :]
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]).astype(np.float32)
+    d2[np.arange(rows.size), rows] = np.float32(np.finfo(np.float32).max)
+    part = np.partition(d2, 3, axis=1)[:, :3]
+    part.sort(axis=1)
+    want = ((part[:, 0] + part[:, 1]) + part[:, 2]) / np.float32(3.0)
+    np.testing.assert_allclose(b.cpu().numpy()[rows], want, rtol=2e-6)
+
+
 # ------------------------------------------------------------------------------------------ view-sharded exchange
 @pytest.fixture
 def rccl_world1(device):
