@@ -41,7 +41,8 @@ from skelsplat_amd.loop import FramePipeline
 from skelsplat_amd.scene import GaussianModel, SyntheticScene, project_points
 
 
-def main():
+def main(argv=None):
+    """Runs the example; with --report returns what the report lines were printed from (device tensors), else None."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset", default="h36m")
     ap.add_argument("--views", type=int, default=4)
@@ -55,7 +56,7 @@ def main():
     ap.add_argument("--uncertainty", action="store_true")
     ap.add_argument("--reject-px", type=float, default=None)
     ap.add_argument("--corrupt", type=int, default=0)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     sc = SyntheticScene(args.dataset, n_views=args.views, seed=0, device=dev)
     rigs = [sc.cameras] + [SyntheticScene(args.dataset, n_views=args.views, seed=r, device=dev).cameras for r in range(1, args.rigs)]
@@ -137,7 +138,7 @@ def main():
         print(f"initial joints, {args.corrupt} corrupted detections per frame: mean MPJPE {ep:.2f} mm from all views -> {e0:.2f} mm "
               f"with reject_px {args.reject_px:g} ({rejected} detections rejected, {fallbacks} joints without a consensus of 3)")
     if args.report:
-        from skelsplat_amd.report import evaluate_sequence, pose_errors
+        from skelsplat_amd.report import evaluate_sequence, evaluate_sequence_aligned, pose_errors
         r = pipe.report
         curve = r.trace_errors.double().mean(dim=0).cpu().numpy()       # (steps + 1, 2): the sequence's mean after every step
         print("optimiser step   mean abs error   mean root-relative error  (mm, over the sequence)")
@@ -152,6 +153,10 @@ def main():
         print(f"evaluate_sequence: abs MPJPE {float(ev['abs']):.3f} mm, rel {float(ev['rel']):.3f} mm; per activity abs "
               + " ".join(f"{x:.2f}" for x in ev["abs_groups"].tolist()) + " | rel "
               + " ".join(f"{x:.2f}" for x in ev["rel_groups"].tolist()))
+        eva = evaluate_sequence_aligned(out, gt_dev, groups=acts, n_groups=4)      # one more call on what is on the device
+        print(f"evaluate_sequence_aligned: PA-MPJPE {float(eva['pa_mpjpe']):.3f} mm, N-MPJPE {float(eva['n_mpjpe']):.3f} mm; "
+              "per activity PA " + " ".join(f"{x:.2f}" for x in eva["pa_mpjpe_groups"].tolist()) + " | N "
+              + " ".join(f"{x:.2f}" for x in eva["n_mpjpe_groups"].tolist()))
     if args.uncertainty:
         from skelsplat_amd.uncertainty import calibration
         unc = pipe.gaussians.uncertainty(gt_dev)
@@ -162,6 +167,7 @@ def main():
         print("ground truth inside   1 sigma   2 sigma   3 sigma")
         for name, row in [("all joints", cal["overall"].tolist())] + list(zip(names, cal["per_joint"].tolist())):
             print(f"{name:18s} " + " ".join(f"{100.0 * x:8.1f}%" for x in row))
+    return dict(joints=out, gt=gt_dev, activities=acts, aligned=eva) if args.report else None
 
 
 if __name__ == "__main__":

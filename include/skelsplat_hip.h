@@ -724,6 +724,49 @@ int sks_view_footprints(int V, int J, int W, int H, const float* means3D, const 
 int sks_calibration(int N, int P, const float* d2, const unsigned char* valid, int K, const float* k_sigma /*HOST K*/, int* counts,
                     void* stream);
 
+/* Pose errors after the best per-frame alignment of the prediction onto the ground truth (csrc/sks_align.hip; added to
+ * sks_version 14: the number did not move): the rigid-aligned error, PA-MPJPE ("Protocol #2") and N-MPJPE of the H36M / Panoptic
+ * literature.  The reference reports MPJPE alone, so there is no reference output behind these; they are held to two textbook
+ * float64 solutions (Umeyama's SVD form, Horn's quaternion form; tests/procrustes_ref.py).  Launches go on `stream`, nothing
+ * synchronises, no atomics; one wavefront per frame, everything in double from the float inputs, every output rounded to its type
+ * once, every sum in a fixed order (lane l adds joints l, l + 64, ..., then a butterfly): a frame's results depend on P and its own
+ * numbers only, and are bitwise the same from run to run.  Bad arguments are refused before any HIP call.  Device memory.
+ *
+ * sks_align_poses: pred, gt (N,P,3) floats, valid (N,P) bytes or NULL (all joints) -> aligned (N,P,3) floats, transform (N,13)
+ *   doubles {s, R row-major, t}, per_joint (N,P) floats, mean (N) floats; each may be NULL, not all four.  pred is fitted onto gt
+ *   over the joints with valid != 0:
+ *     SKS_ALIGN_RIGID, SKS_ALIGN_SIMILARITY: mu_x, mu_y the centroids, x = pred - mu_x, y = gt - mu_y, H = sum x_i y_i^T; R is the
+ *       PROPER rotation that maximises trace(R H) -- V diag(1, 1, det(V U^T)) U^T of H = U S V^T, never a reflection --, found as
+ *       the unit quaternion of Horn's 4x4 symmetric eigenproblem by cyclic Jacobi sweeps (csrc/sks_procrustes.h), which needs no
+ *       case for a planar (rank 2), collinear (rank 1) or mirrored input; H = 0 (one joint, coincident joints) gives R = I.
+ *       SIMILARITY: s = sum <R x_i, y_i> / sum |x_i|^2 (= trace(S D) / sum |x_i|^2), 1 when the denominator is 0; RIGID: s = 1.
+ *       t = mu_y - s R mu_x.
+ *     SKS_ALIGN_SCALE: x_i = pred_i - pred_0, y_i = gt_i - gt_0 (joint 0 is the root, as in column 1 of sks_pose_errors),
+ *       s = sum <x_i, y_i> / sum <x_i, x_i>, 1 when the denominator is 0; R = I, t = gt_0 - s pred_0.  With joint 0 masked out
+ *       every result of the frame is NaN.
+ *   The error of joint i is ||gt_i - (s R pred_i + t)||, formed as gt_i - (s R (pred_i - o_x) + o_y) about the origins o the fit
+ *   used (the centroids; joint 0), which is the same point without the cancellation of a pose far from the world's origin; mean is
+ *   its mean over the valid joints.  aligned and per_joint are written for ALL joints, masked ones included, with the transform
+ *   fitted on the valid ones.  A frame without a valid joint (in every mode): mean NaN, the identity transform (s = 1, R = I,
+ *   t = 0), aligned = pred.  A NaN or inf in a valid joint makes every result of its own frame NaN and touches no other frame; the
+ *   frame skips the fit, so it leaves the kernel no later than a clean one.
+ *
+ * sks_eval_sequence_aligned: the sequence's PA-MPJPE and N-MPJPE, overall and per group.  Three launches: sks_align_poses'
+ *   kernel in SIMILARITY and in SCALE mode with per-joint errors into `scratch` (sks_eval_sequence_aligned_scratch_bytes(N, P)
+ *   bytes at least), then one workgroup per row of out (1 + n_groups, 2) doubles = {PA-MPJPE, N-MPJPE}: row 0 the mean over all
+ *   valid joints of all frames, row 1 + g over the frames with group_ids == g (an id outside [0, n_groups) is in no group); a row
+ *   without valid joints is NaN.  Thread t adds frames t, t + 256, ... in index order, a frame's valid joints in index order, sums
+ *   and counts in double, then a fixed tree: the fixed-order float64 means of exactly the values sks_align_poses writes to
+ *   per_joint for the same inputs.  n_groups <= SKS_EVAL_MAX_GROUPS. */
+#define SKS_ALIGN_RIGID       0   /* R, t;  s = 1 */
+#define SKS_ALIGN_SIMILARITY  1   /* s, R, t  (PA-MPJPE) */
+#define SKS_ALIGN_SCALE       2   /* s only, on root-relative poses (N-MPJPE) */
+int sks_align_poses(int N, int P, const float* pred, const float* gt, const unsigned char* valid, int mode, float* aligned,
+                    double* transform, float* per_joint, float* mean, void* stream);
+int sks_eval_sequence_aligned(int N, int P, const float* pred, const float* gt, const unsigned char* valid, const int* group_ids,
+                              int n_groups, void* scratch, size_t scratch_bytes, double* out, void* stream);
+size_t sks_eval_sequence_aligned_scratch_bytes(int N, int P);
+
 /* Measurement hook used by bench.py (no reference counterpart; state per HOST THREAD, like the error text): while enabled, the dominant kernel of sks_forward
  * (kind 0: forward compositor) and of sks_backward (kind 1: backward compositor) is bracketed by hipEvents recorded
  * on the caller's stream (the small path's kernels carry the pair on their own dispatch, hipExtLaunchKernelGGL).  The low 16

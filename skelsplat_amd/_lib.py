@@ -29,6 +29,7 @@ SKS_SOFTARGMAX_STATS = 6
 SKS_REPORT_MAX_SAVES = 8
 SKS_EVAL_MAX_GROUPS = 64
 SKS_CALIBRATION_MAX_K = 8
+SKS_ALIGN_RIGID, SKS_ALIGN_SIMILARITY, SKS_ALIGN_SCALE = 0, 1, 2
 
 
 SKS_NO_EARLY_FILL = 1 << 30
@@ -168,6 +169,9 @@ SIGNATURES = {
     "sks_joint_uncertainty": (_i, [_i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
     "sks_view_footprints": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "sks_calibration": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "sks_align_poses": (_i, [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sks_eval_sequence_aligned": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _vp]),
+    "sks_eval_sequence_aligned_scratch_bytes": (_sz, [_i, _i]),
     "sks_prof_enable": (_i, [_i]),
     "sks_prof_spin": (_i, [C.c_double, _vp]),
     "sks_prof_read": (_i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),

@@ -2,7 +2,8 @@
 
 save_ply: scene/gaussian_model.py:250-281 (fields x,y,z,nx,ny,nz,f_dc_*,f_rest_*,opacity,scale_*,rot_*; binary little
 endian, float32) without the plyfile dependency; read_ply_xyz: what eval.py:32-33 reads through open3d;
-mpjpe / mpjpe_root_relative: eval.py:123-139; evaluate: eval.py:91-171 (the directory walk around them)."""
+mpjpe / mpjpe_root_relative: eval.py:123-139; similarity_transform / pa_mpjpe / n_mpjpe: the aligned metrics the
+reference does not report (the host counterparts of report.align_poses / report.evaluate_sequence_aligned); evaluate: eval.py:91-171 (the directory walk around them)."""
 import os
 
 import numpy as np
@@ -82,6 +83,63 @@ def mpjpe_root_relative(pred, gt):
     """eval.py:133-139: both poses translated so that joint 0 is the origin."""
     pred, gt = np.asarray(pred, dtype=np.float64), np.asarray(gt, dtype=np.float64)
     return mpjpe(pred - pred[..., 0:1, :], gt - gt[..., 0:1, :])
+
+
+def similarity_transform(pred, gt, valid=None, scale=True):
+    """One pose: (s, R (3,3), t (3,)) minimising sum ||gt_i - (s R pred_i + t)||^2 over the joints with `valid` (all when None), R
+    a proper rotation (Umeyama 1991: the SVD of the cross-covariance with the reflection repaired); `scale=False`: s = 1.
+    Without a valid joint the identity.  numpy float64; on the device: report.align_poses."""
+    pred, gt = np.asarray(pred, dtype=np.float64), np.asarray(gt, dtype=np.float64)
+    if pred.shape != gt.shape or pred.ndim != 2 or pred.shape[1] != 3:
+        raise ValueError(f"similarity_transform: pred and gt must both be (P,3), got {pred.shape} and {gt.shape}")
+    v = np.ones(len(pred), dtype=bool) if valid is None else np.asarray(valid).astype(bool)
+    if not v.any():
+        return 1.0, np.eye(3), np.zeros(3)
+    mx, my = pred[v].mean(axis=0), gt[v].mean(axis=0)
+    x, y = pred[v] - mx, gt[v] - my
+    U, S, Vt = np.linalg.svd(x.T @ y)
+    d = np.array([1.0, 1.0, -1.0 if np.linalg.det(Vt.T @ U.T) < 0 else 1.0])
+    R = (Vt.T * d) @ U.T
+    sxx = float(np.sum(x * x))
+    s = float(np.sum(S * d)) / sxx if scale and sxx != 0 else 1.0
+    return s, R, my - s * (R @ mx)
+
+
+def _frames(pred, gt, valid, what):
+    pred, gt = np.asarray(pred, dtype=np.float64), np.asarray(gt, dtype=np.float64)
+    if pred.shape != gt.shape or pred.ndim not in (2, 3) or pred.shape[-1] != 3:
+        raise ValueError(f"{what}: pred and gt must both be (N,P,3) or (P,3), got {pred.shape} and {gt.shape}")
+    pred, gt = pred.reshape((-1,) + pred.shape[-2:]), gt.reshape((-1,) + gt.shape[-2:])
+    v = np.ones(pred.shape[:2], dtype=bool) if valid is None else np.asarray(valid).astype(bool).reshape(pred.shape[:2])
+    return pred, gt, v
+
+
+def pa_mpjpe(pred, gt, valid=None):
+    """PA-MPJPE ("Protocol #2"): the mean over frames and valid joints of the error after each frame's best similarity transform;
+    pred, gt (N,J,3) or (J,3), valid (N,J) or None.  NaN without a valid joint.  On the device: report.evaluate_sequence_aligned."""
+    pred, gt, v = _frames(pred, gt, valid, "pa_mpjpe")
+    errs = []
+    for p, g, m in zip(pred, gt, v):
+        s, R, t = similarity_transform(p, g, m)
+        errs.append(np.linalg.norm(g - (s * p @ R.T + t), axis=-1)[m])
+    errs = np.concatenate(errs)
+    return float(errs.mean()) if errs.size else float("nan")
+
+
+def n_mpjpe(pred, gt, valid=None):
+    """N-MPJPE: both poses relative to joint 0, the prediction scaled per frame by s = sum <x, y> / sum <x, x> over the valid
+    joints (1 when the denominator is 0); the mean over frames and valid joints.  A frame whose joint 0 is masked out is NaN."""
+    pred, gt, v = _frames(pred, gt, valid, "n_mpjpe")
+    errs = []
+    for p, g, m in zip(pred, gt, v):
+        if not m.any():
+            continue
+        x, y = p - p[0], g - g[0]
+        den = float(np.sum(x[m] * x[m]))
+        s = float(np.sum(x[m] * y[m])) / den if den != 0 else 1.0
+        errs.append(np.linalg.norm(y - s * x, axis=-1)[m] if m[0] else np.full(int(m.sum()), np.nan))
+    errs = np.concatenate(errs) if errs else np.zeros(0)
+    return float(errs.mean()) if errs.size else float("nan")
 
 
 H36M_ACTIVITIES = ("Directions Discussion Eating Greeting Phoning Posing Purchases Sitting SittingDown Smoking Photo "

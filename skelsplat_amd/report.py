@@ -2,11 +2,14 @@
 
 pose_errors        per-joint absolute and root-relative error against the ground truth and their means (train.py:184-213);
 evaluate_sequence  absolute and root-relative MPJPE of a sequence, overall and per group of frames (eval.py:115-142);
+align_poses, aligned_pose_errors, evaluate_sequence_aligned
+                   the same after the best per-frame rigid / similarity / scale alignment of the prediction onto the ground
+                   truth: PA-MPJPE and N-MPJPE, which the reference does not report (csrc/sks_align.hip);
 LoopReport         the buffers a FrameBatchLoop reports into -- errors and losses at every optimiser step, the joints at
                    `save_iterations` (train.py:227-229) -- and the one small launch per group that fills them.
 
 Everything takes device tensors, enqueues on the current stream and never synchronises; every result is bitwise reproducible.
-The host-side counterparts behind a directory of .ply files are io.mpjpe / io.evaluate."""
+The host-side counterparts behind a directory of .ply files are io.mpjpe / io.evaluate, and io.pa_mpjpe / io.n_mpjpe."""
 import ctypes
 
 import numpy as np
@@ -99,6 +102,121 @@ def evaluate_sequence(pred, gt, groups=None, n_groups=None, abs_valid=None):
                                            None if valid is None else valid.data_ptr(), out.data_ptr(), _stream(dev))
     _lib.check(rc, "sks_eval_sequence")
     return dict(abs=out[0, 0], rel=out[0, 1], abs_groups=out[1:, 0], rel_groups=out[1:, 1])
+
+
+def _groups(what, groups, n_groups, N, dev):
+    """Group ids as evaluate_sequence takes them -> ((N,) int32 device tensor or None, G)."""
+    if groups is None:
+        if n_groups:
+            raise ValueError(f"{what}: n_groups without groups")
+        return None, 0
+    if torch.is_tensor(groups) and groups.is_cuda:
+        if n_groups is None:
+            raise ValueError(f"{what}: group ids on the device need n_groups (nothing here waits for the device)")
+        if groups.is_floating_point():
+            raise ValueError(f"{what}: groups must be integers, got {groups.dtype}")
+        ids = groups
+    else:
+        host = np.asarray(groups.cpu() if torch.is_tensor(groups) else groups)
+        if host.dtype.kind not in "iu":
+            raise ValueError(f"{what}: groups must be integers, got {host.dtype}")
+        if n_groups is None:
+            n_groups = int(host.max()) + 1 if host.size else 0
+        ids = torch.as_tensor(host.astype(np.int32))
+    if tuple(ids.shape) != (N,):
+        raise ValueError(f"{what}: groups must be (N,) = ({N},), got {tuple(ids.shape)}")
+    G = int(n_groups)
+    if not 0 <= G <= _lib.SKS_EVAL_MAX_GROUPS:
+        raise ValueError(f"{what}: n_groups = {G}, at most {_lib.SKS_EVAL_MAX_GROUPS}")
+    return (ids.to(device=dev, dtype=torch.int32).contiguous() if G else None), G
+
+
+ALIGN_MODES = {"rigid": _lib.SKS_ALIGN_RIGID, "similarity": _lib.SKS_ALIGN_SIMILARITY, "scale": _lib.SKS_ALIGN_SCALE}
+
+
+def _align_args(what, pred, gt, mode, valid):
+    """The checks the three aligned entries share -> pred, gt (N,P,3), single, mode number, valid (N,P) uint8 or None."""
+    if mode not in ALIGN_MODES:
+        raise ValueError(f"{what}: mode = {mode!r}, one of {sorted(ALIGN_MODES)}")
+    p, g, single = _poses(pred, gt, what)
+    N, P = p.shape[:2]
+    v = None
+    if valid is not None:
+        if not torch.is_tensor(valid) or not valid.is_cuda or valid.device != p.device:
+            raise ValueError(f"{what}: `valid` must be a tensor on the poses' device, {p.device}")
+        if valid.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"{what}: `valid` must be bool or uint8, got {valid.dtype}")
+        if tuple(valid.shape) != ((P,) if single else (N, P)):
+            raise ValueError(f"{what}: `valid` must be {'(P,)' if single else '(N,P)'} = {(P,) if single else (N, P)}, "
+                             f"got {tuple(valid.shape)}")
+        v = valid.reshape(N, P).contiguous()
+        v = v.view(torch.uint8) if v.dtype == torch.bool else v
+    return p, g, single, ALIGN_MODES[mode], v
+
+
+def _align(p, g, v, mode, aligned=None, transform=None, per_joint=None, mean=None):
+    ptr = lambda t: None if t is None else t.data_ptr()
+    N, P = p.shape[:2]
+    with torch.cuda.device(p.device):
+        rc = _lib.load().sks_align_poses(N, P, p.data_ptr(), g.data_ptr(), ptr(v), mode, ptr(aligned), ptr(transform),
+                                         ptr(per_joint), ptr(mean), _stream(p.device))
+    _lib.check(rc, "sks_align_poses")
+
+
+def align_poses(pred, gt, mode="similarity", valid=None, return_transform=False):
+    """pred, gt (N,P,3) float32 on the device -> pred after the best per-frame alignment onto gt, (N,P,3) float32.
+    `mode`: "rigid" (R, t), "similarity" (s, R, t: the alignment of PA-MPJPE) or "scale" (s alone, both poses relative to joint 0:
+    N-MPJPE's).  R is always a proper rotation.  `valid` (N,P) bool or uint8 on the device: the joints the fit uses; every
+    joint is transformed.  `return_transform=True`: also (scale (N,), rotation (N,3,3), translation (N,3)), float64 views of one
+    (N,13) block, with aligned = scale * rotation @ pred + translation.  A frame without a valid joint keeps pred and the
+    identity; a NaN in a valid joint (or, in "scale" mode, a masked joint 0) makes its own frame NaN.  A (P,3) pose gives results
+    without the frame axis.  One launch, one wavefront per frame, float64 inside (include/skelsplat_hip.h)."""
+    p, g, single, m, v = _align_args("align_poses", pred, gt, mode, valid)
+    N = p.shape[0]
+    aligned = torch.empty_like(p)
+    tr = torch.empty((N, 13), dtype=torch.float64, device=p.device) if return_transform else None
+    _align(p, g, v, m, aligned=aligned, transform=tr)
+    if not return_transform:
+        return aligned[0] if single else aligned
+    s, R, t = tr[:, 0], tr[:, 1:10].view(N, 3, 3), tr[:, 10:13]
+    return (aligned[0], (s[0], R[0], t[0])) if single else (aligned, (s, R, t))
+
+
+def aligned_pose_errors(pred, gt, mode="similarity", valid=None, per_joint=False):
+    """pred, gt (N,P,3) float32 on the device -> mean (N,) float32: the mean over the valid joints of ||gt - aligned||, aligned as
+    align_poses gives it ("similarity": the frame's PA-MPJPE, "scale": its N-MPJPE, "rigid": the rigid-aligned error; NaN for a
+    frame without a valid joint).  `per_joint=True`: returns (errors (N,P), mean), the errors of all joints, masked ones
+    included.  A (P,3) pose gives results without the frame axis.  One launch."""
+    p, g, single, m, v = _align_args("aligned_pose_errors", pred, gt, mode, valid)
+    N, P = p.shape[:2]
+    mean = torch.empty(N, dtype=torch.float32, device=p.device)
+    pj = torch.empty((N, P), dtype=torch.float32, device=p.device) if per_joint else None
+    _align(p, g, v, m, per_joint=pj, mean=mean)
+    if single:
+        mean, pj = mean[0], None if pj is None else pj[0]
+    return (pj, mean) if per_joint else mean
+
+
+def evaluate_sequence_aligned(pred, gt, groups=None, n_groups=None, valid=None):
+    """pred, gt (N,P,3) float32 on the device -> dict of float64 device tensors: `pa_mpjpe`, `n_mpjpe` (0-d: the mean over all
+    valid joints of all frames of aligned_pose_errors' per-joint errors in "similarity" and in "scale" mode), `pa_mpjpe_groups`,
+    `n_mpjpe_groups` ((n_groups,): the same per group; NaN for a group without valid joints).  `groups`, `n_groups` as
+    evaluate_sequence takes them; `valid` (N,P) as align_poses takes it.  Three launches; sums in float64 in a fixed order."""
+    what = "evaluate_sequence_aligned"
+    p, g, _, _, v = _align_args(what, pred, gt, "similarity", valid)
+    N, P = p.shape[:2]
+    dev = p.device
+    ids, G = _groups(what, groups, n_groups, N, dev)
+    lib = _lib.load()
+    nbytes = lib.sks_eval_sequence_aligned_scratch_bytes(N, P)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((1 + G, 2), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.sks_eval_sequence_aligned(N, P, p.data_ptr(), g.data_ptr(), None if v is None else v.data_ptr(),
+                                           None if ids is None else ids.data_ptr(), G, scratch.data_ptr(), nbytes, out.data_ptr(),
+                                           _stream(dev))
+    _lib.check(rc, what)
+    return dict(pa_mpjpe=out[0, 0], n_mpjpe=out[0, 1], pa_mpjpe_groups=out[1:, 0], n_mpjpe_groups=out[1:, 1])
 
 
 def check_report_args(report_steps, save_iterations):
