@@ -3,7 +3,7 @@
 other, train.py:74-99) -- but many frames per launch: noisy 2D detections of N frames -> DLT initial guesses -> 500
 iterations of the multi-view loop for every frame (loop.FramePipeline) -> MPJPE per frame.
 python examples/optimize_sequence.py [--frames 64] [--per-launch 16] [--streams 2] [--iters 500] [--init host|device|fuse] [--rigs R]
-    [--report] [--uncertainty] [--reject-px PX] [--corrupt K]
+    [--report] [--uncertainty] [--reject-px PX] [--corrupt K] [--images DIR [--image-frames 0,31,63]]
 --rigs R: the frames cycle through R jittered ring rigs (SyntheticScene seeds 0 .. R-1), as a dataset whose scenes bring their own
 cameras does; one rigs.RigBank holds them on the device and every batch names its frames' rigs (rig_ids).
 --init host (default): the DLT runs on the host, frame by frame, and its points are uploaded; --init device: the detections
@@ -24,6 +24,11 @@ report.evaluate_sequence over four synthetic "activities" (eval.py:115-142).  No
 covariances are read back as the pose's uncertainty on the device (skelsplat_amd/uncertainty.py): the share of ground-truth joints
 inside the 1 / 2 / 3-sigma ellipsoid overall and per joint (utils/analize_error_confidence_correlation.py's percent_inside_sigmas
 and .._per_joint) and the mean trace of the covariance.
+--images DIR: the reference's debug pictures (configs/*.yaml `debug.save_images`, train.py:279-304) of the frames --image-frames
+(default: the first, the middle and the last) -- heatmaps/heatmap_{view}.png, images/render_1_{view}.png, images/render_{view}.png,
+one sub-directory per frame -- made on the device while the timed sequence runs (pipe.set_debug_images, skelsplat_amd/preview.py)
+and written afterwards.  With --corrupt and --reject-px the misplaced blobs the rejection leaves in the heat-maps are there to see
+in heatmap_*.png.  Not with --rigs > 1.
 The curve falls from the reference's default start, --init fuse (21.7 -> 14.3 mm); from the DLT start (--init host / device) it
 RISES from 13.4 to 14.3 mm in the first steps: on this synthetic sequence (3 px of detection noise, exact cameras) the DLT already
 sits below the optimiser's fixed point, and the curve shows it."""
@@ -56,6 +61,8 @@ def main(argv=None):
     ap.add_argument("--uncertainty", action="store_true")
     ap.add_argument("--reject-px", type=float, default=None)
     ap.add_argument("--corrupt", type=int, default=0)
+    ap.add_argument("--images", default=None, metavar="DIR")
+    ap.add_argument("--image-frames", default=None, metavar="I,J,..")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     sc = SyntheticScene(args.dataset, n_views=args.views, seed=0, device=dev)
@@ -75,6 +82,10 @@ def main(argv=None):
         ap.error("--uncertainty measures against --report's ground truth: use the two together")
     if args.reject_px is not None and args.init != "device":
         ap.error("--reject-px rejects while triangulating on the device: use it with --init device")
+    if args.images is not None and args.rigs > 1:
+        ap.error("--images pictures frames seen by one rig: use it without --rigs")
+    if args.image_frames is not None and args.images is None:
+        ap.error("--image-frames chooses the frames of --images DIR")
     Pm = [triangulation.projection_matrices(rig) for rig in rigs]
 
     def host_init():
@@ -118,6 +129,10 @@ def main(argv=None):
             return optimise()
     run()                                                             # captures the hipGraphs
     torch.cuda.synchronize()
+    if args.images is not None:
+        chosen = ([int(x) for x in args.image_frames.split(",")] if args.image_frames
+                  else sorted({0, args.frames // 2, args.frames - 1}))
+        pipe.set_debug_images(chosen)       # from the next sequence on; the graphs captured above are replayed as they are
     t0 = time.perf_counter()
     out, init = run()
     torch.cuda.synchronize()
@@ -130,6 +145,10 @@ def main(argv=None):
           f"({args.frames / dt:.0f} frames/s, {args.per_launch} frames per launch on {args.streams} streams, {args.rigs} rig(s)); "
           f"mean MPJPE {e0:.2f} mm ({'fused predictions on the device' if args.init == 'fuse' else f'DLT on the {args.init}'}) "
           f"-> {e1:.2f} mm")
+    if args.images is not None:
+        dirs = pipe.images.save(args.images, [f"frame_{f:06d}" for f in pipe.images.frames])
+        print(f"debug pictures of frames {pipe.images.frames} (heat-maps, first and last render, {args.views} views each): "
+              + ", ".join(dirs))
     if args.reject_px is not None:
         plain = host_init()
         ep = np.mean([io.mpjpe(plain[f], gt[f]) for f in range(args.frames)])

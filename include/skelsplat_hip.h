@@ -767,6 +767,51 @@ int sks_eval_sequence_aligned(int N, int P, const float* pred, const float* gt, 
                               int n_groups, void* scratch, size_t scratch_bytes, double* out, void* stream);
 size_t sks_eval_sequence_aligned_scratch_bytes(int N, int P);
 
+/* 8-bit grey previews of renders and heat-maps: the reference's debug pictures (train.py:279-304, save_heatmaps / save_images),
+ * on the device (csrc/sks_preview.hip; added to sks_version 14: the number did not move).  Two launches per call on `stream`,
+ * nothing synchronises, no atomics; min and max are exact in any order, so every byte is the same from run to run.  Bad arguments
+ * are refused before any HIP call.  Device memory unless marked HOST.
+ *
+ * The fixed sequence of one view, all fp32, one rounding per operation:
+ *   1. s = p[0]; s += p[1]; ...; s += p[C-1]: the view's channels in ascending order, per pixel;
+ *   2. lo = min(s), hi = max(s) over the view's own h x w pixels; a NaN pixel makes both NaN, as torch.min does;
+ *   3. t = ((s - lo) / (hi - lo)) * 255.0f;
+ *   4. q = (t >= 0 && t <= 255) ? (uint8)trunc(t) : 0.
+ * Step 4 is the reference's `.astype(np.uint8)` wherever the reference is defined.  A flat view (hi == lo: 0 / 0) and a view
+ * that holds a NaN or an inf are undefined there (a NaN cast to uint8); HERE every pixel whose t is NaN or outside [0, 255] is 0
+ * by definition, so such a view is an all-zero picture, and minmax still reports the lo, hi it was made with.
+ *
+ * sks_preview_planes: planes (V,C,H,W) floats -> out (V,H,W) bytes, minmax (V,2) floats {lo, hi} or NULL.  1 <= C <=
+ *   SKS_MAX_CHANNELS, V <= 65535, W x H <= 2^31 - 1.  Pass A reads the planes once (16-byte loads when W % 4 == 0 and planes and
+ *   out are 16-byte aligned, scalar loads otherwise), writes the sum plane into `scratch` and one {min, max} partial per workgroup;
+ *   pass B reduces a view's partials, normalises and packs (one 16-byte store of 16 pixels per lane when W % 16 == 0 and the
+ *   bases are aligned, bytes otherwise).  scratch: sks_preview_scratch_bytes(V, W, H) bytes at least, 16-byte aligned.
+ *
+ * sks_preview_factors: the same picture of the heat-maps sks_heatmap_factors describes (row (V,J,H), col (V,J,W), cmin, den
+ *   (V,J); 1 <= V <= SKS_MAX_VIEWS) without a plane ever written: per pixel the very expression sks_heatmaps stores,
+ *   (row[y] * col[x] - cmin) / den, for j = 0 .. J-1 in order -- bit for bit sks_preview_planes over what sks_heatmaps would have
+ *   written, for finite factors.  (A joint whose row[y] and cmin are both zero contributes exactly +0 and is skipped.)  view_wh:
+ *   HOST V x {W,H} or NULL, every entry within [1, W] x [1, H]; W, H are the strides of row, col and out (the largest view), as in
+ *   sks_heatmap_totals; min and max run over a view's own pixels and the bytes of out outside them are written 0.
+ *
+ * sks_preview_scratch_bytes: host only; 0 for a shape either entry point refuses.
+ * sks_preview_launch: host only, which forms a plane-path call of W x H views takes (aligned != 0: every base pointer is a multiple
+ *   of 16): out[SKS_PREVIEW_LOAD_BYTES] = 16 or 4, out[SKS_PREVIEW_STORE_BYTES] = 16 or 1, out[SKS_PREVIEW_GROUPS_SUM] and
+ *   out[SKS_PREVIEW_GROUPS_PACK] = the workgroups per view of pass A and pass B (256 threads each, at most 256).  The factor
+ *   path's pass A takes one workgroup per band of ceil(H / 256) rows; its pass B is the plane path's. */
+#define SKS_PREVIEW_LOAD_BYTES   0
+#define SKS_PREVIEW_STORE_BYTES  1
+#define SKS_PREVIEW_GROUPS_SUM   2
+#define SKS_PREVIEW_GROUPS_PACK  3
+#define SKS_PREVIEW_LAUNCH_INTS  4
+int sks_preview_planes(int V, int C, int W, int H, const float* planes, void* scratch, float* minmax, unsigned char* out,
+                       void* stream);
+int sks_preview_factors(int V, int J, int W, int H, const float* row, const float* col, const float* cmin, const float* den,
+                        const int* view_wh /*HOST V x {W,H} or NULL*/, void* scratch, float* minmax, unsigned char* out,
+                        void* stream);
+size_t sks_preview_scratch_bytes(int V, int W, int H);
+int sks_preview_launch(int W, int H, int aligned, int* out /*HOST SKS_PREVIEW_LAUNCH_INTS*/);
+
 /* Measurement hook used by bench.py (no reference counterpart; state per HOST THREAD, like the error text): while enabled, the dominant kernel of sks_forward
  * (kind 0: forward compositor) and of sks_backward (kind 1: backward compositor) is bracketed by hipEvents recorded
  * on the caller's stream (the small path's kernels carry the pair on their own dispatch, hipExtLaunchKernelGGL).  The low 16

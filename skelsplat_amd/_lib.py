@@ -30,6 +30,7 @@ SKS_REPORT_MAX_SAVES = 8
 SKS_EVAL_MAX_GROUPS = 64
 SKS_CALIBRATION_MAX_K = 8
 SKS_ALIGN_RIGID, SKS_ALIGN_SIMILARITY, SKS_ALIGN_SCALE = 0, 1, 2
+SKS_PREVIEW_LAUNCH_INTS = 4
 
 
 SKS_NO_EARLY_FILL = 1 << 30
@@ -172,6 +173,10 @@ SIGNATURES = {
     "sks_align_poses": (_i, [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "sks_eval_sequence_aligned": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _vp]),
     "sks_eval_sequence_aligned_scratch_bytes": (_sz, [_i, _i]),
+    "sks_preview_planes": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sks_preview_factors": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sks_preview_scratch_bytes": (_sz, [_i, _i, _i]),
+    "sks_preview_launch": (_i, [_i, _i, _i, _vp]),
     "sks_prof_enable": (_i, [_i]),
     "sks_prof_spin": (_i, [C.c_double, _vp]),
     "sks_prof_read": (_i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
@@ -248,6 +253,18 @@ def masked_l2_launch(n_per_view):
     out = (_i * 2)()
     check(load().sks_masked_l2_launch(n_per_view, out), "sks_masked_l2_launch")
     return out[0], out[1]
+
+
+# sks_preview_launch's record: field name -> index (include/skelsplat_hip.h, SKS_PREVIEW_*)
+PREVIEW_LAUNCH_FIELDS = ("load_bytes", "store_bytes", "groups_sum", "groups_pack")
+
+
+def preview_launch(W, H, aligned=True):
+    """Which forms sks_preview_planes takes for views of W x H, as a dict over PREVIEW_LAUNCH_FIELDS (host only:
+    sks_preview_launch).  aligned: every base pointer is a multiple of 16."""
+    out = (_i * SKS_PREVIEW_LAUNCH_INTS)()
+    check(load().sks_preview_launch(W, H, 1 if aligned else 0, C.cast(out, _vp)), "sks_preview_launch")
+    return {name: out[i] for i, name in enumerate(PREVIEW_LAUNCH_FIELDS)}
 
 
 def prefill_planes(V, P, C_, W, H, flags=0):

@@ -3,8 +3,11 @@
 save_ply: scene/gaussian_model.py:250-281 (fields x,y,z,nx,ny,nz,f_dc_*,f_rest_*,opacity,scale_*,rot_*; binary little
 endian, float32) without the plyfile dependency; read_ply_xyz: what eval.py:32-33 reads through open3d;
 mpjpe / mpjpe_root_relative: eval.py:123-139; similarity_transform / pa_mpjpe / n_mpjpe: the aligned metrics the
-reference does not report (the host counterparts of report.align_poses / report.evaluate_sequence_aligned); evaluate: eval.py:91-171 (the directory walk around them)."""
+reference does not report (the host counterparts of report.align_poses / report.evaluate_sequence_aligned); evaluate: eval.py:91-171 (the directory walk around them);
+write_png_gray / read_png_gray: the 8-bit grey files of train.py:279-304 (save_images / save_heatmaps) without the PIL dependency."""
 import os
+import struct
+import zlib
 
 import numpy as np
 
@@ -48,6 +51,62 @@ def save_ply_arrays(path, gm, xyz, scaling, rotation, opacity):
     with open(path, "wb") as f:
         f.write(("\n".join(header) + "\n").encode("ascii"))
         f.write(np.ascontiguousarray(cols, dtype="<f4").tobytes())
+
+
+_PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
+
+
+def _png_chunk(kind, data):
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xffffffff)
+
+
+def write_png_gray(path, array_u8):
+    """An (H,W) uint8 array as an 8-bit greyscale, non-interlaced PNG (what PIL's Image.fromarray(..).save writes for such an
+    array, train.py:290-291, as far as the decoded pixels go).  Every row goes out with filter type 0 (none)."""
+    a = np.asarray(array_u8.detach().cpu().numpy() if hasattr(array_u8, "detach") else array_u8)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.size == 0:
+        raise ValueError(f"write_png_gray: an (H,W) uint8 array is needed, got {a.dtype} {a.shape}")
+    h, w = a.shape
+    raw = np.zeros((h, w + 1), dtype=np.uint8)      # column 0: the filter byte of each row
+    raw[:, 1:] = a
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(_PNG_MAGIC + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0, 0, 0, 0))
+                + _png_chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + _png_chunk(b"IEND", b""))
+
+
+def read_png_gray(path):
+    """The (H,W) uint8 array of a file write_png_gray wrote (8-bit grey, non-interlaced, filter type 0 on every row); anything
+    else is refused."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != _PNG_MAGIC:
+        raise ValueError(f"read_png_gray: {path} is not a PNG file")
+    pos, idat, shape = 8, [], None
+    while pos + 8 <= len(data):
+        n, kind = struct.unpack(">I4s", data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + n]
+        if struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])[0] != zlib.crc32(kind + body) & 0xffffffff:
+            raise ValueError(f"read_png_gray: {path}: bad checksum in chunk {kind!r}")
+        if kind == b"IHDR":
+            w, h, depth, colour, comp, filt, lace = struct.unpack(">IIBBBBB", body)
+            if (depth, colour, comp, filt, lace) != (8, 0, 0, 0, 0):
+                raise ValueError(f"read_png_gray: {path} is not an 8-bit greyscale, non-interlaced PNG")
+            shape = (h, w)
+        elif kind == b"IDAT":
+            idat.append(body)
+        elif kind == b"IEND":
+            break
+        pos += 12 + n
+    if shape is None or not idat:
+        raise ValueError(f"read_png_gray: {path} has no image")
+    raw = np.frombuffer(zlib.decompress(b"".join(idat)), dtype=np.uint8)
+    if raw.size != shape[0] * (shape[1] + 1):
+        raise ValueError(f"read_png_gray: {path}: {raw.size} bytes of image data for {shape[1]} x {shape[0]} pixels")
+    raw = raw.reshape(shape[0], shape[1] + 1)
+    if raw[:, 0].any():
+        raise ValueError(f"read_png_gray: {path} uses row filters (only files written by write_png_gray are read)")
+    return raw[:, 1:].copy()
 
 
 def read_ply_xyz(path):

@@ -374,6 +374,52 @@ class MultiViewLoop(_GroupLoop):
                 self._refresh_geometry()
             self._fbuf = (self._shard, self._sums)
 
+    # -- the reference's debug pictures (train.py:279-304, `debug.save_images`) of the loop's current scene --------
+    def _local_pictures(self, pictures_of):
+        """(V_local,H,W) uint8 from `pictures_of(slots, views, planes)` per size group: H, W the largest local view, a smaller
+        view in the leading part of its slab."""
+        if len(self.size_groups) == 1:
+            return pictures_of(*self.size_groups[0][:3])
+        W, H = max(w for w, _ in self.hset.sizes), max(h for _, h in self.hset.sizes)
+        out = torch.zeros((len(self.local_ids), H, W), dtype=torch.uint8, device=self.device)
+        for slots, vb, gt, _, idx in self.size_groups:
+            out[idx, :gt.shape[2], :gt.shape[3]] = pictures_of(slots, vb, gt)
+        return out
+
+    def _save_local(self, directory, name, pictures):
+        from .io import write_png_gray
+        host = pictures.cpu().numpy()
+        for k, v in enumerate(self.local_ids):      # (view-sharded: every rank writes its own views' files)
+            w, h = self.hset.sizes[k]
+            write_png_gray(os.path.join(directory, f"{name}_{v}.png"), host[k, :h, :w])
+        return pictures
+
+    def save_heatmaps(self, output_dir, name="heatmap"):
+        """train.py:294-304 for the current scene: {output_dir}/heatmaps/{name}_{view}.png, the channel sum of each local view's
+        pseudo-GT planes, min-max normalised, 8-bit grey (preview.channel_sum_u8).  Returns the (V_local,H,W) uint8 pictures on
+        the device.  Reads them back once; the loop's state is not touched."""
+        from .preview import channel_sum_u8
+        if self.hset is None:
+            raise ValueError("save_heatmaps: this rank holds no view")
+        with torch.no_grad():
+            pictures = self._local_pictures(lambda slots, vb, gt: channel_sum_u8(gt))
+        return self._save_local(os.path.join(output_dir, "heatmaps"), name, pictures)
+
+    def save_images(self, output_dir, name="render"):
+        """train.py:279-291 for the current parameters: {output_dir}/images/{name}_{view}.png, each local view rendered over a
+        black background, clamped to [0, 1], channels summed, min-max normalised, 8-bit grey (preview.render_preview: a
+        workspace of its own -- the loop's recorded plans and captured graphs are not touched).  name="render_1" after the first
+        iteration is the reference's other call.  Returns the (V_local,H,W) uint8 pictures on the device."""
+        from .preview import render_preview
+        if self.hset is None or self.view_grad_fn is not None:
+            raise ValueError("save_images: this rank renders no view")
+        gm, P = self.gm, self.P
+        with torch.no_grad():
+            args = (gm._xyz.detach(), gm.get_scaling.detach(), gm.get_rotation.detach(), gm.get_opacity.detach(),
+                    gm.get_features.detach().reshape(P, -1))
+            pictures = self._local_pictures(lambda slots, vb, gt: render_preview(vb, *args, antialiasing=self.antialiasing))
+        return self._save_local(os.path.join(output_dir, "images"), name, pictures)
+
     def _refresh_geometry(self):
         """The fused tail's persistent geometry from the parameters as they are now (in place once it exists)."""
         gm = self.gm
@@ -882,6 +928,28 @@ def _sequence_gaussians(loop, out):
     return SequenceGaussians(out)
 
 
+def _sequence_images(loop, N):
+    """optimize_sequence's `images`: None for a loop whose debug pictures are off (set_debug_images)."""
+    if loop._debug_frames is None:
+        return None
+    from .preview import SequenceImages
+    va = loop.views_all
+    return SequenceImages(loop._debug_frames, N, loop.V, va.W, va.H, loop.device, va.sizes[:loop.V] if va.mixed else None)
+
+
+def _debug_frames(loop, frames):
+    """set_debug_images' argument -> None (off) or a tuple of sequence indices >= 0."""
+    if frames is None:
+        return None
+    if loop.rigs is not None:
+        raise ValueError("set_debug_images: the debug pictures render a frame in its own cameras from HOST scalars; a loop over "
+                         "a rig bank keeps them on the device (picture such a frame with preview.render_preview and its rig)")
+    chosen = tuple(int(f) for f in frames)
+    if not chosen or min(chosen) < 0:
+        raise ValueError(f"set_debug_images: frames = {list(frames)!r} must be sequence indices >= 0, at least one (None: off)")
+    return chosen
+
+
 def _frame_criterion(early_stopping):
     """FrameBatchLoop's `early_stopping` -> None (off) or (window, tolerance) of the reference's criterion, which the frame
     batch runs per frame on the device; anything else is refused."""
@@ -1000,6 +1068,11 @@ class FrameBatchLoop(_GroupLoop):
         self.keep_gaussians = bool(keep_gaussians)
         self.gaussians = None
         self._gt_next = None    # set_ground_truth's tensor, until the next new_scenes / optimize_sequence takes it
+        # set_debug_images: the sequence indices optimize_sequence pictures (preview.SequenceImages in `images`); off: nothing is
+        # allocated and nothing more is enqueued
+        self._debug_frames = None
+        self.images = None
+        self._frame_views = None
         self._sched, self._lrs, self._adam, self._limb = _optimiser_arrays(gm.opt_cfg, dataset, self.lambda_consistency)
         cams_all = [cameras[k % V] for k in range(F * V)]
         self._cams_all = cams_all
@@ -1186,6 +1259,41 @@ class FrameBatchLoop(_GroupLoop):
         self.iteration = 0
         return self
 
+    def set_debug_images(self, frames):
+        """The reference's debug pictures (configs/*.yaml `debug.save_images`, train.py:113-114, 143-144, 236-237) for the frames
+        with these sequence indices, from now on: every `optimize_sequence` fills `self.images` (a preview.SequenceImages) with
+        each chosen frame's heat-map picture and the picture of its render before the first and after the last iteration, all
+        on the device -- the heat-maps and the first render enqueued right behind the batch's new_scenes, the last render where
+        the joints are copied, on the batch's own stream; nothing is read back until `images.save(dir)`.  The pictures stay
+        outside the captured graphs and a group's launch sequence is the same with and without them.  With them on, a batch that
+        holds a chosen frame enqueues one heat-map picture of all its views and two dense forwards per chosen frame (a debug
+        path: preview.SequenceImages says what that is); other batches enqueue nothing more.  `None` switches them off: nothing
+        is allocated or enqueued and `images` is None after the next sequence.  Returns the loop."""
+        self._debug_frames = _debug_frames(self, frames)
+        return self
+
+    def frame_views(self, i):
+        """The ViewBatch of frame i's V views for a dense forward of that frame alone (the debug pictures): the loop's cameras,
+        which every frame of a batch shares."""
+        if self._frame_views is None:
+            self._frame_views = R.ViewBatch.from_cameras(self._cams_all[:self.V], allow_mixed=True)
+        return self._frame_views
+
+    def heatmap_pictures(self):
+        """((F x V,H,W) uint8, (F x V,2) float32 {min, max}) of the batch's pseudo-GT as it stands: preview.heatmap_preview of
+        the factors, or preview.channel_sum_u8 of the planes (factored=False); H, W the largest view."""
+        from .preview import channel_sum_u8, heatmap_preview
+        if self.factored:
+            return heatmap_preview(self.factors, self.views_all, return_minmax=True)
+        if len(self.size_groups) == 1:
+            return channel_sum_u8(self.size_groups[0][2], return_minmax=True)
+        va = self.views_all
+        out = torch.zeros((va.V, va.H, va.W), dtype=torch.uint8, device=self.device)
+        mm = torch.empty((va.V, 2), dtype=torch.float32, device=self.device)
+        for slots, vb, gt, stats, idx in self.size_groups:
+            out[idx, :vb.H, :vb.W], mm[idx] = channel_sum_u8(gt, return_minmax=True)
+        return out, mm
+
     def set_ground_truth(self, gt):
         """The ground truth of the NEXT batch or sequence (a loop with `report_steps`): (F,P,3) for `new_scenes`, (N,P,3) for
         `optimize_sequence`, float32 on the loop's device.  The next of those calls takes it -- the errors it reports are against
@@ -1292,13 +1400,14 @@ class FrameBatchLoop(_GroupLoop):
         if self._sel is not None:
             self._sel.check()
 
-    def _next_batch(self, pts, p2d, b, initial=None, rig_ids=None, p3d=None, gt=None, consensus=None):
+    def _next_batch(self, pts, p2d, b, initial=None, rig_ids=None, p3d=None, gt=None, consensus=None, images=None):
         """new_scenes for the frames b .. b + F of a sequence (a short last batch is filled up by repeating its final
         frame, rig included); `pts` None: triangulated from the detections.  `initial` (N,P,3): receives the batch's initial
         joints.  `rig_ids`: None or the sequence's (N,) ids as _sequence_rig_ids left them.  `p3d`: None or the sequence's
         (N,V,J,3) predictions, fused into the initial joints instead of the triangulation (`pts` None).  `gt`: None or the sequence's
         (N,P,3) ground truth as _checked_gt left it.  `consensus`: None or the
-        sequence's (inliers (N,V,J), n_consensus (N,J)), which receive the batch's rows on the current stream."""
+        sequence's (inliers (N,V,J), n_consensus (N,J)), which receive the batch's rows on the current stream.  `images`: None or
+        the sequence's preview.SequenceImages, which pictures the batch's chosen frames right behind new_scenes."""
         N, F = p2d.shape[0], self.F
         if gt is not None:
             self._gt_next = gt[b:b + F] if b + F <= N else gt[[min(b + i, N - 1) for i in range(F)]]
@@ -1316,6 +1425,8 @@ class FrameBatchLoop(_GroupLoop):
         if consensus is not None:
             consensus[0][b:min(b + F, N)] = self.inliers[:min(F, N - b)]
             consensus[1][b:min(b + F, N)] = self.n_consensus[:min(F, N - b)]
+        if images is not None:
+            images.begin(self, b, min(F, N - b))
 
     def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, return_initial=False, rig_ids=None,
                           poses_3d=None):
@@ -1336,7 +1447,9 @@ class FrameBatchLoop(_GroupLoop):
         `set_ground_truth` before this call, NaN without one.
         A loop built with keep_gaussians=True: afterwards `self.gaussians` (an uncertainty.SequenceGaussians) holds every frame's
         xyz -- the tensor returned --, scaling, rotation and opacity as the frame ended, what scene.save_h36m writes
-        (io.save_ply_arrays) and uncertainty.joint_uncertainty reads; None otherwise."""
+        (io.save_ply_arrays) and uncertainty.joint_uncertainty reads; None otherwise.
+        After `set_debug_images(frames)`: `self.images` (a preview.SequenceImages) holds the chosen frames' debug pictures; None
+        otherwise."""
         pts, p2d, N = _sequence_inputs(points, poses_2d)
         p3d = _sequence_predictions(points, poses_3d, N)
         _checked_reject(self._reject, points, poses_3d, "optimize_sequence")
@@ -1349,12 +1462,15 @@ class FrameBatchLoop(_GroupLoop):
         out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
         initial = torch.empty_like(out) if return_initial else None
         self.gaussians = _sequence_gaussians(self, out)
+        self.images = _sequence_images(self, N)
         for b in range(0, N, F):
-            self._next_batch(pts, p2d, b, initial, ids, p3d, gt, cons)
+            self._next_batch(pts, p2d, b, initial, ids, p3d, gt, cons, self.images)
             res = self.run(iterations, groups_per_graph)
             out[b:min(b + F, N)] = res[:min(F, N - b)]
             if self.gaussians is not None:
                 self.gaussians.take(self, b, min(F, N - b))
+            if self.images is not None:
+                self.images.take(self, b, min(F, N - b))
             if self.report is not None:
                 self.report.take(self, b, min(F, N - b))
         self.check_rigs()
@@ -1383,6 +1499,7 @@ class FramePipeline:
         self.report = None           # loops that report: report.SequenceReport of the last optimize_sequence
         self.gaussians = None        # keep_gaussians=True: uncertainty.SequenceGaussians of the last optimize_sequence
         self._gt_next = None         # set_ground_truth's tensor, until the next optimize_sequence takes it
+        self.images = None           # set_debug_images: preview.SequenceImages of the last optimize_sequence
         self.inliers = self.n_consensus = None     # optimize_sequence with rejection: (N,V,J) bool, (N,J) int32
 
     def set_outlier_rejection(self, reject_px=None, min_inliers=3):
@@ -1390,6 +1507,14 @@ class FramePipeline:
         detections while it triangulates (None: off again).  Returns the pipeline."""
         for fb in self.loops:
             fb.set_outlier_rejection(reject_px, min_inliers)
+        return self
+
+    def set_debug_images(self, frames):
+        """FrameBatchLoop.set_debug_images of every loop: from now on optimize_sequence pictures the frames with these sequence
+        indices into `self.images` (a preview.SequenceImages), each batch's pictures enqueued on its own stream (None: off again,
+        and `images` is None after the next sequence).  Returns the pipeline."""
+        for fb in self.loops:
+            fb.set_debug_images(frames)
         return self
 
     def set_ground_truth(self, gt):
@@ -1418,7 +1543,9 @@ class FramePipeline:
         of all N frames, copied on each batch's own stream -- the errors against the (N,P,3) ground truth given to
         `set_ground_truth` before this call, NaN without one.  The return value is the same.
         Loops built with keep_gaussians=True: `self.gaussians` (an uncertainty.SequenceGaussians) holds every frame's scaling,
-        rotation and opacity next to the joints returned, copied on each batch's own stream; None otherwise."""
+        rotation and opacity next to the joints returned, copied on each batch's own stream; None otherwise.
+        After `set_debug_images(frames)`: `self.images` holds the chosen frames' debug pictures, made on each batch's own stream;
+        None otherwise."""
         pts, p2d, N = _sequence_inputs(points, poses_2d)
         p3d = _sequence_predictions(points, poses_3d, N)
         _checked_reject(self.loops[0]._reject, points, poses_3d, "optimize_sequence")
@@ -1431,6 +1558,7 @@ class FramePipeline:
         out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
         initial = torch.empty_like(out) if return_initial else None
         self.gaussians = _sequence_gaussians(self.loops[0], out)
+        self.images = _sequence_images(self.loops[0], N)
         cur = torch.cuda.current_stream(self.device)
         starts = list(range(0, N, F))
         if self.loops[0]._es is not None:
@@ -1448,7 +1576,7 @@ class FramePipeline:
             active = list(zip(self.loops, self.streams, starts[w:w + S]))
             for fb, st, b in active:
                 with torch.cuda.stream(st):
-                    fb._next_batch(pts, p2d, b, initial, ids, p3d, gt, cons)
+                    fb._next_batch(pts, p2d, b, initial, ids, p3d, gt, cons, self.images)
             for k in range(0, iterations, max(int(interleave), 1)):
                 for fb, st, b in active:
                     with torch.cuda.stream(st):
@@ -1458,6 +1586,8 @@ class FramePipeline:
                     out[b:min(b + F, N)] = fb.xyz[:min(F, N - b)]
                     if self.gaussians is not None:
                         self.gaussians.take(fb, b, min(F, N - b))
+                    if self.images is not None:
+                        self.images.take(fb, b, min(F, N - b))
                     if self.report is not None:
                         self.report.take(fb, b, min(F, N - b))
         for st in self.streams:
@@ -1483,7 +1613,7 @@ class FramePipeline:
             if b is None:
                 return None
             with torch.cuda.stream(st):
-                fb._next_batch(pts, p2d, b, initial, rig_ids, p3d, gt, cons)
+                fb._next_batch(pts, p2d, b, initial, rig_ids, p3d, gt, cons, self.images)
             return [fb, st, b, 0]
 
         step = max(int(interleave), 1)
@@ -1502,6 +1632,8 @@ class FramePipeline:
                         self.stopped_at[b:b + n] = fb._es_state[:n, 1]      # (0: the frame ran to the end)
                         if self.gaussians is not None:
                             self.gaussians.take(fb, b, n)
+                        if self.images is not None:
+                            self.images.take(fb, b, n)
                         if self.report is not None:
                             self.report.take(fb, b, n)
                         slot = take(fb, st)
