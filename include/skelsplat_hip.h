@@ -127,6 +127,19 @@ int sks_scratch_bytes(int V, int P, int C, int W, int H, size_t bin_capacity,
 #define SKS_REGIME_INTS       16
 int sks_launch_regime(int V, int P, int C, int W, int H, unsigned flags, int out_aligned128, int* out);
 
+/* The list lengths at which the binned path changes how it orders or walks a tile's list.  Host only, no GPU call, like
+ * sks_launch_regime: the values are the kernels' own constants, so a test can place a list on either side of each and fails loudly
+ * when one is retuned.  out: SKS_LIST_REGIME_INTS ints, indexed by the names below. */
+#define SKS_LIST_WAVE_SORT     0   /* lists up to this many entries are ranked by the forward's wavefront as it loads them */
+#define SKS_LIST_WAVE_K        1   /* ... up to this many: sorted in one wavefront's registers ahead of its compositing */
+#define SKS_LIST_SORT_LDS      2   /* ... up to this many: sorted by the scatter workgroup in LDS; longer ones in global memory */
+#define SKS_LIST_LONG_LIST     3   /* a band with up to this many lists beyond SKS_LIST_WAVE_K remembers their columns; with more
+                                      it finds them again by a walk over all columns */
+#define SKS_LIST_CLASSES       4   /* tile classes by list length: class c holds [2^c, 2^(c+1)), the last one the rest */
+#define SKS_LIST_BAND_THREADS  5   /* threads of the workgroup that scatters a band and sorts its long lists */
+#define SKS_LIST_REGIME_INTS   8
+int sks_list_regime(int* out);
+
 /* Replaces _C.rasterize_gaussians (DGR/rasterize_points.cu:35-124 -> rasterizer_impl.cu:198-341).
  * features: (P,C) -- the reference reads them from `sh` with M == 1.
  * Outputs: out_color (V,C,H,W), out_invdepth (V,1,H,W), radii (V,P); every element is written

@@ -128,6 +128,7 @@ SIGNATURES = {
     "sks_version": (_i, []),
     "sks_scratch_bytes": (_i, [_i, _i, _i, _i, _i, _sz, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     "sks_launch_regime": (_i, [_i, _i, _i, _i, _i, _u, _i, C.POINTER(_i)]),
+    "sks_list_regime": (_i, [C.POINTER(_i)]),
     "sks_forward": (_i, [ct for _, ct in FORWARD_PARAMS]),
     "sks_backward": (_i, [ct for _, ct in BACKWARD_PARAMS]),
     "sks_forward_backward": (_i, [ct for _, ct in FORWARD_BACKWARD_PARAMS]),
@@ -245,6 +246,19 @@ def launch_regime(V, P, C_, W, H, flags=0, out_aligned128=True):
     out = (_i * REGIME_INTS)()
     check(load().sks_launch_regime(V, P, C_, W, H, flags, 1 if out_aligned128 else 0, out), "sks_launch_regime")
     return {name: out[i] for i, name in enumerate(REGIME_FIELDS)}
+
+
+# sks_list_regime's record: field name -> index (include/skelsplat_hip.h, SKS_LIST_*)
+LIST_REGIME_FIELDS = ("wave_sort", "wave_k", "sort_lds", "long_list", "classes", "band_threads")
+LIST_REGIME_INTS = 8
+
+
+def list_regime():
+    """The list lengths at which the binned path switches sorter or walk, as a dict over LIST_REGIME_FIELDS (host only:
+    sks_list_regime)."""
+    out = (_i * LIST_REGIME_INTS)()
+    check(load().sks_list_regime(out), "sks_list_regime")
+    return {name: out[i] for i, name in enumerate(LIST_REGIME_FIELDS)}
 
 
 def masked_l2_launch(n_per_view):

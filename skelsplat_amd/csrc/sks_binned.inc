@@ -306,8 +306,7 @@ __global__ __launch_bounds__(BAND_TC) void k_bin_band_count(int P, int gx, Geom 
 // Lists longer than a wavefront (never on the skeleton scenes): ascending sort of the (depth bits << 32 | index) keys through the
 // whole workgroup's all-ascending bitonic network with virtual +inf padding (in LDS up to SORT_LDS keys, else in the still unused
 // partial-sum rows), then the records are written again in that order.  Called by every thread of the workgroup that placed the
-// tile's records (their stores are drained and fenced by the caller).
-constexpr int SORT_LDS = 2048;
+// tile's records (their stores are drained and fenced by the caller).  (SORT_LDS: sks_common.inc)
 __device__ inline void sort_long_tile(int v, int P, int gx, int tile, size_t cap, const Geom& g, const Bin& b, unsigned long long* s)
 {
     const int tid = threadIdx.x;
@@ -352,8 +351,7 @@ __device__ inline void sort_long_tile(int v, int P, int gx, int tile, size_t cap
 // lane holds its whole records in registers before the first one is written back to its position.  Called by the FORWARD's
 // wavefront that owns the tile, right before it composites it: the lists of this size are spread over the whole launch there
 // (inside k_bin_band_scatter they were 6 us on the critical path of the few bands that hold them all); only lists beyond
-// 64 * WSORT_K entries are sorted ahead of the forward, by k_bin_band_scatter's workgroup-wide network.
-constexpr int WSORT_K = 4;
+// 64 * WSORT_K entries are sorted ahead of the forward, by k_bin_band_scatter's workgroup-wide network.  (WSORT_K: sks_common.inc)
 __device__ __forceinline__ void sort_list_wave(float4* __restrict__ e_co, float4* __restrict__ e_xyd, uint4* __restrict__ e_ids, size_t eb, int n)
 {
     const int lane = threadIdx.x & 63;
@@ -405,8 +403,7 @@ __global__ __launch_bounds__(BAND_TS) void k_bin_band_scatter(int P, int gx, siz
 {
     extern __shared__ uint32_t s_band[];          // [gx] cursors, [gx] channel masks
     __shared__ unsigned long long s_sort[SORT_LDS];
-    constexpr int LONG_LIST = 256;                 // long tiles of the band remembered by column (more: found again by a walk)
-    __shared__ int s_nlong;
+    __shared__ int s_nlong;                       // long tiles of the band, up to LONG_LIST of them remembered by column
     __shared__ unsigned short s_long[LONG_LIST];
     __shared__ unsigned s_any[SKS_MAX_CHANNELS];
     uint32_t* s_cur = s_band;

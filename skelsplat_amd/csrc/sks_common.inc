@@ -279,6 +279,10 @@ inline size_t geom_bytes(int V, int P, int W, int H, int C)
 // registers and writes them back in that order (with each entry's strip mask), so the backward and the export read sorted
 // lists; longer ones are sorted in place by k_bin_band_scatter before the forward.
 constexpr int BIN_WAVE_SORT = 64;
+// The other list-length switches of the binned path (sks_binned.inc), kept here so that sks_list_regime reports what the kernels use:
+constexpr int WSORT_K = 4;             // lists of BIN_WAVE_SORT + 1 .. 64 * WSORT_K entries: sort_list_wave, in the forward's wavefront
+constexpr int SORT_LDS = 2048;         // longer ones: sort_long_tile, in LDS up to SORT_LDS keys, beyond in the partial-sum rows
+constexpr int LONG_LIST = 256;         // long tiles of a band remembered by column in k_bin_band_scatter (more: found again by a walk)
 constexpr int BIN_ROWS = 2;            // partial-sum rows per slot: one per 8-row half of the tile (a wavefront of the backward)
 constexpr int BIN_CLASSES = 8;         // tile classes by list length: class c holds lengths [2^c, 2^(c+1)), the last one the rest
 constexpr int BIN_HDR_CLASS = 8;        // Bin::hdr[BIN_HDR_CLASS + g * BIN_CLASSES + c]: number of non-empty tiles of class c in view group g

@@ -529,6 +529,19 @@ int sks_launch_regime(int V, int P, int C, int W, int H, unsigned flags, int out
     return 0;
 }
 
+int sks_list_regime(int* out)
+{
+    if (!out) return fail(-2, "sks_list_regime: out must be provided");
+    memset(out, 0, SKS_LIST_REGIME_INTS * sizeof(int));
+    out[SKS_LIST_WAVE_SORT] = BIN_WAVE_SORT;
+    out[SKS_LIST_WAVE_K] = 64 * WSORT_K;
+    out[SKS_LIST_SORT_LDS] = SORT_LDS;
+    out[SKS_LIST_LONG_LIST] = LONG_LIST;
+    out[SKS_LIST_CLASSES] = BIN_CLASSES;
+    out[SKS_LIST_BAND_THREADS] = BAND_TS;
+    return 0;
+}
+
 }  // extern "C"
 
 namespace {

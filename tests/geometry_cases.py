@@ -71,7 +71,6 @@ def _pick_seams(seams, n):
 
 def make(name, W, H, P, C, V=1, seed=0, dense=True, force_binned=False, extras=False, claims=None, flags=0):
     """extras: the backward gets a background and an inverse-depth gradient."""
-    from skelsplat_amd.scene import Camera
     rng = np.random.default_rng(1000 + seed)
     gx, gy = (W + 15) // 16, (H + 15) // 16
     c = Case()
@@ -145,11 +144,19 @@ def make(name, W, H, P, C, V=1, seed=0, dense=True, force_binned=False, extras=F
         c.feat = np.zeros((P, C), np.float32)
         c.feat[np.arange(P), np.arange(P) % C] = 1.0
     c.bg = rng.uniform(0.1, 0.9, C).astype(np.float32) if extras else None
-    K = np.array([[F, 0.0, 0.5 * W], [0.0, F, 0.5 * H], [0.0, 0.0, 1.0]])
-    c.cams = [Camera(v, np.eye(3), np.array([0.25 * (v % 4), -0.25 * ((v // 4) % 4), 0.125 * (v % 3)]), K, W, H) for v in range(V)]
-    c.ocams = [orc.Cam(W, H, math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5), cam.world_view_transform.numpy(),
-                       cam.full_proj_transform.numpy()) for cam in c.cams]
+    c.cams, c.ocams = cameras(W, H, V)
     return c
+
+
+def cameras(W, H, V):
+    """The V near-orthographic cameras of a W x H scene (identity rotation, focal length F, a sub-pixel shift per view), for the
+    device and for the oracle."""
+    from skelsplat_amd.scene import Camera
+    K = np.array([[F, 0.0, 0.5 * W], [0.0, F, 0.5 * H], [0.0, 0.0, 1.0]])
+    cams = [Camera(v, np.eye(3), np.array([0.25 * (v % 4), -0.25 * ((v // 4) % 4), 0.125 * (v % 3)]), K, W, H) for v in range(V)]
+    ocams = [orc.Cam(W, H, math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5), cam.world_view_transform.numpy(),
+                     cam.full_proj_transform.numpy()) for cam in cams]
+    return cams, ocams
 
 
 def host_bytes(c):
@@ -316,19 +323,22 @@ GRADS = (("means3D", "dL_dmeans3D"), ("means2D", "dL_dmeans2D"), ("opacities", "
 class Run:
     """A case on the device with its upstream gradients and the oracle's forward and backward of every view."""
 
-    def __init__(self, c, dev):
+    def __init__(self, c, dev, fwd=None, bound=None):
+        """fwd: the oracle's forward of every view where the caller has it already; bound: True = the gradients are held to the
+        oracle's computed rounding bound (default: the two tallest images only)."""
         import torch
         from skelsplat_amd import rasterizer as R
         self.c = c
         self.regime = check_claims(c)
         self.dev = dev
-        self.bound = c.H >= 1 << 19      # pixel coordinates near 2**19 leave fp32 ~0.03 px: the oracle's computed rounding bound
+        # pixel coordinates near 2**19 leave fp32 ~0.03 px: the oracle's computed rounding bound
+        self.bound = c.H >= 1 << 19 if bound is None else bool(bound)
         t = lambda a: None if a is None else torch.tensor(np.ascontiguousarray(a, dtype=np.float32), device=dev)
         self.views = R.ViewBatch.from_cameras([cam.to(dev) for cam in c.cams])
         self.args = (t(c.means), t(c.feat), t(c.opac), t(c.scales), t(c.quats), None)
         dLc, dLi = draw_dL(c)
         self.dLc, self.dLi, self.bg = t(dLc), t(dLi), t(c.bg)
-        self.fwd = [oracle_forward(c, v) for v in range(c.V)]
+        self.fwd = [oracle_forward(c, v) for v in range(c.V)] if fwd is None else fwd
         self.bwd = [oracle_backward(c, v, self.fwd[v], dLc, dLi, bounds=self.bound) for v in range(c.V)]
 
     def nan_workspace(self, **kw):
@@ -355,11 +365,12 @@ def held_nan(ws, c, dev):
     return (ws.get(("fwd", "color"), (c.V, c.C, c.H, c.W), torch.float32, dev), ws.get(("fwd", "invdepth"), (c.V, 1, c.H, c.W), torch.float32, dev))
 
 
-def check_forward_bits(run):
+def check_forward_bits(run, **kw):
+    """kw: further switches of the forward (a bin_capacity, check_capacity)."""
     from skelsplat_amd import rasterizer as R
     c = run.c
     ws = run.nan_workspace()
-    color, inv, radii, st, final_T, n_contrib = run.forward(ws, want_aux=True)
+    color, inv, radii, st, final_T, n_contrib = run.forward(ws, want_aux=True, **kw)
     assert color.data_ptr() == held_nan(ws, c, run.dev)[0].data_ptr(), "the forward did not render into the NaN-filled outputs"
     binned = run.regime["path"] == _lib.PATH_BINNED
     if binned:
@@ -379,16 +390,19 @@ def check_forward_bits(run):
             assert np.array_equal(pl[v, :o["R"]].cpu().numpy().astype(np.uint32), o["point_list"]), f"view {v}: point_list"
 
 
-def check_gradients(run, stats=None):
-    """stats: a dict that receives the largest bound excess per gradient (the tall cases)."""
+def check_gradients(run, stats=None, want_dfeatures=True):
+    """stats: a dict that receives the largest bound excess per gradient (the cases held to the computed bound).
+    want_dfeatures=False: the backward that skips the channels no Gaussian of a tile has a feature on; six gradients."""
     import torch
     from tests import util
     c = run.c
     _, _, _, st = run.forward()
-    g = run.backward(st, want_dfeatures=True)
+    g = run.backward(st, want_dfeatures=want_dfeatures)
     torch.cuda.synchronize()
     failures = []
     for key, oname in GRADS:
+        if g[key] is None and not want_dfeatures and key == "features":
+            continue
         got = g[key].cpu().numpy()
         for v in range(c.V):
             want = run.bwd[v][oname]

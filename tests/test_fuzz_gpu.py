@@ -91,3 +91,12 @@ def test_random_shapes_at_the_geometry_boundaries(device, seed):
     from tests.geometry_cases import run_case as run_geom_case
     r = run_geom_case(seed, device)
     assert r["visible"] > 0 and r["grad"] > 0
+
+
+@pytest.mark.parametrize("seed", range(600, 612))
+def test_random_list_lengths_at_the_sorter_thresholds(device, seed):
+    """Tile lists drawn around the lengths at which the binned path changes sorter (tests/list_length_cases.py fuzz_case: +- 1,
+    +- 64; equal depths, a half-tile that saturates early, every channel form)."""
+    from tests.list_length_cases import run_case as run_lists_case
+    r = run_lists_case(seed, device)
+    assert r["n_contrib"] > 0.75 * r["longest"] and r["grad"] > 0
