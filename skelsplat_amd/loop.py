@@ -22,6 +22,8 @@ import torch.distributed as dist
 
 from . import rasterizer as R
 from ._group import next_group
+from ._sequence import SequenceRun, _accept_gt, _checked_gt, _checked_reject, _debug_frames, _rejection
+from ._sequence import _sequence_predictions, _sequence_rig_ids     # noqa: F401  (callers and tests reach them as loop.<name>)
 from .scene import DATASETS
 
 
@@ -817,139 +819,6 @@ class MultiViewLoop(_GroupLoop):
         return self.gm._xyz.detach()
 
 
-def _sequence_inputs(points, poses_2d):
-    """optimize_sequence's (points or None, detections, N): tensors stay where they are, arrays become CPU tensors."""
-    p2d = poses_2d if torch.is_tensor(poses_2d) else torch.as_tensor(np.asarray(poses_2d))
-    if points is None:
-        return None, p2d, p2d.shape[0]
-    pts = points if torch.is_tensor(points) else torch.as_tensor(np.asarray(points))
-    if p2d.shape[0] != pts.shape[0]:
-        raise ValueError(f"{pts.shape[0]} frames of points, {p2d.shape[0]} of detections")
-    return pts, p2d, pts.shape[0]
-
-
-def _rejection(reject_px, min_inliers):
-    """set_outlier_rejection's arguments -> None (off) or the checked (reject_px, min_inliers)."""
-    if reject_px is None:
-        return None
-    from .triangulation import _checked_rejection
-    return _checked_rejection(reject_px, min_inliers)
-
-
-def _checked_reject(reject, points, poses_3d, who):
-    """`reject`: a loop's set_outlier_rejection setting.  It acts on the triangulation of the initial joints alone: refused
-    beside explicit points or poses_3d.  Returns (reject_px or None, min_inliers)."""
-    if reject is None:
-        return None, 3
-    if points is not None:
-        raise ValueError(f"{who}: outlier rejection (set_outlier_rejection) acts while the initial joints are triangulated "
-                         "(points=None); explicit points are taken as they are -- switch it off with set_outlier_rejection(None)")
-    if poses_3d is not None:
-        raise ValueError(f"{who}: outlier rejection (set_outlier_rejection) belongs to the triangulation; fusing poses_3d is a "
-                         "different estimator and takes every kept view -- switch it off with set_outlier_rejection(None)")
-    return reject
-
-
-def _sequence_consensus(loop, reject, N):
-    """optimize_sequence's (inliers (N,V,J) bool, n_consensus (N,J) int32) on the device, None without rejection."""
-    if reject is None:
-        return None
-    return (torch.empty((N, loop.V, loop.P), dtype=torch.bool, device=loop.device),
-            torch.empty((N, loop.P), dtype=torch.int32, device=loop.device))
-
-
-def _sequence_predictions(points, poses_3d, N):
-    """optimize_sequence's `poses_3d` -> None or the (N,V,J,3) predictions as a tensor where they are (arrays: on the host)."""
-    if poses_3d is None:
-        return None
-    if points is not None:
-        raise ValueError("optimize_sequence: poses_3d are fused into the initial joints when points is None; give one of the two")
-    p3d = poses_3d if torch.is_tensor(poses_3d) else torch.as_tensor(np.asarray(poses_3d))
-    if p3d.dim() != 4 or p3d.shape[0] != N or p3d.shape[-1] != 3:
-        raise ValueError(f"poses_3d must be (N,V,J,3) with N = {N} frames like poses_2d, got {tuple(p3d.shape)}")
-    return p3d
-
-
-def _sequence_rig_ids(sel, rig_ids, N):
-    """optimize_sequence's `rig_ids` -> None or an (N,) integer tensor on the device: host ids are validated against the bank
-    and uploaded once per sequence; a device tensor is taken as it is (the gather kernel checks its bounds)."""
-    if rig_ids is None:
-        return None
-    if sel is None:
-        raise ValueError("rig_ids needs a rig bank: FrameBatchLoop / FramePipeline(gaussians, rigs=RigBank(rigs, device), ...)")
-    if torch.is_tensor(rig_ids) and rig_ids.device.type != "cpu":
-        if rig_ids.dim() != 1 or rig_ids.shape[0] != N or rig_ids.is_floating_point():
-            raise ValueError(f"rig_ids must be ({N},) integers, got {tuple(rig_ids.shape)} {rig_ids.dtype}")
-        return rig_ids
-    from .rigs import validate_rig_ids
-    return torch.as_tensor(validate_rig_ids(rig_ids, sel.bank.R, N), dtype=torch.int32).to(sel.ids.device)
-
-
-def _checked_gt(loop, gt, n, what):
-    """The ground truth handed to set_ground_truth -> the (n,P,3) float32 tensor on the loop's device that `what` (new_scenes: n = F
-    frames; optimize_sequence: n = N frames) needs; None stays None; anything else is refused."""
-    if gt is None:
-        return None
-    want = (n, loop.P, 3)
-    if tuple(gt.shape) != want:
-        raise ValueError(f"{what}: the ground truth given to set_ground_truth must be {want}, got {tuple(gt.shape)}")
-    return gt
-
-
-def _accept_gt(loop, gt):
-    """set_ground_truth's argument: None, or a float32 (n,P,3) tensor on the loop's device, for a loop whose error reporting is on."""
-    if gt is None:
-        return None
-    if loop._report is None or loop._report.steps == 0:
-        raise ValueError("ground truth is given, but error reporting is off: the errors against it are trace rows, which need "
-                         "FrameBatchLoop / FramePipeline(..., report_steps=rows) with rows > 0"
-                         + (" (this loop has save_iterations only: snapshots need no ground truth)" if loop._report is not None else ""))
-    dev = loop.xyz.device
-    if (not torch.is_tensor(gt) or gt.dim() != 3 or tuple(gt.shape[1:]) != (loop.P, 3) or gt.dtype != torch.float32
-            or gt.device != dev):
-        got = f"{tuple(gt.shape)} {gt.dtype} on {gt.device}" if torch.is_tensor(gt) else type(gt).__name__
-        raise ValueError(f"the ground truth must be a float32 tensor (frames,P,3) = (frames, {loop.P}, 3) on {dev}, got {got}")
-    return gt
-
-
-def _sequence_report(loop, N):
-    """optimize_sequence's `report`: None for a loop that reports nothing."""
-    if loop._report is None:
-        return None
-    from .report import SequenceReport
-    return SequenceReport(loop, N)
-
-
-def _sequence_gaussians(loop, out):
-    """optimize_sequence's `gaussians` around the joints `out` it returns: None for a loop that does not keep them."""
-    if not loop.keep_gaussians:
-        return None
-    from .uncertainty import SequenceGaussians
-    return SequenceGaussians(out)
-
-
-def _sequence_images(loop, N):
-    """optimize_sequence's `images`: None for a loop whose debug pictures are off (set_debug_images)."""
-    if loop._debug_frames is None:
-        return None
-    from .preview import SequenceImages
-    va = loop.views_all
-    return SequenceImages(loop._debug_frames, N, loop.V, va.W, va.H, loop.device, va.sizes[:loop.V] if va.mixed else None)
-
-
-def _debug_frames(loop, frames):
-    """set_debug_images' argument -> None (off) or a tuple of sequence indices >= 0."""
-    if frames is None:
-        return None
-    if loop.rigs is not None:
-        raise ValueError("set_debug_images: the debug pictures render a frame in its own cameras from HOST scalars; a loop over "
-                         "a rig bank keeps them on the device (picture such a frame with preview.render_preview and its rig)")
-    chosen = tuple(int(f) for f in frames)
-    if not chosen or min(chosen) < 0:
-        raise ValueError(f"set_debug_images: frames = {list(frames)!r} must be sequence indices >= 0, at least one (None: off)")
-    return chosen
-
-
 def _frame_criterion(early_stopping):
     """FrameBatchLoop's `early_stopping` -> None (off) or (window, tolerance) of the reference's criterion, which the frame
     batch runs per frame on the device; anything else is refused."""
@@ -1400,34 +1269,6 @@ class FrameBatchLoop(_GroupLoop):
         if self._sel is not None:
             self._sel.check()
 
-    def _next_batch(self, pts, p2d, b, initial=None, rig_ids=None, p3d=None, gt=None, consensus=None, images=None):
-        """new_scenes for the frames b .. b + F of a sequence (a short last batch is filled up by repeating its final
-        frame, rig included); `pts` None: triangulated from the detections.  `initial` (N,P,3): receives the batch's initial
-        joints.  `rig_ids`: None or the sequence's (N,) ids as _sequence_rig_ids left them.  `p3d`: None or the sequence's
-        (N,V,J,3) predictions, fused into the initial joints instead of the triangulation (`pts` None).  `gt`: None or the sequence's
-        (N,P,3) ground truth as _checked_gt left it.  `consensus`: None or the
-        sequence's (inliers (N,V,J), n_consensus (N,J)), which receive the batch's rows on the current stream.  `images`: None or
-        the sequence's preview.SequenceImages, which pictures the batch's chosen frames right behind new_scenes."""
-        N, F = p2d.shape[0], self.F
-        if gt is not None:
-            self._gt_next = gt[b:b + F] if b + F <= N else gt[[min(b + i, N - 1) for i in range(F)]]
-        if b + F <= N:      # a full batch: views of the inputs, no gather
-            self.new_scenes(None if pts is None else pts[b:b + F], poses_2d=p2d[b:b + F],
-                            rig_ids=None if rig_ids is None else rig_ids[b:b + F],
-                            poses_3d=None if p3d is None else p3d[b:b + F])
-        else:
-            idx = [min(b + i, N - 1) for i in range(F)]
-            self.new_scenes(None if pts is None else pts[idx], poses_2d=p2d[idx],
-                            rig_ids=None if rig_ids is None else rig_ids[idx],
-                            poses_3d=None if p3d is None else p3d[idx])
-        if initial is not None:
-            initial[b:min(b + F, N)] = self.xyz[:min(F, N - b)]
-        if consensus is not None:
-            consensus[0][b:min(b + F, N)] = self.inliers[:min(F, N - b)]
-            consensus[1][b:min(b + F, N)] = self.n_consensus[:min(F, N - b)]
-        if images is not None:
-            images.begin(self, b, min(F, N - b))
-
     def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, return_initial=False, rig_ids=None,
                           poses_3d=None):
         """The reference's outer loop over the frames of a sequence (train.py:74-99) F frames at a time: `points`
@@ -1450,31 +1291,15 @@ class FrameBatchLoop(_GroupLoop):
         (io.save_ply_arrays) and uncertainty.joint_uncertainty reads; None otherwise.
         After `set_debug_images(frames)`: `self.images` (a preview.SequenceImages) holds the chosen frames' debug pictures; None
         otherwise."""
-        pts, p2d, N = _sequence_inputs(points, poses_2d)
-        p3d = _sequence_predictions(points, poses_3d, N)
-        _checked_reject(self._reject, points, poses_3d, "optimize_sequence")
-        ids = _sequence_rig_ids(self._sel, rig_ids, N)
-        cons = _sequence_consensus(self, self._reject, N)
-        self.seq_inliers, self.seq_n_consensus = cons if cons is not None else (None, None)
-        gt, self._gt_next = _checked_gt(self, self._gt_next, N, "optimize_sequence"), None
-        self.report = _sequence_report(self, N)
-        F = self.F
-        out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
-        initial = torch.empty_like(out) if return_initial else None
-        self.gaussians = _sequence_gaussians(self, out)
-        self.images = _sequence_images(self, N)
-        for b in range(0, N, F):
-            self._next_batch(pts, p2d, b, initial, ids, p3d, gt, cons, self.images)
-            res = self.run(iterations, groups_per_graph)
-            out[b:min(b + F, N)] = res[:min(F, N - b)]
-            if self.gaussians is not None:
-                self.gaussians.take(self, b, min(F, N - b))
-            if self.images is not None:
-                self.images.take(self, b, min(F, N - b))
-            if self.report is not None:
-                self.report.take(self, b, min(F, N - b))
+        run, self._gt_next = SequenceRun(self, self._gt_next, points, poses_2d, poses_3d, rig_ids, return_initial), None
+        self.seq_inliers, self.seq_n_consensus = run.inliers, run.n_consensus
+        self.report, self.gaussians, self.images = run.report, run.gaussians, run.images
+        for b in run.starts():
+            run.begin(self, b)
+            self.run(iterations, groups_per_graph)      # (returns self.xyz, which take() copies)
+            run.take(self, b)
         self.check_rigs()
-        return (out, initial) if return_initial else out
+        return run.result()
 
 
 class FramePipeline:
@@ -1546,74 +1371,55 @@ class FramePipeline:
         rotation and opacity next to the joints returned, copied on each batch's own stream; None otherwise.
         After `set_debug_images(frames)`: `self.images` holds the chosen frames' debug pictures, made on each batch's own stream;
         None otherwise."""
-        pts, p2d, N = _sequence_inputs(points, poses_2d)
-        p3d = _sequence_predictions(points, poses_3d, N)
-        _checked_reject(self.loops[0]._reject, points, poses_3d, "optimize_sequence")
-        ids = _sequence_rig_ids(self.loops[0]._sel, rig_ids, N)     # (uploaded on the caller's stream, which every stream waits for)
-        cons = _sequence_consensus(self.loops[0], self.loops[0]._reject, N)
-        self.inliers, self.n_consensus = cons if cons is not None else (None, None)
-        gt, self._gt_next = _checked_gt(self.loops[0], self._gt_next, N, "optimize_sequence"), None
-        self.report = _sequence_report(self.loops[0], N)
-        F, S = self.F, len(self.loops)
-        out = torch.empty((N, self.P, 3), dtype=torch.float32, device=self.device)
-        initial = torch.empty_like(out) if return_initial else None
-        self.gaussians = _sequence_gaussians(self.loops[0], out)
-        self.images = _sequence_images(self.loops[0], N)
+        run, self._gt_next = SequenceRun(self.loops[0], self._gt_next, points, poses_2d, poses_3d, rig_ids, return_initial), None
+        self.inliers, self.n_consensus = run.inliers, run.n_consensus
+        self.report, self.gaussians, self.images = run.report, run.gaussians, run.images
         cur = torch.cuda.current_stream(self.device)
-        starts = list(range(0, N, F))
-        if self.loops[0]._es is not None:
-            self.stopped_at = torch.zeros(N, dtype=torch.int64, device=self.device)
-            for st in self.streams:
-                st.wait_stream(cur)
-            self._sequence_es(pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial, ids, p3d, gt, cons)
-            for st in self.streams:
-                cur.wait_stream(st)
-            self.check_rigs()
-            return (out, initial) if return_initial else out
+        es = self.loops[0]._es is not None
+        if es:
+            self.stopped_at = run.stopped_at = torch.zeros(run.N, dtype=torch.int64, device=self.device)
         for st in self.streams:
             st.wait_stream(cur)                      # inputs and `out` were produced on the caller's stream
-        for w in range(0, len(starts), S):
-            active = list(zip(self.loops, self.streams, starts[w:w + S]))
-            for fb, st, b in active:
-                with torch.cuda.stream(st):
-                    fb._next_batch(pts, p2d, b, initial, ids, p3d, gt, cons, self.images)
-            for k in range(0, iterations, max(int(interleave), 1)):
-                for fb, st, b in active:
-                    with torch.cuda.stream(st):
-                        fb.run(min(iterations, k + interleave), groups_per_graph)
-            for fb, st, b in active:
-                with torch.cuda.stream(st):
-                    out[b:min(b + F, N)] = fb.xyz[:min(F, N - b)]
-                    if self.gaussians is not None:
-                        self.gaussians.take(fb, b, min(F, N - b))
-                    if self.images is not None:
-                        self.images.take(fb, b, min(F, N - b))
-                    if self.report is not None:
-                        self.report.take(fb, b, min(F, N - b))
+        schedule = self._sequence_es if es else self._sequence_waves
+        schedule(run, iterations, groups_per_graph, interleave)
         for st in self.streams:
             cur.wait_stream(st)
         self.check_rigs()
-        return (out, initial) if return_initial else out
+        return run.result()
 
     def check_rigs(self):
         """FrameBatchLoop.check_rigs of every loop (never waits: final once the device has been synchronised)."""
         for fb in self.loops:
             fb.check_rigs()
 
-    def _sequence_es(self, pts, p2d, out, starts, iterations, groups_per_graph, interleave, initial=None, rig_ids=None,
-                     p3d=None, gt=None, cons=None):
+    def _sequence_waves(self, run, iterations, groups_per_graph, interleave):
+        """optimize_sequence without early stopping: waves of one batch per stream, begun, run round-robin and taken together."""
+        starts, S = run.starts(), len(self.loops)
+        for w in range(0, len(starts), S):
+            active = list(zip(self.loops, self.streams, starts[w:w + S]))
+            for fb, st, b in active:
+                with torch.cuda.stream(st):
+                    run.begin(fb, b)
+            for k in range(0, iterations, max(int(interleave), 1)):
+                for fb, st, b in active:
+                    with torch.cuda.stream(st):
+                        fb.run(min(iterations, k + interleave), groups_per_graph)
+            for fb, st, b in active:
+                with torch.cuda.stream(st):
+                    run.take(fb, b)
+
+    def _sequence_es(self, run, iterations, groups_per_graph, interleave):
         """optimize_sequence with early stopping: every stream keeps its own batch and takes the next one as soon as its
         batch is done -- all frames stopped (seen in the pinned flags, without waiting) or `iterations` enqueued -- instead
         of waiting for the other streams' batches.  Results and stopping iterations are copied on the batch's stream."""
-        N, F = p2d.shape[0], self.F
-        pending = iter(starts)
+        pending = iter(run.starts())
 
         def take(fb, st):
             b = next(pending, None)
             if b is None:
                 return None
             with torch.cuda.stream(st):
-                fb._next_batch(pts, p2d, b, initial, rig_ids, p3d, gt, cons, self.images)
+                run.begin(fb, b)
             return [fb, st, b, 0]
 
         step = max(int(interleave), 1)
@@ -1627,15 +1433,7 @@ class FramePipeline:
                     fb._enqueue(k, groups_per_graph)
                     slot[3] = k
                     if k >= iterations or fb._all_stopped():
-                        n = min(F, N - b)
-                        out[b:b + n] = fb.xyz[:n]
-                        self.stopped_at[b:b + n] = fb._es_state[:n, 1]      # (0: the frame ran to the end)
-                        if self.gaussians is not None:
-                            self.gaussians.take(fb, b, n)
-                        if self.images is not None:
-                            self.images.take(fb, b, n)
-                        if self.report is not None:
-                            self.report.take(fb, b, n)
+                        run.take(fb, b)
                         slot = take(fb, st)
                 if slot is not None:
                     nxt.append(slot)
