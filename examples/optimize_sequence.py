@@ -3,7 +3,7 @@
 other, train.py:74-99) -- but many frames per launch: noisy 2D detections of N frames -> DLT initial guesses -> 500
 iterations of the multi-view loop for every frame (loop.FramePipeline) -> MPJPE per frame.
 python examples/optimize_sequence.py [--frames 64] [--per-launch 16] [--streams 2] [--iters 500] [--init host|device|fuse] [--rigs R]
-    [--report] [--uncertainty] [--reject-px PX] [--corrupt K] [--images DIR [--image-frames 0,31,63]]
+    [--report] [--uncertainty] [--reject-px PX] [--corrupt K] [--refine [--huber-px D]] [--images DIR [--image-frames 0,31,63]]
 --rigs R: the frames cycle through R jittered ring rigs (SyntheticScene seeds 0 .. R-1), as a dataset whose scenes bring their own
 cameras does; one rigs.RigBank holds them on the device and every batch names its frames' rigs (rig_ids).
 --init host (default): the DLT runs on the host, frame by frame, and its points are uploaded; --init device: the detections
@@ -16,10 +16,15 @@ noise per view) go to the device once with the detections, and every batch start
 --reject-px PX (with --init device): every batch's triangulation first rejects outlier detections by two-view consensus on the
 device (pipe.set_outlier_rejection(PX), then optimize_sequence(None, ...)); the initial error is printed with and without the rejection, and how many
 detections were rejected.  The heat-maps still draw every detection: the final error shows what the outliers left in them cost.
+--refine [--huber-px D] (with --init device): every batch's triangulation is followed by the refinement that minimises the
+reprojection error from there (pipe.set_refinement; plain squares, or the Huber cost at D pixels); the initial error is printed with
+and without it.  With --reject-px it runs over the consensus' inliers.
 --report: the synthetic ground truth goes to the device once and the loops report while they run (report_steps, save_iterations;
 skelsplat_amd/report.py): the mean absolute / root-relative error over the sequence after 0, 1, 5, 25 and the last optimiser
 step -- the reference's convergence curve (train.py:184-213) --, the error at the snapshot of the middle iteration, and
-report.evaluate_sequence over four synthetic "activities" (eval.py:115-142).  Nothing is read back while the loops run.
+report.evaluate_sequence over four synthetic "activities" (eval.py:115-142).  Nothing is read back while the loops run.  Under
+these lines, the figure that needs no ground truth: the mean reprojection error of the initial and of the optimised joints against the
+detections, overall and per view (pipe.set_reprojection_report, skelsplat_amd/reprojection.py).
 --uncertainty (with --report's ground truth): the loops keep every frame's optimised Gaussians (keep_gaussians=True) and the
 covariances are read back as the pose's uncertainty on the device (skelsplat_amd/uncertainty.py): the share of ground-truth joints
 inside the 1 / 2 / 3-sigma ellipsoid overall and per joint (utils/analize_error_confidence_correlation.py's percent_inside_sigmas
@@ -61,6 +66,8 @@ def main(argv=None):
     ap.add_argument("--uncertainty", action="store_true")
     ap.add_argument("--reject-px", type=float, default=None)
     ap.add_argument("--corrupt", type=int, default=0)
+    ap.add_argument("--refine", action="store_true")
+    ap.add_argument("--huber-px", type=float, default=None)
     ap.add_argument("--images", default=None, metavar="DIR")
     ap.add_argument("--image-frames", default=None, metavar="I,J,..")
     args = ap.parse_args(argv)
@@ -82,6 +89,10 @@ def main(argv=None):
         ap.error("--uncertainty measures against --report's ground truth: use the two together")
     if args.reject_px is not None and args.init != "device":
         ap.error("--reject-px rejects while triangulating on the device: use it with --init device")
+    if args.refine and args.init != "device":
+        ap.error("--refine follows the triangulation on the device: use it with --init device")
+    if args.huber_px is not None and not args.refine:
+        ap.error("--huber-px is the cost of --refine")
     if args.images is not None and args.rigs > 1:
         ap.error("--images pictures frames seen by one rig: use it without --rigs")
     if args.image_frames is not None and args.images is None:
@@ -109,6 +120,7 @@ def main(argv=None):
     if args.init == "device":
         p2d_dev = torch.as_tensor(p2d, device=dev)
         pipe.set_outlier_rejection(args.reject_px)        # (None: off)
+        pipe.set_refinement(16 if args.refine else None, huber_px=args.huber_px)
         run = lambda: pipe.optimize_sequence(None, p2d_dev, iterations=args.iters, return_initial=True, **ids)
     elif args.init == "fuse":
         sigma = np.linspace(20.0, 50.0, args.views)[:, None, None]
@@ -121,6 +133,7 @@ def main(argv=None):
             init = host_init()
             return pipe.optimize_sequence(init, p2d, iterations=args.iters, **ids), init
     if args.report:
+        pipe.set_reprojection_report()
         gt_dev = torch.as_tensor(gt.astype(np.float32), device=dev)
         optimise = run
 
@@ -156,6 +169,14 @@ def main(argv=None):
         fallbacks = int((pipe.n_consensus < 3).sum())
         print(f"initial joints, {args.corrupt} corrupted detections per frame: mean MPJPE {ep:.2f} mm from all views -> {e0:.2f} mm "
               f"with reject_px {args.reject_px:g} ({rejected} detections rejected, {fallbacks} joints without a consensus of 3)")
+    if args.refine:
+        det = torch.as_tensor(p2d, device=dev)
+        Pd = torch.as_tensor(np.stack([Pm[r] for r in rig_of]), device=dev)
+        valid = pipe.inliers if args.reject_px is not None else None
+        dlt = triangulation.triangulate_sequence(Pd, det, valid=valid).cpu().numpy()
+        ed = np.mean([io.mpjpe(dlt[f], gt[f]) for f in range(args.frames)])
+        cost = "plain squares" if args.huber_px is None else f"Huber at {args.huber_px:g} px"
+        print(f"initial joints: mean MPJPE {ed:.2f} mm from the DLT -> {e0:.2f} mm refined ({cost})")
     if args.report:
         from skelsplat_amd.report import evaluate_sequence, evaluate_sequence_aligned, pose_errors
         r = pipe.report
@@ -176,6 +197,11 @@ def main(argv=None):
         print(f"evaluate_sequence_aligned: PA-MPJPE {float(eva['pa_mpjpe']):.3f} mm, N-MPJPE {float(eva['n_mpjpe']):.3f} mm; "
               "per activity PA " + " ".join(f"{x:.2f}" for x in eva["pa_mpjpe_groups"].tolist()) + " | N "
               + " ".join(f"{x:.2f}" for x in eva["n_mpjpe_groups"].tolist()))
+    if args.report:
+        tables = pipe.reprojection.summary()        # two launches on what is on the device; read back here, to print
+        for name, t in (("initial", tables["initial"][0].tolist()), ("optimised", tables["final"][0].tolist())):
+            print(f"reprojection error of the {name} joints: mean {t[0]:.3f} px; per view "
+                  + " ".join(f"{x:.3f}" for x in t[1:1 + args.views]))
     if args.uncertainty:
         from skelsplat_amd.uncertainty import calibration
         unc = pipe.gaussians.uncertainty(gt_dev)

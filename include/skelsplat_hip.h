@@ -415,6 +415,54 @@ int sks_fuse_predictions(int N, int V, int J, const double* proj, size_t rig_str
                          const unsigned char* valid, int norm_f32, float* xyz, double* xyz_f64, double* reproj_err,
                          int* n_used, void* stream);
 
+/* The reprojection error of joints against the views' detections, measured and minimised (csrc/sks_reproject.hip; reference:
+ * compute_reprojection_error, dataset_tools/h36m/compute_initial_guess.py:23-79).  Added to sks_version 14: the number did not
+ * move (a caller that must know looks the symbol up).  One launch each on `stream`, nothing synchronises, no atomics, no scratch.
+ *
+ * sks_reproject: N frames of J joints into V views.  proj, rig_stride, valid: as sks_triangulate takes them; the joints (N,J,3) as
+ * float (xyz) or as double (xyz_f64), exactly one of the two; the detections (N,V,J,2) as float (poses_2d) or as double
+ * (poses_2d_f64), at most one of the two -- neither: project only, every pair is left out.  Float inputs are widened exactly, the
+ * arithmetic is float64: u = P_v [X; 1] added in column order 0..3, uv = (u0 / u2, u1 / u2) with no test for points behind the
+ * camera (as the reference), in_front = u2 > 0, err = sqrt(dx * dx + dy * dy) with (dx, dy) = uv - detection.  A pair (v, j) is
+ * LEFT OUT when valid == 0, when its detection is not finite or when the joint has a NaN coordinate: its err is NaN (uv and
+ * in_front are written all the same).  The means skip every NaN err and are NaN over nothing, each added in a fixed order:
+ * per_joint[n,j] over the views in ascending order (all kept: the reference's mean_l2), n_used[n,j] the number of views that
+ * entered it; per_view[n,v] over the joints in ascending order; per_frame[n] = (S_0 + S_1 + ..) / (C_0 + C_1 + ..) with S_v, C_v
+ * the sum and count of view v as in per_view -- all kept pairs, view-major, grouped by view.
+ * outputs, each optional but at least one: uv (N,V,J,2), err (N,V,J), per_joint (N,J), per_view (N,V), per_frame (N) doubles,
+ * in_front (N,V,J) bytes, n_used (N,J) ints.  1 <= V <= SKS_MAX_VIEWS.  A frame's outputs depend on its own inputs, V and J only:
+ * never on N, on its place in the batch or on the stream.
+ *
+ * sks_eval_reprojection: the means of err (N,V,J; NaN = left out) over a sequence, shaped after sks_eval_sequence.  out
+ * (1 + n_groups, 1 + V + J) doubles: row 0 over all frames, row 1 + g over the frames with group_ids[i] == g (an id outside
+ * 0 .. n_groups - 1 enters row 0 only); a row holds the overall mean, then the V per-view and the J per-joint means over the
+ * non-NaN entries, NaN where there are none.  Thread t of a row's workgroup takes frames t, t + 256, ... in index order and the
+ * 256 partial sums meet in a fixed tree.  0 <= n_groups <= SKS_EVAL_MAX_GROUPS; group_ids (N) ints, NULL with n_groups == 0.
+ *
+ * sks_triangulate_refine: per (frame, joint) minimises cost(X) = sum over the kept views of rho(e_v), e_v = sks_reproject's err,
+ * rho(e) = e * e -- or, with huber_px = d > 0, e * e for e <= d and 2 d e - d * d beyond -- from the start xyz0 by damped
+ * Gauss-Newton in float64.  A view is kept when valid != 0 and its detection is finite.  One trip: with J_v the 2 x 3 Jacobian
+ * rows (P_v[k,:3] - uv_k * P_v[2,:3]) / u2, r_v = uv - detection and w_v = min(1, d / e_v) (1 without Huber), A = sum w_v J_v^T
+ * J_v and g = sum w_v J_v^T r_v (butterfly sums over the next power of two >= V lanes), (A + lambda diag A) delta = -g by
+ * Cholesky, trial = X + delta; the trial is ACCEPTED only if its cost is strictly smaller and every kept view has u2 > 0 there
+ * (and the Cholesky pivots were > 0).  lambda starts at 1e-3, x 0.1 on acceptance, x 10 on rejection.  A joint stops after an
+ * accepted trip that lowered the cost by less than 1e-6 x the cost (scale-free), or after max_iters trips (1 ..
+ * SKS_REFINE_MAX_ITERS); iters = its trips, accepted or not.  A joint with fewer than two kept views, with a start that is not
+ * finite, or with a kept view that has u2 <= 0 at the start comes back unchanged with iters = 0.
+ * proj, rig_stride, valid, the detections: as sks_triangulate takes them; the start (N,J,3) as float (xyz0) or as double
+ * (xyz0_f64), exactly one of the two; huber_px finite and >= 0 (0: plain squares).  outputs, at least one of the first two: xyz
+ * (N,J,3) float (rounded to nearest; it may be xyz0 itself: in place), xyz_f64 (N,J,3) double; optional cost (N,J,2) doubles =
+ * {at the start, at the result} and iters (N,J) ints.  A joint's result depends on V and its own inputs only, never on N, on its
+ * place in the batch, on its neighbours in the wavefront or on the stream. */
+#define SKS_REFINE_MAX_ITERS 16
+int sks_reproject(int N, int V, int J, const double* proj, size_t rig_stride, const float* xyz, const double* xyz_f64,
+                  const float* poses_2d, const double* poses_2d_f64, const unsigned char* valid, double* uv, double* err,
+                  unsigned char* in_front, double* per_joint, double* per_view, double* per_frame, int* n_used, void* stream);
+int sks_eval_reprojection(int N, int V, int J, const double* err, const int* group_ids, int n_groups, double* out, void* stream);
+int sks_triangulate_refine(int N, int V, int J, const double* proj, size_t rig_stride, const float* poses_2d,
+                           const double* poses_2d_f64, const unsigned char* valid, const float* xyz0, const double* xyz0_f64,
+                           double huber_px, int max_iters, float* xyz, double* xyz_f64, double* cost, int* iters, void* stream);
+
 /* Replaces fusedssim (submodules/fused-ssim/ssim.cu:368-404, binding ext.cpp): img1, img2, ssim_map and the three
  * optional partial-derivative maps (train == true) are (B,CH,H,W) fp32; "same" zero padding. */
 int sks_fused_ssim_fwd(int B, int CH, int H, int W, float C1, float C2, const float* img1, const float* img2,

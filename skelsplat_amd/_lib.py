@@ -29,6 +29,7 @@ SKS_SOFTARGMAX_STATS = 6
 SKS_REPORT_MAX_SAVES = 8
 SKS_EVAL_MAX_GROUPS = 64
 SKS_CALIBRATION_MAX_K = 8
+SKS_REFINE_MAX_ITERS = 16
 SKS_ALIGN_RIGID, SKS_ALIGN_SIMILARITY, SKS_ALIGN_SCALE = 0, 1, 2
 SKS_PREVIEW_LAUNCH_INTS = 4
 
@@ -164,6 +165,9 @@ SIGNATURES = {
     "sks_triangulate": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sks_triangulate_robust": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sks_fuse_predictions": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sks_reproject": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sks_eval_reprojection": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "sks_triangulate_refine": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, C.c_double, _i, _vp, _vp, _vp, _vp, _vp]),
     **{name: (_i, [ct for _, ct in params]) for name, params in {**STEP_PARAMS, **DV_PARAMS}.items()},
     "sks_pose_errors": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "sks_loop_report": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),

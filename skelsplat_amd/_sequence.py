@@ -38,6 +38,36 @@ def _checked_reject(reject, points, poses_3d, who):
     return reject
 
 
+def _refinement(max_iters, huber_px):
+    """set_refinement's arguments -> None (off) or the checked (huber_px, max_iters)."""
+    if max_iters is None:
+        return None
+    from .reprojection import _checked_refinement
+    return _checked_refinement(huber_px, max_iters)
+
+
+def _checked_refine(refine, points, poses_3d, who):
+    """`refine`: a loop's set_refinement setting.  Like the rejection it belongs to the triangulation of the initial joints:
+    refused beside explicit points or poses_3d.  Returns it."""
+    if refine is None:
+        return None
+    if points is not None:
+        raise ValueError(f"{who}: the refinement (set_refinement) follows the triangulation of the initial joints (points=None); "
+                         "explicit points are taken as they are -- switch it off with set_refinement(None)")
+    if poses_3d is not None:
+        raise ValueError(f"{who}: the refinement (set_refinement) follows the triangulation; fusing poses_3d is a different "
+                         "estimator -- switch it off with set_refinement(None)")
+    return refine
+
+
+def _sequence_reprojection(loop, N):
+    """optimize_sequence's `reprojection`: None for a loop whose reprojection report is off (set_reprojection_report)."""
+    if not getattr(loop, "_reproject", False):
+        return None
+    from .reprojection import SequenceReprojection
+    return SequenceReprojection(N, loop.V, loop.P, loop.device)
+
+
 def _sequence_consensus(loop, reject, N):
     """optimize_sequence's (inliers (N,V,J) bool, n_consensus (N,J) int32) on the device, None without rejection."""
     if reject is None:
@@ -147,13 +177,14 @@ class SequenceRun:
       ids, gt       None or the (N,) rig ids as _sequence_rig_ids left them; None or the (N,P,3) ground truth (`gt_next`: what
                     set_ground_truth left) as _checked_gt left it
       out, initial  (N,P,3) optimised joints; the initial joints, None unless `return_initial`
-      inliers, n_consensus, report, gaussians, images   what optimize_sequence documents under these names, None where the loop
+      inliers, n_consensus, report, gaussians, images, reprojection   what optimize_sequence documents under these names, None where the loop
                     has the feature off;  stopped_at: None, or the (N,) int64 zeros of a pipeline with early stopping"""
 
     def __init__(self, loop, gt_next, points, poses_2d, poses_3d, rig_ids, return_initial, who="optimize_sequence"):
         self.pts, self.p2d, self.N = _sequence_inputs(points, poses_2d)
         self.p3d = _sequence_predictions(points, poses_3d, self.N)
         _checked_reject(loop._reject, points, poses_3d, who)
+        _checked_refine(getattr(loop, "_refine", None), points, poses_3d, who)      # (a loop without the switch: off)
         self.ids = _sequence_rig_ids(loop._sel, rig_ids, self.N)    # (uploaded on the caller's stream)
         self.inliers, self.n_consensus = _sequence_consensus(loop, loop._reject, self.N) or (None, None)
         self.gt = _checked_gt(loop, gt_next, self.N, who)
@@ -163,6 +194,7 @@ class SequenceRun:
         self.initial = torch.empty_like(self.out) if return_initial else None
         self.gaussians = _sequence_gaussians(loop, self.out)
         self.images = _sequence_images(loop, self.N)
+        self.reprojection = _sequence_reprojection(loop, self.N)
 
     def starts(self):
         return range(0, self.N, self.F)     # the first frame of every batch
@@ -186,6 +218,8 @@ class SequenceRun:
             self.n_consensus[b:b + n] = loop.n_consensus[:n]
         if self.images is not None:
             self.images.begin(loop, b, n)       # (right behind new_scenes: the heat-maps and the first renders)
+        if self.reprojection is not None:
+            self.reprojection.begin(loop, b, n, self.p2d[rows])
 
     def take(self, loop, b):
         """Batch b is done on `loop`: its first n frames' results, on the current stream (the filler frames are dropped)."""
@@ -193,7 +227,7 @@ class SequenceRun:
         self.out[b:b + n] = loop.xyz[:n]
         if self.stopped_at is not None:
             self.stopped_at[b:b + n] = loop._es_state[:n, 1]        # (0: the frame ran to the end)
-        for kept in (self.gaussians, self.images, self.report):
+        for kept in (self.gaussians, self.images, self.report, self.reprojection):
             if kept is not None:
                 kept.take(loop, b, n)
 

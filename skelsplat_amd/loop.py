@@ -22,7 +22,7 @@ import torch.distributed as dist
 
 from . import rasterizer as R
 from ._group import next_group
-from ._sequence import SequenceRun, _accept_gt, _checked_gt, _checked_reject, _debug_frames, _rejection
+from ._sequence import SequenceRun, _accept_gt, _checked_gt, _checked_refine, _checked_reject, _debug_frames, _refinement, _rejection
 from ._sequence import _sequence_predictions, _sequence_rig_ids     # noqa: F401  (callers and tests reach them as loop.<name>)
 from .scene import DATASETS
 
@@ -124,6 +124,16 @@ class _GroupLoop:
         self._reject = _rejection(reject_px, min_inliers)
         return self
 
+    def set_refinement(self, max_iters=16, huber_px=None):
+        """From now on new_scene / new_scenes / optimize_sequence with `points=None` (and without `poses_3d`) follow the
+        triangulation of the initial joints by one launch that minimises their reprojection error from there
+        (reprojection.refine_triangulation: at most `max_iters` (1 .. 16) damped Gauss-Newton trips per joint, plain squares or,
+        with `huber_px`, the Huber cost), in place, in front of the heat-map factors that read the joints.  With outlier
+        rejection on, it minimises over the consensus' `inliers`.  While it is on, explicit points or `poses_3d` are refused;
+        `max_iters=None` switches it off.  Returns the loop."""
+        self._refine = _refinement(max_iters, huber_px)
+        return self
+
     def _enqueue(self, iterations, groups_per_graph, graphs=True):
         """run() without its final synchronisation (FramePipeline drives several loops with it).  With use_graph, while every group
         is the same one (all views, acc_steps iterations), G = `groups_per_graph` of them are ONE hipGraph: an eager group warms
@@ -206,6 +216,7 @@ class MultiViewLoop(_GroupLoop):
         from .triangulation import device_projection_matrices
         self._proj = device_projection_matrices(cameras, dev)
         self._reject = None                         # set_outlier_rejection's (reject_px, min_inliers)
+        self._refine = None                         # set_refinement's (huber_px, max_iters)
         self.inliers = self.n_consensus = None      # new_scene(points=None) with rejection: (V,J) bool, (J,) int32, allocated once
         P = gaussians._xyz.shape[0]
         self.P = P
@@ -455,6 +466,7 @@ class MultiViewLoop(_GroupLoop):
         from .heatmaps import generate_heatmaps
         gm = self.gm
         reject_px, min_inliers = _checked_reject(self._reject, points, poses_3d, "new_scene")
+        refine = _checked_refine(self._refine, points, poses_3d, "new_scene")
         if points is not None:
             if poses_3d is not None:
                 raise ValueError("new_scene: poses_3d are fused into the initial joints when points is None; give one of the two")
@@ -502,9 +514,15 @@ class MultiViewLoop(_GroupLoop):
                     if reject_px is not None and self.inliers is None:
                         self.inliers = torch.zeros((self.V, self.P), dtype=torch.bool, device=self.device)
                         self.n_consensus = torch.zeros((self.P,), dtype=torch.int32, device=self.device)
-                    gm.reset_from_points(triangulate_sequence(
-                        self._proj, p2d, valid=None if drop is None else ~drop, reject_px=reject_px, min_inliers=min_inliers,
-                        out_inliers=None if reject_px is None else (self.inliers[None], self.n_consensus[None])))
+                    keep = None if drop is None else ~drop
+                    pts = triangulate_sequence(
+                        self._proj, p2d, valid=keep, reject_px=reject_px, min_inliers=min_inliers,
+                        out_inliers=None if reject_px is None else (self.inliers[None], self.n_consensus[None]))
+                    if refine is not None:
+                        from .reprojection import refine_triangulation
+                        refine_triangulation(self._proj, p2d, pts, valid=keep if reject_px is None else self.inliers,
+                                             huber_px=refine[0], max_iters=refine[1], out=pts)
+                    gm.reset_from_points(pts)
             for grp in self.size_groups:
                 slots, vb, gt, stats, idx = grp
                 ids = [self.local_ids[k] for k in slots]
@@ -958,6 +976,9 @@ class FrameBatchLoop(_GroupLoop):
         from .triangulation import device_projection_matrices
         self._proj = device_projection_matrices(cameras, dev)
         self._reject = None     # set_outlier_rejection's (reject_px, min_inliers)
+        self._refine = None     # set_refinement's (huber_px, max_iters)
+        self._reproject = False     # set_reprojection_report
+        self.reprojection = None    # optimize_sequence's reprojection.SequenceReprojection of the last sequence
         # new_scenes(points=None) with rejection: the views each joint of the batch was triangulated from, the winners' counts
         self.inliers = torch.ones((F, V, self.P), dtype=torch.bool, device=dev)
         self.n_consensus = torch.zeros((F, self.P), dtype=torch.int32, device=dev)
@@ -1031,6 +1052,9 @@ class FrameBatchLoop(_GroupLoop):
         front of the triangulation and the heat-map factors that read them.  Host ids are validated here; ids in a device
         tensor are bounds-checked by the kernel, which skips a frame whose id is outside the bank (it keeps the cameras its
         slot had) and raises an error word that `check_rigs()` reports.  None: the frames keep the rigs they have.
+        After `set_refinement(max_iters, huber_px)`, with `points=None` and without `poses_3d` (refused otherwise): one more
+        launch in the same place minimises the triangulated joints' reprojection error in place (reprojection.refine_triangulation),
+        over `valid = ~drop_masks`, or over `self.inliers` with rejection on.
         A loop that reports (`report_steps` / `save_iterations`): the ground truth given to `set_ground_truth` since the last batch,
         (F,P,3), is copied in place -- without one the errors of this batch are NaN, losses and snapshots are reported all the
         same --, the traces and snapshots go back to NaN and one report launch behind everything above writes row 0 and the
@@ -1042,7 +1066,11 @@ class FrameBatchLoop(_GroupLoop):
             raise ValueError("ready heat-map planes need FrameBatchLoop(..., factored=False)")
         if rig_ids is not None and self._sel is None:
             raise ValueError("rig_ids needs a rig bank: FrameBatchLoop(gaussians, rigs=RigBank(rigs, device), frames=F)")
+        if self._reproject and heatmaps is not None:
+            raise ValueError("new_scenes: the reprojection report (set_reprojection_report) measures against detections, and ready "
+                             "heatmaps carry none -- give poses_2d, or switch it off with set_reprojection_report(False)")
         reject_px, min_inliers = _checked_reject(self._reject, points, poses_3d, "new_scenes")
+        refine = _checked_refine(self._refine, points, poses_3d, "new_scenes")
         gt_pose, self._gt_next = _checked_gt(self, self._gt_next, F, "new_scenes"), None      # (`gt` below: heat-map planes)
         with torch.no_grad():
             if self._sel is not None:
@@ -1087,6 +1115,10 @@ class FrameBatchLoop(_GroupLoop):
                     triangulate_sequence(self._proj, p2d_dlt, valid=keep, out=self.xyz, reject_px=reject_px,
                                          min_inliers=min_inliers,
                                          out_inliers=None if reject_px is None else (self.inliers, self.n_consensus))
+                    if refine is not None:      # one more launch in the same place, in place on the joints
+                        from .reprojection import refine_triangulation
+                        refine_triangulation(self._proj, p2d_dlt, self.xyz, valid=keep if reject_px is None else self.inliers,
+                                             huber_px=refine[0], max_iters=refine[1], out=self.xyz)
             else:
                 self.xyz.copy_(pts.to(device=self.device, dtype=torch.float32))
             self.scaling.copy_(self._init[0].expand(F, P, 3))
@@ -1126,6 +1158,14 @@ class FrameBatchLoop(_GroupLoop):
                 self._report.launch(self, losses=False)
         self._geom_valid = False
         self.iteration = 0
+        return self
+
+    def set_reprojection_report(self, on=True):
+        """From now on every `optimize_sequence` measures the reprojection error of each batch's initial and final joints against
+        the batch's detections (reprojection.reproject: one launch each, on the batch's own stream, nothing is read back) into
+        `self.reprojection`, a reprojection.SequenceReprojection -- the ground-truth-free figure of the sequence; None after a
+        sequence without it.  The optimiser's steps and captured graphs are untouched.  Returns the loop."""
+        self._reproject = bool(on)
         return self
 
     def set_debug_images(self, frames):
@@ -1290,10 +1330,15 @@ class FrameBatchLoop(_GroupLoop):
         xyz -- the tensor returned --, scaling, rotation and opacity as the frame ended, what scene.save_h36m writes
         (io.save_ply_arrays) and uncertainty.joint_uncertainty reads; None otherwise.
         After `set_debug_images(frames)`: `self.images` (a preview.SequenceImages) holds the chosen frames' debug pictures; None
-        otherwise."""
+        otherwise.
+        After `set_refinement(max_iters, huber_px)`, with `points=None` and without `poses_3d` (refused otherwise): every batch's
+        triangulated joints are refined in place by one more launch (new_scenes).  After `set_reprojection_report()`:
+        `self.reprojection` (a reprojection.SequenceReprojection) holds the reprojection errors of every frame's initial and final
+        joints against its detections; None otherwise."""
         run, self._gt_next = SequenceRun(self, self._gt_next, points, poses_2d, poses_3d, rig_ids, return_initial), None
         self.seq_inliers, self.seq_n_consensus = run.inliers, run.n_consensus
         self.report, self.gaussians, self.images = run.report, run.gaussians, run.images
+        self.reprojection = run.reprojection
         for b in run.starts():
             run.begin(self, b)
             self.run(iterations, groups_per_graph)      # (returns self.xyz, which take() copies)
@@ -1326,12 +1371,28 @@ class FramePipeline:
         self._gt_next = None         # set_ground_truth's tensor, until the next optimize_sequence takes it
         self.images = None           # set_debug_images: preview.SequenceImages of the last optimize_sequence
         self.inliers = self.n_consensus = None     # optimize_sequence with rejection: (N,V,J) bool, (N,J) int32
+        self.reprojection = None     # set_reprojection_report: reprojection.SequenceReprojection of the last optimize_sequence
 
     def set_outlier_rejection(self, reject_px=None, min_inliers=3):
         """FrameBatchLoop.set_outlier_rejection of every loop: from now on optimize_sequence(None, detections) rejects outlier
         detections while it triangulates (None: off again).  Returns the pipeline."""
         for fb in self.loops:
             fb.set_outlier_rejection(reject_px, min_inliers)
+        return self
+
+    def set_refinement(self, max_iters=16, huber_px=None):
+        """FrameBatchLoop.set_refinement of every loop: from now on optimize_sequence(None, detections) minimises the triangulated
+        initial joints' reprojection error before it starts (`max_iters=None`: off again).  Returns the pipeline."""
+        for fb in self.loops:
+            fb.set_refinement(max_iters, huber_px)
+        return self
+
+    def set_reprojection_report(self, on=True):
+        """FrameBatchLoop.set_reprojection_report of every loop: from now on optimize_sequence fills `self.reprojection` (a
+        reprojection.SequenceReprojection) with the reprojection errors of every frame's initial and final joints, each batch's
+        on its own stream (False: off again, and `reprojection` is None after the next sequence).  Returns the pipeline."""
+        for fb in self.loops:
+            fb.set_reprojection_report(on)
         return self
 
     def set_debug_images(self, frames):
@@ -1370,10 +1431,15 @@ class FramePipeline:
         Loops built with keep_gaussians=True: `self.gaussians` (an uncertainty.SequenceGaussians) holds every frame's scaling,
         rotation and opacity next to the joints returned, copied on each batch's own stream; None otherwise.
         After `set_debug_images(frames)`: `self.images` holds the chosen frames' debug pictures, made on each batch's own stream;
-        None otherwise."""
+        None otherwise.
+        After `set_refinement(max_iters, huber_px)`, with `points=None` and without `poses_3d` (refused otherwise): every batch's
+        triangulated joints are refined in place by one more launch on its stream.  After `set_reprojection_report()`:
+        `self.reprojection` (a reprojection.SequenceReprojection) holds the reprojection errors of every frame's initial and final
+        joints against its detections, two launches per batch on its own stream; None otherwise."""
         run, self._gt_next = SequenceRun(self.loops[0], self._gt_next, points, poses_2d, poses_3d, rig_ids, return_initial), None
         self.inliers, self.n_consensus = run.inliers, run.n_consensus
         self.report, self.gaussians, self.images = run.report, run.gaussians, run.images
+        self.reprojection = run.reprojection
         cur = torch.cuda.current_stream(self.device)
         es = self.loops[0]._es is not None
         if es:

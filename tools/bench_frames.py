@@ -19,6 +19,10 @@ save_iterations=), set_ground_truth(gt)): the H36M pipeline (S streams of F fram
   parent_off   (--parent DIR, a built checkout of the commit to compare with) that tree's pipeline, reporting unknown to it.
 bench_frames.py --report --keep [...]: the same three-way comparison for FramePipeline(keep_gaussians=True) (case `keep`: every
 frame's scaling / rotation / opacity copied next to its joints, three small device copies per batch) in place of `on`.
+bench_frames.py --report --reproject [...]: the same for the two switches of skelsplat_amd/reprojection.py.  `off` (points given,
+both switches off) is what `parent_off` is held against; the switches act on sequences that start from detections, so their cost is
+read against `dlt` (optimize_sequence(None, detections on the device), both off): `refine` (set_refinement(16): one more launch
+per batch behind the triangulation), `reproj` (set_reprojection_report(): two more launches per batch) and `both`.
 Every tree is measured by a worker process of its own that stays warm; the driver asks them for one repetition of one case at a
 time, round-robin, N times, so drift hits all cases alike.  Prints median, min and max per case and the ratios of the medians."""
 import os, sys, time
@@ -114,6 +118,7 @@ def report_worker(argv):
     from skelsplat_amd.loop import FramePipeline
     F, S = int(argv[0]), int(argv[1])
     keep = len(argv) > 2 and argv[2] == "keep"
+    reproject = len(argv) > 2 and argv[2] == "reproject"
     iters = int(os.environ.get("ITERS", "500"))
     N = S * F * 4
     sc = SyntheticScene("h36m", n_views=4, seed=0, device=dev)
@@ -127,16 +132,27 @@ def report_worker(argv):
         gm.training_setup()
         return gm
     pipes = {"off": (FramePipeline(model(), sc.cameras, frames=F, streams=S, dataset="h36m"), None)}
-    if keep:
+    from_detections = set()
+    if reproject:
+        if hasattr(FramePipeline, "set_reprojection_report"):
+            for name, refine, rep in (("dlt", None, False), ("refine", 16, False), ("reproj", None, True), ("both", 16, True)):
+                pipe = FramePipeline(model(), sc.cameras, frames=F, streams=S, dataset="h36m")
+                pipes[name] = (pipe.set_refinement(refine).set_reprojection_report(rep), None)
+                from_detections.add(name)
+    elif keep:
         if "keep_gaussians" in inspect.signature(FrameBatchLoop.__init__).parameters:
             pipes["keep"] = (FramePipeline(model(), sc.cameras, frames=F, streams=S, dataset="h36m", keep_gaussians=True), None)
     elif "report_steps" in inspect.signature(FrameBatchLoop.__init__).parameters:
         pipes["on"] = (FramePipeline(model(), sc.cameras, frames=F, streams=S, dataset="h36m", report_steps=iters // 4 + 1,
                                      save_iterations=(0, iters // 2, iters)), gt)
-    for pipe, truth in pipes.values():
+    p2d_dev = torch.as_tensor(p2d, device=dev)
+    for name, (pipe, truth) in pipes.items():
         if truth is not None:
             pipe.set_ground_truth(truth)
-        pipe.optimize_sequence(pts, p2d, iterations=iters)       # warm-up: allocations, graph capture
+        if name in from_detections:
+            pipe.optimize_sequence(None, p2d_dev, iterations=iters)
+        else:
+            pipe.optimize_sequence(pts, p2d, iterations=iters)       # warm-up: allocations, graph capture
     torch.cuda.synchronize()
     print("ready " + ",".join(pipes), flush=True)
     for line in sys.stdin:
@@ -144,7 +160,10 @@ def report_worker(argv):
         torch.cuda.synchronize(); t0 = time.perf_counter()
         if truth is not None:
             pipe.set_ground_truth(truth)
-        pipe.optimize_sequence(pts, p2d, iterations=iters)
+        if line.strip() in from_detections:
+            pipe.optimize_sequence(None, p2d_dev, iterations=iters)
+        else:
+            pipe.optimize_sequence(pts, p2d, iterations=iters)
         torch.cuda.synchronize()
         print(f"{N / (time.perf_counter() - t0):.1f}", flush=True)
 
@@ -154,6 +173,7 @@ def bench_report(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--keep", action="store_true")
+    ap.add_argument("--reproject", action="store_true")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--streams", type=int, default=2)
@@ -165,7 +185,7 @@ def bench_report(argv):
     def worker(root):
         env = dict(os.environ, SKS_BENCH_ROOT=os.path.abspath(root))
         w = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--report-worker", str(a.frames), str(a.streams),
-                              "keep" if a.keep else "report"],
+                              "keep" if a.keep else "reproject" if a.reproject else "report"],
                              stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env=env, cwd=root)
         head = w.stdout.readline().split()
         if not head or head[0] != "ready":
@@ -197,6 +217,9 @@ def bench_report(argv):
     for c in ("on", "keep"):
         if c in med:
             print(f"report {c} / off = {med[c] / med['off']:.4f}")
+    for c in ("refine", "reproj", "both"):
+        if c in med:
+            print(f"report {c} / dlt = {med[c] / med['dlt']:.4f}")
     if "parent_off" in med:
         lo, hi = min(rates["parent_off"]), max(rates["parent_off"])
         print(f"report off / parent_off = {med['off'] / med['parent_off']:.4f}; median of off "
