@@ -110,11 +110,22 @@ def heatmap_factors(means, scaling, rotation_raw, poses_2d, cameras, scaling_mod
     cov3D = covariance_from_scaling_rotation(scaling, rotation_raw, scaling_modifier)
     l1, l2 = ewa_lambdas_views(means, cov3D, cameras, W, H)           # (V, J) each
     J = l1.shape[1]
-    xs = torch.clamp(poses_2d[:, :, 0].long(), 0, W - 1)              # .long() truncates like the reference (:275-278)
-    ys = torch.clamp(poses_2d[:, :, 1].long(), 0, H - 1)
+    # No impulse (this library's own definition -- the reference raises inside scipy on a NaN sigma; DESIGN.md "Unobserved
+    # joints"): a joint whose mean holds a NaN has NaN lambdas, and a non-finite detection has no pixel.  Such a plane is all
+    # zero: row = col = 0, so cmin = 0 and den = 1e-8.  The responses of those planes are formed from stand-in values (sigma 1,
+    # pixel 0) and discarded, so that no conversion and no trip count sees a NaN; every other plane's bits are untouched.
+    seen = torch.isfinite(l1) & torch.isfinite(l2) & torch.isfinite(poses_2d[:, :, :2]).all(dim=-1)             # (V, J)
+    px = torch.where(seen, poses_2d[:, :, 0], torch.zeros_like(poses_2d[:, :, 0]))
+    py = torch.where(seen, poses_2d[:, :, 1], torch.zeros_like(poses_2d[:, :, 1]))
+    l1 = torch.where(seen, l1, torch.ones_like(l1))
+    l2 = torch.where(seen, l2, torch.ones_like(l2))
+    xs = torch.clamp(px.long(), 0, W - 1)                             # .long() truncates like the reference (:275-278)
+    ys = torch.clamp(py.long(), 0, H - 1)
     # sigma1 filters axis 0 (rows), sigma2 axis 1 (columns); all V*J one-dimensional responses in one go
-    row = (255.0 * _impulse_response_1d(ys.reshape(-1), torch.sqrt(l1).reshape(-1), H, dev)).reshape(V, J, H).contiguous()
-    col = _impulse_response_1d(xs.reshape(-1), torch.sqrt(l2).reshape(-1), W, dev).reshape(V, J, W).contiguous()
+    row = (255.0 * _impulse_response_1d(ys.reshape(-1), torch.sqrt(l1).reshape(-1), H, dev)).reshape(V, J, H)
+    col = _impulse_response_1d(xs.reshape(-1), torch.sqrt(l2).reshape(-1), W, dev).reshape(V, J, W)
+    row = torch.where(seen[:, :, None], row, torch.zeros_like(row)).contiguous()
+    col = torch.where(seen[:, :, None], col, torch.zeros_like(col)).contiguous()
     cmin = row.amin(dim=2) * col.amin(dim=2)
     cmax = row.amax(dim=2) * col.amax(dim=2)
     den = cmax - cmin + 1e-8

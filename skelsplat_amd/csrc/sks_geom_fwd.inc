@@ -29,7 +29,12 @@ __device__ __forceinline__ uint4 geom_fwd_one(int P, const VT& vt, const float* 
     const float p_orig[3] = { means[3 * li], means[3 * li + 1], means[3 * li + 2] };
     float p_view[3];
     transformPoint4x3(p_orig, V, p_view);
-    if (live && p_view[2] > 0.2f) {
+    // The near-plane cull, written so that NOT being in front of the plane is what rejects: a mean with a NaN coordinate has a
+    // NaN view depth, for which `z > 0.2f` is false, so an unobserved joint (DESIGN.md "Unobserved joints") is culled like a
+    // Gaussian behind the camera and leaves the same record -- radius 0, rect 0.  (The reference rejects `z <= 0.2f`, which lets
+    // a NaN through; for every other depth the two are the same test.)
+    const bool culled = !(p_view[2] > 0.2f);
+    if (live && !culled) {
         float p_hom[4];
         transformPoint4x4(p_orig, PM, p_hom);
         const float p_w = 1.0f / (p_hom[3] + 0.0000001f);
@@ -202,5 +207,6 @@ __global__ void k_mark_visible(int P, const float* __restrict__ means, const flo
     const float p[3] = { means[3 * idx], means[3 * idx + 1], means[3 * idx + 2] };
     float pv[3];
     transformPoint4x3(p, V, pv);
-    present[idx] = pv[2] > 0.2f;
+    const bool culled = !(pv[2] > 0.2f);   // (geom_fwd_one's cull: a NaN depth is not visible)
+    present[idx] = !culled;
 }

@@ -79,7 +79,12 @@ __device__ inline void early_stop_decide(const AdamArgs& a, int* st, int* host_f
             const float d0 = s_xyz[3 * i0] - s_xyz[3 * i1], d1 = s_xyz[3 * i0 + 1] - s_xyz[3 * i1 + 1], d2 = s_xyz[3 * i0 + 2] - s_xyz[3 * i1 + 2];
             len[k] = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
         }
-        cons = (fabsf(len[0] - len[1]) + fabsf(len[2] - len[3])) * a.lambda_consistency;
+        // A pair (arms, legs) with a non-finite limb length -- one of its joints is unobserved, DESIGN.md "Unobserved joints" --
+        // is left out of the loss, as adam_block_finish leaves it out of the gradient (its direction and sign selections are 0
+        // for a NaN length).  For finite lengths the sum is the one it always was.
+        const float arms = (isfinite(len[0]) && isfinite(len[1])) ? fabsf(len[0] - len[1]) : 0.0f;
+        const float legs = (isfinite(len[2]) && isfinite(len[3])) ? fabsf(len[2] - len[3]) : 0.0f;
+        cons = (arms + legs) * a.lambda_consistency;
     }
     const int w = a.es_window, ring = 2 * w;
     const int it0 = a.counters[0] + 1;
@@ -207,7 +212,9 @@ __device__ __forceinline__ void adam_block_finish(const AdamArgs& a, float* s_xy
 #pragma unroll
             for (int c = 0; c < 3; c++) dir[k][c] = len[k] > 0.0f ? d[c] / len[k] : 0.0f;
         }
-        // d|x|/dx = sign(x) (torch.norm of a scalar; 0 at 0)
+        // d|x|/dx = sign(x) (torch.norm of a scalar; 0 at 0).  A NaN length -- an unobserved joint on the pair -- compares false
+        // both ways: the sign is 0 and the whole pair adds +-0 to gc, exactly; so does the NaN limb's own direction above
+        // (`len > 0` is false).  early_stop_decide drops the same pair from the loss.
         const float sa = (len[0] - len[1]) > 0.0f ? 1.0f : ((len[0] - len[1]) < 0.0f ? -1.0f : 0.0f);
         const float sl = (len[2] - len[3]) > 0.0f ? 1.0f : ((len[2] - len[3]) < 0.0f ? -1.0f : 0.0f);
         const float coef[4] = { sa, -sa, sl, -sl };

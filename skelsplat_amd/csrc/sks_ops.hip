@@ -479,8 +479,19 @@ __global__ __launch_bounds__(256) void k_heatmap_factors(int J, int W, int H, co
     float R[3][3], sd[3], Sg[3][3], l1, l2;
     sks::gaussian_sigma(rots + 4 * j, scales + 3 * j, scale_modifier, R, sd, Sg);
     sks::ewa_lambdas(Sg, viewmatrix + 16 * v, means + 3 * j, W, H, tan.x[v], tan.y[v], l1, l2);
+    // ---- no impulse: an unobserved joint (a NaN mean makes both lambdas NaN) or a non-finite detection (DESIGN.md "Unobserved
+    // joints").  The plane is all zero: row = col = 0, cmin = 0, den = 1e-8 -- what the arithmetic below gives for NaN lambdas
+    // (no loop trip is taken, the normalisation is 1), stated here so that no trip count and no float -> int conversion ever
+    // sees a non-finite number.  (block-uniform: every thread has the same scalars)
+    const float det_x = poses_2d[2 * vj], det_y = poses_2d[2 * vj + 1];
+    if (!(isfinite(l1) && isfinite(l2) && isfinite(det_x) && isfinite(det_y))) {
+        for (int i = threadIdx.x; i < H; i += 256) row[(size_t)vj * Hs + i] = 0.0f;
+        for (int i = threadIdx.x; i < W; i += 256) col[(size_t)vj * Ws + i] = 0.0f;
+        if (threadIdx.x == 0) { cmin[vj] = 0.0f; den[vj] = 1e-8f; }
+        return;
+    }
     // ---- responses: sigma1 filters rows (axis 0), sigma2 columns; the impulse sits at the truncated 2D detection ----
-    const int xs = min(max((int)poses_2d[2 * vj], 0), W - 1), ys = min(max((int)poses_2d[2 * vj + 1], 0), H - 1);
+    const int xs = min(max((int)det_x, 0), W - 1), ys = min(max((int)det_y, 0), H - 1);
     float rmin, rmax, kmin, kmax;
     impulse_response(H, ys, sqrtf(l1), 255.0f, row + (size_t)vj * Hs, s_red, rmin, rmax);
     impulse_response(W, xs, sqrtf(l2), 1.0f, col + (size_t)vj * Ws, s_red, kmin, kmax);

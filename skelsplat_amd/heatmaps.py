@@ -35,7 +35,9 @@ def heatmap_factors(means, scaling, rotation_raw, poses_2d, cameras, scaling_mod
     list frames x Vf views frame-major, the parameters are stacked (frames, J, ..) and poses_2d is (frames*Vf, J, 2).
     `out`: a rasterizer.HeatmapFactors to fill in place (the sparse fused step reads the factors themselves, no plane is
     ever written); only then may the cameras differ in size (rows / columns keep the largest view's strides).
-    `drop_mask` (V,J) bool: planes without an impulse (see generate_heatmaps)."""
+    `drop_mask` (V,J) bool: planes without an impulse (see generate_heatmaps).
+    A joint whose mean holds a NaN (an unobserved joint, DESIGN.md "Unobserved joints") and a non-finite detection draw no
+    impulse either: row = col = 0, cmin = 0, den = 1e-8, an all-zero plane (oracle/heatmaps_ref.py defines the same)."""
     from . import _lib
     from ._base import ViewBatch, _f32c
     dev = means.device

@@ -44,6 +44,21 @@ def limb_3d_consistency_loss(xyz, dataset):
     return torch.norm(l_arm - r_arm) + torch.norm(l_leg - r_leg)
 
 
+def limb_consistency_observed(xyz, dataset):
+    """limb_3d_consistency_loss as the loops apply it (DESIGN.md "Unobserved joints"): a pair (arms, legs) that holds a joint
+    with a non-finite coordinate adds 0 to the loss and 0 to every gradient, the other pair is unaffected -- the rule of the device
+    tail (sks_loop_dev.h).  The lengths of such a pair are taken from zeros in place of the missing rows, so that autograd
+    never multiplies a NaN by the 0 it is weighted with.  For finite `xyz` the value and the gradient are
+    limb_3d_consistency_loss's, bit for bit (the weights are 1.0)."""
+    (la0, la1), (ra0, ra1), (ll0, ll1), (rl0, rl1) = DATASETS[dataset]["limbs"]
+    seen = torch.isfinite(xyz).all(dim=-1)
+    safe = torch.where(seen[:, None], xyz, torch.zeros_like(xyz))
+    length = lambda a, b: torch.norm(safe[a] - safe[b], dim=-1)
+    arms = (seen[la0] & seen[la1] & seen[ra0] & seen[ra1]).to(xyz.dtype)
+    legs = (seen[ll0] & seen[ll1] & seen[rl0] & seen[rl1]).to(xyz.dtype)
+    return torch.norm(length(la0, la1) - length(ra0, ra1)) * arms + torch.norm(length(ll0, ll1) - length(rl0, rl1)) * legs
+
+
 def masked_l2_grad_torch(render, gt):
     """Plain-tensor-op statement of the masked-L2 gradient (device-side, no host sync); render, gt: (V,C,H,W).
     Returns (dL, per-view loss, per-view scale): the true gradient is dL * scale[v]."""
@@ -455,7 +470,8 @@ class MultiViewLoop(_GroupLoop):
         `points=None`: the initial joints are the DLT triangulation of `poses_2d` (triangulation.triangulate_sequence, on
         the device, on the current stream; with `dropout` the dropped planes' detections stay out of it).  It needs all V
         views' detections, so a view-sharded loop (world > 1) refuses it; a joint kept in fewer than two views has no
-        triangulation and starts as NaN.
+        triangulation and starts as NaN: it is then UNOBSERVED for the whole loop, on every path of this class (DESIGN.md
+        "Unobserved joints").  The same holds for a NaN row of explicit `points`.
         `poses_3d` (V,J,3), with `points=None`: the initial joints are instead the reprojection-error-weighted mean of the
         views' 3D predictions (initial_guess.fuse_predictions, the reference's "metrabs" guess), under the same conditions; a
         joint whose views are all dropped starts as NaN.  Together with explicit `points` it is refused.
@@ -583,7 +599,7 @@ class MultiViewLoop(_GroupLoop):
 
     def _consistency_grad(self):
         xyz = self.gm._xyz.detach().clone().requires_grad_(True)
-        loss = limb_3d_consistency_loss(xyz, self.dataset) * self.lambda_consistency
+        loss = limb_consistency_observed(xyz, self.dataset) * self.lambda_consistency
         (gx,) = torch.autograd.grad(loss, xyz)
         return gx, loss.detach()
 
@@ -710,7 +726,7 @@ class MultiViewLoop(_GroupLoop):
         l2 = (sums[:, 0] / sums[:, 1].clamp_min(1.0)).to(torch.float32)
         cons = torch.zeros((), dtype=torch.float32)
         if self.lambda_consistency != 0.0:
-            cons = (limb_3d_consistency_loss(self.gm._xyz.detach(), self.dataset) * self.lambda_consistency).float().cpu()
+            cons = (limb_consistency_observed(self.gm._xyz.detach(), self.dataset) * self.lambda_consistency).float().cpu()
         return self._cut_where_stopped(grp, l2, cons).key
 
     def _gathered_rows(self):
@@ -1035,7 +1051,9 @@ class FrameBatchLoop(_GroupLoop):
         written straight into `self.xyz` by one launch on the current stream, in front of the heat-map factors that read
         them: detections already on the device never touch the host.  `drop_masks` are then also the DLT's
         `valid = ~drop_masks` -- a dropped plane is a detection the caller does not trust --, and a joint kept in fewer than
-        two views has no triangulation: it starts as NaN.  Ready `heatmaps` carry no detections: refused.
+        two views has no triangulation: it starts as NaN, and is then UNOBSERVED for the whole loop (DESIGN.md "Unobserved
+        joints": it renders nothing, its planes are zero, its limb pair leaves the loss, it stays NaN, and neither the frame's
+        other joints nor any other frame notice).  Ready `heatmaps` carry no detections: refused.
         `poses_3d` (F,V,J,3), with `points=None`: the initial joints are instead the reprojection-error-weighted mean of the
         views' 3D predictions (initial_guess.fuse_predictions, the reference's "metrabs" guess), written into `self.xyz` by one
         launch in the same place with the same `valid = ~drop_masks`; a joint whose views are all dropped starts as NaN.

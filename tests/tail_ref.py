@@ -49,23 +49,40 @@ K_U = 1 + 1       # step_size * .: the step size rounded to float, the multiplic
 K_P = 1           # param - .
 
 
-def limb_loss(xyz, limb):
+def pairs_kept(limb, missing=()):
+    """Which of the two limb-symmetry pairs (arms: limb[0:4], legs: limb[4:8]) the loss keeps: a pair that touches an
+    UNOBSERVED joint (`missing`; DESIGN.md "Unobserved joints") is left out of the loss and of every gradient."""
+    missing = set(int(p) for p in missing)
+    return tuple(not (set(limb[4 * h:4 * h + 4]) & missing) for h in range(2))
+
+
+def limb_loss(xyz, limb, missing=()):
     """loop.limb_3d_consistency_loss (utils/loss_utils.py:226-250) for any four joint pairs `limb` (8 indices); the CPU suite
-    holds it to that function on the datasets' own pairs."""
+    holds it to that function on the datasets' own pairs.  `missing`: see pairs_kept; the lengths of a pair that is left out
+    are never formed (its rows of `xyz` may hold NaN)."""
     n = lambda a, b: torch.norm(xyz[a] - xyz[b], dim=-1)
-    return torch.norm(n(limb[0], limb[1]) - n(limb[2], limb[3])) + torch.norm(n(limb[4], limb[5]) - n(limb[6], limb[7]))
+    if not missing:
+        return torch.norm(n(limb[0], limb[1]) - n(limb[2], limb[3])) + torch.norm(n(limb[4], limb[5]) - n(limb[6], limb[7]))
+    total = torch.zeros((), dtype=xyz.dtype)
+    for h, kept in enumerate(pairs_kept(limb, missing)):
+        if kept:
+            total = total + torch.norm(n(limb[4 * h], limb[4 * h + 1]) - n(limb[4 * h + 2], limb[4 * h + 3]))
+    return total
 
 
-def _limb_grad(xyz64, lam32, limb):
+def _limb_grad(xyz64, lam32, limb, missing=()):
     """(gradient of float32(lambda) x limb loss wrt xyz, its sum of |terms|), (P,3) float64 each."""
     P = xyz64.shape[0]
-    if limb is None or float(lam32) == 0.0:
+    kept = pairs_kept(limb, missing) if limb is not None else (False, False)
+    if limb is None or float(lam32) == 0.0 or not any(kept):
         return torch.zeros((P, 3), dtype=torch.float64), torch.zeros((P, 3), dtype=torch.float64)
     x = xyz64.clone().requires_grad_(True)
-    (g,) = torch.autograd.grad(limb_loss(x, limb) * float(lam32), x)
+    (g,) = torch.autograd.grad(limb_loss(x, limb, missing) * float(lam32), x)
     # |terms|: a joint's gradient is a sum of +-lambda * unit vectors, one per pair it ends; same sum with every sign +
     mag = torch.zeros((P, 3), dtype=torch.float64)
     for k in range(4):
+        if not kept[k // 2]:
+            continue
         d = xyz64[limb[2 * k]] - xyz64[limb[2 * k + 1]]
         ln = d.norm()
         if float(ln) > 0.0:
@@ -113,18 +130,20 @@ def lr_ref(sched, iteration):
 
 
 def adam_step_ref(grads, slots, group_mask, last_view, params, exp_avg, exp_avg_sq, counters, acc_steps, sched, lrs, adam,
-                  lam, limb):
+                  lam, limb, missing=()):
     """ONE sks_loop_adam_step call in float64 from the state BEFORE it.  grads (V,P,11), slots (V,P,3), params = (xyz (P,3),
     scaling (P,3), rotation (P,4), opacity (P,1)), exp_avg / exp_avg_sq (P,11), counters = (iteration, adam steps); `lam` is
     rounded to float32 like the C argument.  Returns a dict of (value, allowance in units of 2**-24) pairs for
-    "slots", "m", "v", "xyz", "scaling", "rotation", "opacity", and "counters" (ints)."""
+    "slots", "m", "v", "xyz", "scaling", "rotation", "opacity", and "counters" (ints).
+    `missing`: unobserved joints (pairs_kept) -- their rows of xyz hold NaN and stay NaN (compared as such), a limb pair that
+    touches one adds nothing to any joint's gradient; the rounding counts of every other row are what they are without it."""
     d = lambda t: torch.as_tensor(t).detach().cpu().to(torch.float64)
     grads, slots, m0, v0 = d(grads), d(slots).clone(), d(exp_avg), d(exp_avg_sq)
     prm = [d(p) for p in params]
     V, P = grads.shape[0], grads.shape[1]
     lam32 = np.float32(lam)
     # slots of the views in the mask <- this group's xyz gradient + the limb gradient (train.py:150-152,175)
-    gc, gc_mag = _limb_grad(prm[0], lam32, limb)
+    gc, gc_mag = _limb_grad(prm[0], lam32, limb, missing)
     slot_allow = torch.zeros_like(slots)
     for v in range(V):
         if (group_mask >> v) & 1:
