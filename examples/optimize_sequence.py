@@ -4,6 +4,7 @@ other, train.py:74-99) -- but many frames per launch: noisy 2D detections of N f
 iterations of the multi-view loop for every frame (loop.FramePipeline) -> MPJPE per frame.
 python examples/optimize_sequence.py [--frames 64] [--per-launch 16] [--streams 2] [--iters 500] [--init host|device|fuse] [--rigs R]
     [--report] [--uncertainty] [--reject-px PX] [--corrupt K] [--refine [--huber-px D]] [--images DIR [--image-frames 0,31,63]]
+    [--smooth H [--smooth-degree D]] [--motion wobble|smooth]
 --rigs R: the frames cycle through R jittered ring rigs (SyntheticScene seeds 0 .. R-1), as a dataset whose scenes bring their own
 cameras does; one rigs.RigBank holds them on the device and every batch names its frames' rigs (rig_ids).
 --init host (default): the DLT runs on the host, frame by frame, and its points are uploaded; --init device: the detections
@@ -34,6 +35,14 @@ and .._per_joint) and the mean trace of the covariance.
 one sub-directory per frame -- made on the device while the timed sequence runs (pipe.set_debug_images, skelsplat_amd/preview.py)
 and written afterwards.  With --corrupt and --reject-px the misplaced blobs the rejection leaves in the heat-maps are there to see
 in heatmap_*.png.  Not with --rigs > 1.
+--smooth H [--smooth-degree D] (with --report's ground truth): the optimised joints are smoothed over time on the device once the
+sequence is through (pipe.set_smoothing, skelsplat_amd/smoothing.py): a local polynomial fit of degree D (default 2) over H frames
+on each side, tricube taper; with --uncertainty every frame of a joint is weighted by the inverse of its optimised Gaussian's
+covariance, else by 1.  Printed: MPJPE, Accel and Accel error (smoothing.sequence_accel) of the raw and of the smoothed joints --
+with --uncertainty for both weightings, next to the calibration table that says how far the covariances were from calibrated.
+--motion smooth: the skeleton moves on low-frequency sinusoids per joint instead of the default `wobble`, whose ground truth jumps
+independently by 5 mm per frame -- a signal no temporal filter can beat.  What the covariance weights gain on real sequences has not
+been measured.
 The curve falls from the reference's default start, --init fuse (21.7 -> 14.3 mm); from the DLT start (--init host / device) it
 RISES from 13.4 to 14.3 mm in the first steps: on this synthetic sequence (3 px of detection noise, exact cameras) the DLT already
 sits below the optimiser's fixed point, and the curve shows it."""
@@ -70,6 +79,9 @@ def main(argv=None):
     ap.add_argument("--huber-px", type=float, default=None)
     ap.add_argument("--images", default=None, metavar="DIR")
     ap.add_argument("--image-frames", default=None, metavar="I,J,..")
+    ap.add_argument("--smooth", type=int, default=None, metavar="H")
+    ap.add_argument("--smooth-degree", type=int, default=2, metavar="D")
+    ap.add_argument("--motion", choices=("wobble", "smooth"), default="wobble")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     sc = SyntheticScene(args.dataset, n_views=args.views, seed=0, device=dev)
@@ -77,8 +89,14 @@ def main(argv=None):
     rig_of = [f % args.rigs for f in range(args.frames)]
     rng = np.random.default_rng(1)
     # a moving skeleton: the template drifts and wobbles from frame to frame; detections carry 3 px of noise
-    gt = np.stack([sc.pose_3d_gt + np.array([8.0 * f, 3.0 * f, 0.0]) + rng.normal(0, 5.0, sc.pose_3d_gt.shape)
-                   for f in range(args.frames)])
+    if args.motion == "wobble":
+        gt = np.stack([sc.pose_3d_gt + np.array([8.0 * f, 3.0 * f, 0.0]) + rng.normal(0, 5.0, sc.pose_3d_gt.shape)
+                       for f in range(args.frames)])
+    else:       # the same drift, and per joint and coordinate a sinusoid of 20-60 mm with a period of 25-100 frames
+        mrng = np.random.default_rng(2)
+        amp, period, phase = (mrng.uniform(lo, hi, sc.pose_3d_gt.shape) for lo, hi in ((20.0, 60.0), (25.0, 100.0), (0.0, 2.0 * np.pi)))
+        gt = np.stack([sc.pose_3d_gt + np.array([8.0 * f, 3.0 * f, 0.0]) + amp * np.sin(2.0 * np.pi * f / period + phase)
+                       for f in range(args.frames)])
     p2d = np.stack([np.stack([project_points(c, gt[f]) + rng.normal(0, 3.0, (sc.n_points, 2)) for c in rigs[rig_of[f]]])
                     for f in range(args.frames)]).astype(np.float32)
     for f in range(args.frames if args.corrupt else 0):
@@ -87,6 +105,8 @@ def main(argv=None):
             p2d[f, k // sc.n_points, k % sc.n_points] += (r * np.cos(th), r * np.sin(th))
     if args.uncertainty and not args.report:
         ap.error("--uncertainty measures against --report's ground truth: use the two together")
+    if args.smooth is not None and not args.report:
+        ap.error("--smooth prints its errors against --report's ground truth: use the two together")
     if args.reject_px is not None and args.init != "device":
         ap.error("--reject-px rejects while triangulating on the device: use it with --init device")
     if args.refine and args.init != "device":
@@ -132,6 +152,8 @@ def main(argv=None):
         def run():
             init = host_init()
             return pipe.optimize_sequence(init, p2d, iterations=args.iters, **ids), init
+    if args.smooth is not None:
+        pipe.set_smoothing(args.smooth, degree=args.smooth_degree, use_covariance=args.uncertainty)
     if args.report:
         pipe.set_reprojection_report()
         gt_dev = torch.as_tensor(gt.astype(np.float32), device=dev)
@@ -202,6 +224,17 @@ def main(argv=None):
         for name, t in (("initial", tables["initial"][0].tolist()), ("optimised", tables["final"][0].tolist())):
             print(f"reprojection error of the {name} joints: mean {t[0]:.3f} px; per view "
                   + " ".join(f"{x:.3f}" for x in t[1:1 + args.views]))
+    if args.smooth is not None:
+        from skelsplat_amd.report import evaluate_sequence
+        from skelsplat_amd.smoothing import sequence_accel, smooth_sequence
+        rows = [("raw", out), ("smoothed, covariance weights" if args.uncertainty else "smoothed, unit weights", pipe.smoothed.joints)]
+        if args.uncertainty:
+            rows.append(("smoothed, unit weights", smooth_sequence(out, half_window=args.smooth, degree=args.smooth_degree).joints))
+        print(f"temporal smoothing, {args.smooth} frames on each side, degree {args.smooth_degree}, tricube taper ({args.motion} motion):")
+        for name, x in rows:
+            acc = sequence_accel(x, gt_dev)
+            print(f"  {name:30s} MPJPE {float(evaluate_sequence(x, gt_dev)['abs']):7.3f} mm   Accel {float(acc['accel']):7.3f}   "
+                  f"Accel error {float(acc['accel_error']):7.3f}  (mm per frame^2)")
     if args.uncertainty:
         from skelsplat_amd.uncertainty import calibration
         unc = pipe.gaussians.uncertainty(gt_dev)
@@ -212,7 +245,10 @@ def main(argv=None):
         print("ground truth inside   1 sigma   2 sigma   3 sigma")
         for name, row in [("all joints", cal["overall"].tolist())] + list(zip(names, cal["per_joint"].tolist())):
             print(f"{name:18s} " + " ".join(f"{100.0 * x:8.1f}%" for x in row))
-    return dict(joints=out, gt=gt_dev, activities=acts, aligned=eva) if args.report else None
+    res = dict(joints=out, gt=gt_dev, activities=acts, aligned=eva) if args.report else None
+    if args.smooth is not None:
+        res["smoothed"] = pipe.smoothed
+    return res
 
 
 if __name__ == "__main__":

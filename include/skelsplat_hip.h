@@ -463,6 +463,82 @@ int sks_triangulate_refine(int N, int V, int J, const double* proj, size_t rig_s
                            const double* poses_2d_f64, const unsigned char* valid, const float* xyz0, const double* xyz0_f64,
                            double huber_px, int max_iters, float* xyz, double* xyz_f64, double* cost, int* iters, void* stream);
 
+/* Covariance-weighted temporal smoothing of a sequence, and the smoothness figures that go with it (csrc/sks_smooth.hip; added to
+ * sks_version 14: the number did not move).  The reference optimises every frame on its own; this is the local polynomial fit a
+ * consumer of its poses runs afterwards, with every joint's optimised 3x3 covariance (sks_joint_uncertainty's cov6) as the weight
+ * of its frame.  What it gains on real sequences depends on how well those covariances are calibrated (sks_calibration) and has
+ * NOT been measured.  One launch each on `stream`, nothing synchronises, no atomics, no scratch.  Device memory unless marked HOST.
+ *
+ * THE FIT (one definition: the kernel, smoothing.smooth_host and tests/smooth_ref.py follow it).  Inputs: xyz (N,J,3) floats;
+ * optional cov6 (N,J,6) floats xx, xy, xz, yy, yz, zz; optional weights (N,J) floats; optional valid (N,J) bytes; optional
+ * group_ids (N) ints; half_window h, degree d, taper, cov_floor >= 0 (mm^2).  For every target (f, j) the taps are the frames
+ * k = max(0, f - h) .. min(N - 1, f + h) in ASCENDING order, t = k - f.  A tap is USABLE when group_ids[k] == group_ids[f],
+ * valid[k,j] != 0, xyz[k,j] is finite, weights[k,j] is finite and > 0 (each where given) and, with cov6, the covariance
+ * C = cov6[k,j] widened to float64 with cov_floor added to xx, yy, zz has three finite pivots > 0 in this LDL^T (all float64, one
+ * rounding per operation, no fused multiply-add anywhere below):
+ *     d0 = xx;  l10 = xy / d0;  l20 = xz / d0;  d1 = yy - l10 * xy;  e = yz - l20 * xy;  z1 = zz - l20 * xz;  l21 = e / d1;
+ *     d2 = z1 - l21 * e.
+ * Its information matrix Lambda = C^-1 (the identity without cov6) is, with i0 = 1 / d0, i1 = 1 / d1, i2 = 1 / d2 and
+ * m = l21 * l10 - l20:
+ *     xx = (i0 + (l10 * l10) * i1) + (m * m) * i2;  xy = -(l10 * i1) - (m * l21) * i2;  xz = m * i2;
+ *     yy = i1 + (l21 * l21) * i2;  yz = -(l21 * i2);  zz = i2.
+ * Its weight is omega = w * taper with w = weights[k,j] widened (1 without weights) and taper = 1 (SKS_SMOOTH_BOX) or, with
+ * u = |t| / (h + 1) and q = 1 - (u * u) * u, (q * q) * q (SKS_SMOOTH_TRICUBE).  With n usable taps the effective degree is
+ * d_eff = min(d, n - 1) and the fit minimises  sum_k omega_k (x_k - sum_i c_i t^i)^T Lambda_k (x_k - sum_i c_i t^i)  over the
+ * 3-vectors c_0 .. c_d_eff through its normal equations, formed about x_0 = the FIRST usable tap's position (a difference of two
+ * floats is exact in float64).  Per usable tap, in ascending k, starting from zeros:
+ *     W = omega * Lambda (six products);  dx = x_k - x_0;  v_r = (W_r0 * dx_0 + W_r1 * dx_1) + W_r2 * dx_2;
+ *     t^0 .. t^4 = 1, t, t * t, (t * t) * t, (t * t) * (t * t)  (exact);
+ *     M_p = M_p + t^p * W  for p = 0 .. 2d;   r_a = r_a + t^a * v  for a = 0 .. d.
+ * The unknowns are ordered c_d_eff, .., c_1, c_0 (the position LAST): B = [M_(2 d_eff - a - b)] in 3x3 blocks a, b = 0 .. d_eff,
+ * y = [r_(d_eff - a)], m = 3 (d_eff + 1) rows.  LDL^T in place on the lower triangle, right-looking, the right-hand side with it:
+ *     for j = 0 .. m-1:  for i = j+1 .. m-1: l_i = B[i][j] / B[j][j];
+ *                        for i = j+1 .. m-1, for c = j+1 .. i: B[i][c] = B[i][c] - l_i * B[c][j]   (B[c][j] still undivided);
+ *                        for i = j+1 .. m-1: B[i][j] = l_i, y[i] = y[i] - l_i * y[j];
+ *     for j = 0 .. m-1:  y[j] = y[j] / B[j][j];
+ *     for j = m-1 .. 1:  for i = 0 .. j-1: y[i] = y[i] - B[j][i] * y[j].
+ * c_0 = y[m-3 .. m-1], c_1 = y[m-6 .. m-4].  The trailing 3x3 of the factor is the LDL^T of the position's Schur complement, so the
+ * fit's own covariance of the position -- the top-left block of the inverse normal matrix in the order c_0, c_1, .. -- is Lambda's
+ * formula above on d0, d1, d2 = B[m-3][m-3], B[m-2][m-2], B[m-1][m-1] and l10, l20, l21 = B[m-2][m-3], B[m-1][m-3], B[m-1][m-2].
+ * Outputs, each rounded to float once: joints = c_0 + x_0 (added in float64), velocity = c_1 in mm per frame (0 when d_eff = 0),
+ * cov6 as above, n_used = n.  With n = 0 the three float outputs are NaN and n_used is 0.  A joint whose own row is NaN or
+ * masked out but has usable taps in its window receives a value: the gap is filled.
+ *
+ * sks_smooth_sequence: the fit of all N x J targets.  1 <= N <= 2^30, 1 <= J <= SKS_SMOOTH_MAX_JOINTS, 1 <= half_window <=
+ *   SKS_SMOOTH_MAX_HALF_WINDOW, 0 <= degree <= 2, cov_floor finite and >= 0; xyz and out_xyz (N,J,3) are required and must not
+ *   overlap (a workgroup reads the frames of its neighbours); out_vel (N,J,3), out_cov6 (N,J,6), n_used (N,J) ints are optional.
+ *   One (frame, joint) per lane; a workgroup of 256 threads owns a tile of T consecutive frames x all J joints, stages the tile and
+ *   half_window halo frames on each side once -- usable?, weight, position and Lambda per staged (frame, joint), 64 bytes, in LDS --
+ *   and each lane then walks its own taps in ascending order.  Where T + 2 half_window frames of all joints would not fit 64 KiB
+ *   (large J x half_window), the joints are split into equal runs and a workgroup owns T frames of one run.  A target's outputs
+ *   depend on its own window only: never on N, on its place in a tile, on the launch shape or on the stream.
+ * sks_smooth_launch: HOST only, no GPU call: out[SKS_SMOOTH_TILE] = T, out[SKS_SMOOTH_GROUPS] = the workgroups,
+ *   out[SKS_SMOOTH_THREADS] = the threads per workgroup, out[SKS_SMOOTH_LDS_BYTES] = the LDS bytes of a workgroup, for a call of
+ *   this N, J and half_window.
+ * sks_eval_accel: the sequence's "Accel" and "Accel error" of the video-pose literature.  xyz, gt (N,J,3) floats (gt or NULL),
+ *   group_ids (N) ints or NULL, 0 <= n_groups <= SKS_EVAL_MAX_GROUPS (n_groups > 0 needs group_ids; group_ids with n_groups = 0
+ *   still fence the frames).  Per joint a_f = (x_(f-1) - 2 * x_f) + x_(f+1) per coordinate in float64, |a| = sqrt((a_0 * a_0 +
+ *   a_1 * a_1) + a_2 * a_2); the error is the same norm of a - a_gt.  Frame f (1 .. N-2) of joint j ENTERS the first figure when
+ *   its three positions are finite and frames f-1, f, f+1 carry the same group id, the second when the ground truth's three are
+ *   finite too.  out (1 + n_groups, 2, 1 + J) doubles: row 0 over all frames, row 1 + g over the frames with group_ids[f] == g;
+ *   [.,0,.] the mean |a|, [.,1,.] the mean error (NaN without gt); column 0 over all joints (a frame's joints in index order),
+ *   column 1 + j over joint j; NaN where nothing entered.  One workgroup per row: thread t takes frames 1 + t, 1 + t + 256, ... in
+ *   index order and the 256 partial sums and counts meet in a fixed tree, so every figure is bitwise the same from run to run. */
+#define SKS_SMOOTH_MAX_JOINTS       256
+#define SKS_SMOOTH_MAX_HALF_WINDOW  32
+#define SKS_SMOOTH_BOX              0
+#define SKS_SMOOTH_TRICUBE          1
+#define SKS_SMOOTH_TILE       0
+#define SKS_SMOOTH_GROUPS     1
+#define SKS_SMOOTH_THREADS    2
+#define SKS_SMOOTH_LDS_BYTES  3
+#define SKS_SMOOTH_LAUNCH_INTS 4
+int sks_smooth_sequence(int N, int J, const float* xyz, const float* cov6, const float* weights, const unsigned char* valid,
+                        const int* group_ids, int half_window, int degree, int taper, double cov_floor, float* out_xyz,
+                        float* out_vel, float* out_cov6, int* n_used, void* stream);
+int sks_smooth_launch(int N, int J, int half_window, int* out /*HOST SKS_SMOOTH_LAUNCH_INTS*/);
+int sks_eval_accel(int N, int J, const float* xyz, const float* gt, const int* group_ids, int n_groups, double* out, void* stream);
+
 /* Replaces fusedssim (submodules/fused-ssim/ssim.cu:368-404, binding ext.cpp): img1, img2, ssim_map and the three
  * optional partial-derivative maps (train == true) are (B,CH,H,W) fp32; "same" zero padding. */
 int sks_fused_ssim_fwd(int B, int CH, int H, int W, float C1, float C2, const float* img1, const float* img2,

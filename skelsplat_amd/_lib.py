@@ -30,6 +30,10 @@ SKS_REPORT_MAX_SAVES = 8
 SKS_EVAL_MAX_GROUPS = 64
 SKS_CALIBRATION_MAX_K = 8
 SKS_REFINE_MAX_ITERS = 16
+SKS_SMOOTH_MAX_JOINTS = 256
+SKS_SMOOTH_MAX_HALF_WINDOW = 32
+SKS_SMOOTH_BOX, SKS_SMOOTH_TRICUBE = 0, 1
+SKS_SMOOTH_LAUNCH_INTS = 4
 SKS_ALIGN_RIGID, SKS_ALIGN_SIMILARITY, SKS_ALIGN_SCALE = 0, 1, 2
 SKS_PREVIEW_LAUNCH_INTS = 4
 
@@ -168,6 +172,9 @@ SIGNATURES = {
     "sks_reproject": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sks_eval_reprojection": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "sks_triangulate_refine": (_i, [_i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, C.c_double, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sks_smooth_sequence": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "sks_smooth_launch": (_i, [_i, _i, _i, _vp]),
+    "sks_eval_accel": (_i, [_i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     **{name: (_i, [ct for _, ct in params]) for name, params in {**STEP_PARAMS, **DV_PARAMS}.items()},
     "sks_pose_errors": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "sks_loop_report": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
@@ -283,6 +290,18 @@ def preview_launch(W, H, aligned=True):
     out = (_i * SKS_PREVIEW_LAUNCH_INTS)()
     check(load().sks_preview_launch(W, H, 1 if aligned else 0, C.cast(out, _vp)), "sks_preview_launch")
     return {name: out[i] for i, name in enumerate(PREVIEW_LAUNCH_FIELDS)}
+
+
+# sks_smooth_launch's record: field name -> index (include/skelsplat_hip.h, SKS_SMOOTH_*)
+SMOOTH_LAUNCH_FIELDS = ("tile", "groups", "threads", "lds_bytes")
+
+
+def smooth_launch(N, J, half_window):
+    """The launch sks_smooth_sequence makes for N frames of J joints, as a dict over SMOOTH_LAUNCH_FIELDS: the tile length T in
+    frames, the workgroups, the threads per workgroup and a workgroup's LDS bytes (host only: sks_smooth_launch)."""
+    out = (_i * SKS_SMOOTH_LAUNCH_INTS)()
+    check(load().sks_smooth_launch(N, J, half_window, C.cast(out, _vp)), "sks_smooth_launch")
+    return {name: out[i] for i, name in enumerate(SMOOTH_LAUNCH_FIELDS)}
 
 
 def prefill_planes(V, P, C_, W, H, flags=0):

@@ -68,6 +68,39 @@ def _sequence_reprojection(loop, N):
     return SequenceReprojection(N, loop.V, loop.P, loop.device)
 
 
+def _smoothing(loop, half_window, degree, taper, use_covariance, cov_floor, groups):
+    """set_smoothing's arguments -> None (off) or the checked settings as a dict of smoothing.smooth_sequence's keywords plus
+    `use_covariance`; `groups` stays as given until a sequence's length is known (_sequence_smoothing)."""
+    if half_window is None:
+        return None
+    from .smoothing import _settings
+    h, d, floor, _ = _settings("set_smoothing", half_window, degree, taper, cov_floor)
+    if use_covariance and not loop.keep_gaussians:
+        raise ValueError("set_smoothing: use_covariance=True weights every frame by the covariance of its optimised Gaussians, which "
+                         "this loop does not keep -- build it with FrameBatchLoop / FramePipeline(..., keep_gaussians=True), or "
+                         "pass use_covariance=False for unit weights")
+    return dict(half_window=h, degree=d, taper=taper, cov_floor=floor, use_covariance=bool(use_covariance), groups=groups)
+
+
+def _sequence_smoothing(loop, N, who):
+    """optimize_sequence's smoothing settings with `groups` as an (N,) int32 tensor on the loop's device (uploaded on the caller's
+    stream); None for a loop whose smoothing is off (set_smoothing)."""
+    s = getattr(loop, "_smooth", None)      # (a loop without the switch: off)
+    if s is None:
+        return None
+    if s["use_covariance"] and not loop.keep_gaussians:
+        raise ValueError(f"{who}: set_smoothing(use_covariance=True) needs the Gaussians this loop no longer keeps (keep_gaussians)")
+    s = dict(s)
+    g = s["groups"]
+    if g is not None:
+        g = g if torch.is_tensor(g) else torch.as_tensor(np.asarray(g))
+        if g.dim() != 1 or g.shape[0] != N or g.is_floating_point() or g.dtype == torch.bool:
+            raise ValueError(f"{who}: the groups given to set_smoothing must be ({N},) integers, one per frame of this sequence, "
+                             f"got {tuple(g.shape)} {g.dtype}")
+        s["groups"] = g.to(device=loop.device, dtype=torch.int32)
+    return s
+
+
 def _sequence_consensus(loop, reject, N):
     """optimize_sequence's (inliers (N,V,J) bool, n_consensus (N,J) int32) on the device, None without rejection."""
     if reject is None:
@@ -178,7 +211,8 @@ class SequenceRun:
                     set_ground_truth left) as _checked_gt left it
       out, initial  (N,P,3) optimised joints; the initial joints, None unless `return_initial`
       inliers, n_consensus, report, gaussians, images, reprojection   what optimize_sequence documents under these names, None where the loop
-                    has the feature off;  stopped_at: None, or the (N,) int64 zeros of a pipeline with early stopping"""
+                    has the feature off;  stopped_at: None, or the (N,) int64 zeros of a pipeline with early stopping
+      smoothing     None or set_smoothing's settings for this sequence; smoothed() makes the result once every batch is taken"""
 
     def __init__(self, loop, gt_next, points, poses_2d, poses_3d, rig_ids, return_initial, who="optimize_sequence"):
         self.pts, self.p2d, self.N = _sequence_inputs(points, poses_2d)
@@ -195,6 +229,18 @@ class SequenceRun:
         self.gaussians = _sequence_gaussians(loop, self.out)
         self.images = _sequence_images(loop, self.N)
         self.reprojection = _sequence_reprojection(loop, self.N)
+        self.smoothing = _sequence_smoothing(loop, self.N, who)
+
+    def smoothed(self):
+        """Behind the last take(), on the CALLER's stream once it waits for every batch: None with the smoothing off, else
+        smoothing.smooth_sequence of `out` -- one launch, behind one joint_uncertainty launch when the covariances weight it.
+        Reads `out` and the kept Gaussians, writes neither."""
+        if self.smoothing is None:
+            return None
+        from .smoothing import smooth_sequence
+        kw = dict(self.smoothing)
+        cov6 = self.gaussians.uncertainty().cov6 if kw.pop("use_covariance") else None
+        return smooth_sequence(self.out, cov6, **kw)
 
     def starts(self):
         return range(0, self.N, self.F)     # the first frame of every batch

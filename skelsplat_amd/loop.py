@@ -22,7 +22,8 @@ import torch.distributed as dist
 
 from . import rasterizer as R
 from ._group import next_group
-from ._sequence import SequenceRun, _accept_gt, _checked_gt, _checked_refine, _checked_reject, _debug_frames, _refinement, _rejection
+from ._sequence import (SequenceRun, _accept_gt, _checked_gt, _checked_refine, _checked_reject, _debug_frames, _refinement, _rejection,
+                        _smoothing)
 from ._sequence import _sequence_predictions, _sequence_rig_ids     # noqa: F401  (callers and tests reach them as loop.<name>)
 from .scene import DATASETS
 
@@ -995,6 +996,8 @@ class FrameBatchLoop(_GroupLoop):
         self._refine = None     # set_refinement's (huber_px, max_iters)
         self._reproject = False     # set_reprojection_report
         self.reprojection = None    # optimize_sequence's reprojection.SequenceReprojection of the last sequence
+        self._smooth = None         # set_smoothing's settings
+        self.smoothed = None        # optimize_sequence's smoothing.Smoothed of the last sequence
         # new_scenes(points=None) with rejection: the views each joint of the batch was triangulated from, the winners' counts
         self.inliers = torch.ones((F, V, self.P), dtype=torch.bool, device=dev)
         self.n_consensus = torch.zeros((F, self.P), dtype=torch.int32, device=dev)
@@ -1186,6 +1189,21 @@ class FrameBatchLoop(_GroupLoop):
         self._reproject = bool(on)
         return self
 
+    def set_smoothing(self, half_window=None, degree=2, taper="tricube", use_covariance=True, cov_floor=0.0, groups=None):
+        """From now on every `optimize_sequence` smooths the joints it returns over time once all batches are taken
+        (smoothing.smooth_sequence: one launch on the caller's stream, nothing is read back) into `self.smoothed`, a
+        smoothing.Smoothed of joints, velocity, cov6 and n_used for all N frames; None after a sequence without it.
+        `half_window` frames on each side (None: off again), `degree` 0 .. 2, `taper` "box" or "tricube".  `use_covariance`: every
+        frame of a joint is weighted by the inverse of its optimised Gaussian's covariance -- one joint_uncertainty launch in
+        front, on a loop built with keep_gaussians=True (refused otherwise) --, with `cov_floor` mm^2 added to the diagonals;
+        False: unit weights.  `groups` (N,) integers, host or device: a window never crosses from one recording into the next
+        (checked against the next sequence's length).  A joint that ended NaN ("Unobserved joints") is filled from the frames
+        around it.  The joints `optimize_sequence` returns, `gaussians`, `report` and every other output are untouched, as are the
+        optimiser's steps and captured graphs.  What the covariance weights gain on real sequences depends on how well the
+        optimised covariances are calibrated (uncertainty.calibration) and has not been measured.  Returns the loop."""
+        self._smooth = _smoothing(self, half_window, degree, taper, use_covariance, cov_floor, groups)
+        return self
+
     def set_debug_images(self, frames):
         """The reference's debug pictures (configs/*.yaml `debug.save_images`, train.py:113-114, 143-144, 236-237) for the frames
         with these sequence indices, from now on: every `optimize_sequence` fills `self.images` (a preview.SequenceImages) with
@@ -1352,7 +1370,9 @@ class FrameBatchLoop(_GroupLoop):
         After `set_refinement(max_iters, huber_px)`, with `points=None` and without `poses_3d` (refused otherwise): every batch's
         triangulated joints are refined in place by one more launch (new_scenes).  After `set_reprojection_report()`:
         `self.reprojection` (a reprojection.SequenceReprojection) holds the reprojection errors of every frame's initial and final
-        joints against its detections; None otherwise."""
+        joints against its detections; None otherwise.
+        After `set_smoothing(half_window, ...)`: `self.smoothed` (a smoothing.Smoothed) holds the returned joints smoothed over
+        time, one launch behind the last batch; None otherwise."""
         run, self._gt_next = SequenceRun(self, self._gt_next, points, poses_2d, poses_3d, rig_ids, return_initial), None
         self.seq_inliers, self.seq_n_consensus = run.inliers, run.n_consensus
         self.report, self.gaussians, self.images = run.report, run.gaussians, run.images
@@ -1361,6 +1381,7 @@ class FrameBatchLoop(_GroupLoop):
             run.begin(self, b)
             self.run(iterations, groups_per_graph)      # (returns self.xyz, which take() copies)
             run.take(self, b)
+        self.smoothed = run.smoothed()
         self.check_rigs()
         return run.result()
 
@@ -1390,6 +1411,16 @@ class FramePipeline:
         self.images = None           # set_debug_images: preview.SequenceImages of the last optimize_sequence
         self.inliers = self.n_consensus = None     # optimize_sequence with rejection: (N,V,J) bool, (N,J) int32
         self.reprojection = None     # set_reprojection_report: reprojection.SequenceReprojection of the last optimize_sequence
+        self.smoothed = None         # set_smoothing: smoothing.Smoothed of the last optimize_sequence
+
+    def set_smoothing(self, half_window=None, degree=2, taper="tricube", use_covariance=True, cov_floor=0.0, groups=None):
+        """FrameBatchLoop.set_smoothing of every loop: from now on optimize_sequence smooths the joints it returns over time into
+        `self.smoothed` (a smoothing.Smoothed) by one launch on the caller's stream, behind its wait for every batch's stream --
+        and behind one joint_uncertainty launch with `use_covariance`, which needs keep_gaussians=True (`half_window=None`: off
+        again, and `smoothed` is None after the next sequence).  Returns the pipeline."""
+        for fb in self.loops:
+            fb.set_smoothing(half_window, degree, taper, use_covariance, cov_floor, groups)
+        return self
 
     def set_outlier_rejection(self, reject_px=None, min_inliers=3):
         """FrameBatchLoop.set_outlier_rejection of every loop: from now on optimize_sequence(None, detections) rejects outlier
@@ -1453,7 +1484,9 @@ class FramePipeline:
         After `set_refinement(max_iters, huber_px)`, with `points=None` and without `poses_3d` (refused otherwise): every batch's
         triangulated joints are refined in place by one more launch on its stream.  After `set_reprojection_report()`:
         `self.reprojection` (a reprojection.SequenceReprojection) holds the reprojection errors of every frame's initial and final
-        joints against its detections, two launches per batch on its own stream; None otherwise."""
+        joints against its detections, two launches per batch on its own stream; None otherwise.
+        After `set_smoothing(half_window, ...)`: `self.smoothed` (a smoothing.Smoothed) holds the returned joints smoothed over
+        time, enqueued on the caller's stream once it waits for every batch; None otherwise."""
         run, self._gt_next = SequenceRun(self.loops[0], self._gt_next, points, poses_2d, poses_3d, rig_ids, return_initial), None
         self.inliers, self.n_consensus = run.inliers, run.n_consensus
         self.report, self.gaussians, self.images = run.report, run.gaussians, run.images
@@ -1468,6 +1501,7 @@ class FramePipeline:
         schedule(run, iterations, groups_per_graph, interleave)
         for st in self.streams:
             cur.wait_stream(st)
+        self.smoothed = run.smoothed()
         self.check_rigs()
         return run.result()
 
