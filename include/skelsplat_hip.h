@@ -345,7 +345,16 @@ int sks_heatmaps(int V, int J, int W, int H, const float* row, const float* col,
  * floor(4 sigma + 0.5) of a sample counts -- the impulse and one mirror per side while radius <= n, further bounces on a
  * coarse image or under a wide Gaussian (any radius is exact; the cost grows with radius / n).  means3D (J,3), scales (J,3) activated,
  * rotations (J,4) raw quaternions, poses_2d (V,J,2) pixel (x, y), viewmatrix (V,16) as for sks_forward,
- * tanfovx/tanfovy HOST arrays of V. */
+ * tanfovx/tanfovy HOST arrays of V.
+ * A plane (view, joint) DRAWS NO IMPULSE -- row = col = +0 over the view's own H and W, cmin = 0, den = 1e-8f, nothing written
+ * beyond the view's size -- when (a) a lambda or a coordinate of the detection is not finite (a NaN or infinite mean gives NaN
+ * lambdas), (b) !(lambda1 > 0) || !(lambda2 > 0) (lambda2 = mid - sqrt(max(mid^2 - det, 0.1)) reaches about -0.016 for a
+ * footprint whose trace is below 0.032 px^2, and exactly +0), or (c) on either axis floor(4.0 * (double)sqrtf(lambda) + 0.5) >
+ * SKS_HEATMAP_MAX_RADIUS.  One degenerate axis makes the whole plane the no-impulse plane; every other plane is untouched.  (c)
+ * bounds the launch: per thread at most SKS_HEATMAP_MAX_RADIUS / 256 + 4 * ceil(n / 256) * (SKS_HEATMAP_MAX_RADIUS / 2n + 1) + 3 *
+ * ceil(n / 256) double-precision exp on an axis of n samples.  sks_view_footprints reports the raw lambdas the rule is applied to. */
+#define SKS_HEATMAP_MAX_RADIUS 262144   /* 2^18: 64 x the widest image in use; an axis of <= 4100 samples under such a kernel is flat
+                                           to an fp32 ulp */
 int sks_heatmap_factors(int V, int J, int W, int H, const float* means3D, const float* scales, const float* rotations,
                         float scale_modifier, const float* poses_2d, const float* viewmatrix, const float* tanfovx,
                         const float* tanfovy, float* row, float* col, float* cmin, float* den,
@@ -741,7 +750,7 @@ int sks_loop_fused_step_es(int V, int P, int C, int W, int H, const float* viewm
  *      for its frame and stores 1 + f into *error_word (device or pinned host memory, zeroed by the caller; one of them when
  *      several frames do);
  *  sks_geometry_dv, sks_heatmap_factors_dv, sks_heatmap_totals_dv: as the entry points they are named after, views_dev in place
- *      of tanfovx / tanfovy / view_wh;
+ *      of tanfovx / tanfovy / view_wh (sks_heatmap_factors_dv: the same no-impulse rule, SKS_HEATMAP_MAX_RADIUS included);
  *  sks_loop_fused_step_dv, sks_loop_fused_step_es_dv: views_dev in place of tanfovx / tanfovy, lr_sched_dev in place of lr_sched
  *      (the tail workgroup of frame f reads row f).  view_wh stays a HOST argument with the same sizes as views_dev holds: the
  *      compositing backward reads nothing but the sizes, which are fixed per view slot, and keeps them in its argument segment.

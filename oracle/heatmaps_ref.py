@@ -16,6 +16,8 @@ import math
 
 import torch
 
+HEATMAP_MAX_RADIUS = 1 << 18      # SKS_HEATMAP_MAX_RADIUS (include/skelsplat_hip.h; tests hold the two equal)
+
 
 def ewa_lambdas(means, cov3D, cam, W, H):
     """(lambda1, lambda2) of every Gaussian in one camera: general_utils.py:189-265; see ewa_lambdas_views."""
@@ -114,7 +116,13 @@ def heatmap_factors(means, scaling, rotation_raw, poses_2d, cameras, scaling_mod
     # joints"): a joint whose mean holds a NaN has NaN lambdas, and a non-finite detection has no pixel.  Such a plane is all
     # zero: row = col = 0, so cmin = 0 and den = 1e-8.  The responses of those planes are formed from stand-in values (sigma 1,
     # pixel 0) and discarded, so that no conversion and no trip count sees a NaN; every other plane's bits are untouched.
+    # The same for a degenerate footprint (DESIGN.md "Degenerate footprints"): a lambda that is not positive, or a truncation
+    # radius floor(4 sigma + 0.5) beyond HEATMAP_MAX_RADIUS on either axis (sigma: the fp32 root, widened -- the kernel's own test).
     seen = torch.isfinite(l1) & torch.isfinite(l2) & torch.isfinite(poses_2d[:, :, :2]).all(dim=-1)             # (V, J)
+    seen = seen & (l1 > 0) & (l2 > 0)
+    for lam in (l1, l2):
+        sig = torch.sqrt(torch.where(seen, lam, torch.ones_like(lam))).to(torch.float64)
+        seen = seen & (torch.floor(4.0 * sig + 0.5) <= HEATMAP_MAX_RADIUS)
     px = torch.where(seen, poses_2d[:, :, 0], torch.zeros_like(poses_2d[:, :, 0]))
     py = torch.where(seen, poses_2d[:, :, 1], torch.zeros_like(poses_2d[:, :, 1]))
     l1 = torch.where(seen, l1, torch.ones_like(l1))

@@ -36,6 +36,7 @@ SKS_SMOOTH_BOX, SKS_SMOOTH_TRICUBE = 0, 1
 SKS_SMOOTH_LAUNCH_INTS = 4
 SKS_ALIGN_RIGID, SKS_ALIGN_SIMILARITY, SKS_ALIGN_SCALE = 0, 1, 2
 SKS_PREVIEW_LAUNCH_INTS = 4
+SKS_HEATMAP_MAX_RADIUS = 1 << 18     # a truncation radius beyond it draws no impulse (sks_heatmap_factors, DESIGN.md "Degenerate footprints")
 
 
 SKS_NO_EARLY_FILL = 1 << 30

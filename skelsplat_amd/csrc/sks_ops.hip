@@ -480,11 +480,23 @@ __global__ __launch_bounds__(256) void k_heatmap_factors(int J, int W, int H, co
     sks::gaussian_sigma(rots + 4 * j, scales + 3 * j, scale_modifier, R, sd, Sg);
     sks::ewa_lambdas(Sg, viewmatrix + 16 * v, means + 3 * j, W, H, tan.x[v], tan.y[v], l1, l2);
     // ---- no impulse: an unobserved joint (a NaN mean makes both lambdas NaN) or a non-finite detection (DESIGN.md "Unobserved
-    // joints").  The plane is all zero: row = col = 0, cmin = 0, den = 1e-8 -- what the arithmetic below gives for NaN lambdas
-    // (no loop trip is taken, the normalisation is 1), stated here so that no trip count and no float -> int conversion ever
-    // sees a non-finite number.  (block-uniform: every thread has the same scalars)
+    // joints"), or a degenerate footprint (DESIGN.md "Degenerate footprints"): a lambda that is not positive (lambda2 reaches
+    // mid - sqrt(0.1) ~ -0.016 and passes through exactly +0, where sigma = 0 would divide 0 by 0), or a truncation radius
+    // floor(4 sigma + 0.5) beyond SKS_HEATMAP_MAX_RADIUS on either axis.  The plane is all zero: row = col = 0, cmin = 0,
+    // den = 1e-8 -- what the arithmetic below gives for NaN lambdas (no loop trip is taken, the normalisation is 1), stated here so
+    // that no trip count and no float -> int conversion ever sees a non-finite number.  The decision is made in doubles, before any
+    // loop, and is block-uniform (every thread has the same scalars).
+    // It bounds the work of impulse_response per thread, with R = SKS_HEATMAP_MAX_RADIUS and an axis of n samples: the
+    // normalisation takes at most R / 256 = 1024 trips of one exp, and the response loop at most
+    //   ceil(n / 256) * (3 + 4 * floor((R + n - 1) / 2n))  <=  4 * ceil(n / 256) * (R / 2n + 1) + 3 ceil(n / 256)
+    // exp: 2^19 + 4 (+ 3) at n = 1, about 2^11 at n >= 256.
     const float det_x = poses_2d[2 * vj], det_y = poses_2d[2 * vj + 1];
-    if (!(isfinite(l1) && isfinite(l2) && isfinite(det_x) && isfinite(det_y))) {
+    const float sigma1 = sqrtf(l1), sigma2 = sqrtf(l2);     // (NaN for a negative lambda: never used then)
+    bool draw = isfinite(l1) && isfinite(l2) && isfinite(det_x) && isfinite(det_y) && l1 > 0.0f && l2 > 0.0f;
+    if (draw)
+        draw = floor(4.0 * (double)sigma1 + 0.5) <= (double)SKS_HEATMAP_MAX_RADIUS &&
+               floor(4.0 * (double)sigma2 + 0.5) <= (double)SKS_HEATMAP_MAX_RADIUS;
+    if (!draw) {
         for (int i = threadIdx.x; i < H; i += 256) row[(size_t)vj * Hs + i] = 0.0f;
         for (int i = threadIdx.x; i < W; i += 256) col[(size_t)vj * Ws + i] = 0.0f;
         if (threadIdx.x == 0) { cmin[vj] = 0.0f; den[vj] = 1e-8f; }
@@ -493,8 +505,8 @@ __global__ __launch_bounds__(256) void k_heatmap_factors(int J, int W, int H, co
     // ---- responses: sigma1 filters rows (axis 0), sigma2 columns; the impulse sits at the truncated 2D detection ----
     const int xs = min(max((int)det_x, 0), W - 1), ys = min(max((int)det_y, 0), H - 1);
     float rmin, rmax, kmin, kmax;
-    impulse_response(H, ys, sqrtf(l1), 255.0f, row + (size_t)vj * Hs, s_red, rmin, rmax);
-    impulse_response(W, xs, sqrtf(l2), 1.0f, col + (size_t)vj * Ws, s_red, kmin, kmax);
+    impulse_response(H, ys, sigma1, 255.0f, row + (size_t)vj * Hs, s_red, rmin, rmax);
+    impulse_response(W, xs, sigma2, 1.0f, col + (size_t)vj * Ws, s_red, kmin, kmax);
     rmin = block_minmax(rmin, false, s_redf);
     rmax = block_minmax(rmax, true, s_redf);
     kmin = block_minmax(kmin, false, s_redf);

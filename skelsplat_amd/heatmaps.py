@@ -37,7 +37,12 @@ def heatmap_factors(means, scaling, rotation_raw, poses_2d, cameras, scaling_mod
     ever written); only then may the cameras differ in size (rows / columns keep the largest view's strides).
     `drop_mask` (V,J) bool: planes without an impulse (see generate_heatmaps).
     A joint whose mean holds a NaN (an unobserved joint, DESIGN.md "Unobserved joints") and a non-finite detection draw no
-    impulse either: row = col = 0, cmin = 0, den = 1e-8, an all-zero plane (oracle/heatmaps_ref.py defines the same)."""
+    impulse either: row = col = 0, cmin = 0, den = 1e-8, an all-zero plane (oracle/heatmaps_ref.py defines the same).
+    The same for a degenerate footprint (DESIGN.md "Degenerate footprints"): a projected variance that is not positive (lambda2
+    goes down to about -0.016, through exactly 0, for a footprint below 0.032 px^2 -- a tiny, distant or infinitely far
+    Gaussian), or a truncation radius floor(4 sigma + 0.5) beyond _lib.SKS_HEATMAP_MAX_RADIUS = 2^18 on either axis (a joint
+    almost in a camera's plane; it also bounds the launch).  uncertainty.view_footprints reports the variances the rule is
+    applied to."""
     from . import _lib
     from ._base import ViewBatch, _f32c
     dev = means.device
@@ -109,7 +114,9 @@ def generate_heatmaps(means, scaling, rotation_raw, poses_2d, cameras, scaling_m
     {sum gt^2, count gt > 0} (rasterizer.GtStats.totals) while the planes are written, instead of a separate pass.
     `dropout=True` draws the reference's dropped (camera, joint) planes (draw_dropout); `drop_mask` (V,J) bool gives them
     explicitly.  A dropped plane has no impulse: it is all zero before and after normalize_heatmaps (0 / 1e-8), which the
-    separable form states as row = 0, cmin = 0, den = 1.  `frames`: see heatmap_factors."""
+    separable form states as row = 0, cmin = 0, den = 1.  A plane heatmap_factors finds degenerate (an unobserved joint, a
+    non-finite detection, a variance that is not positive, a truncation radius beyond 2^18) is all zero too: planes and totals
+    are, bit for bit, those of the call with `drop_mask` set there.  `frames`: see heatmap_factors."""
     from . import _lib
     if dropout and drop_mask is None:
         drop_mask = draw_dropout(len(cameras), means.shape[-2])
