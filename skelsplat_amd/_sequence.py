@@ -1,8 +1,11 @@
-"""One `optimize_sequence` call of a FrameBatchLoop / FramePipeline as a record (SequenceRun), and the checks of the per-sequence
-settings.  Imports nothing from loop.py, which imports from here."""
+"""What the loops share around a scene's start: where its initial joints come from (InitialJoints), the switches that decide it and
+what a sequence keeps (JointSwitches, SequenceSwitches) with their checks, and one `optimize_sequence` call of a FrameBatchLoop /
+FramePipeline as a record (SequenceRun).  Imports nothing from loop.py, which imports from here."""
 import numpy as np
 
 import torch
+
+from . import initial_guess, reprojection, triangulation
 
 
 def _sequence_inputs(points, poses_2d):
@@ -20,8 +23,7 @@ def _rejection(reject_px, min_inliers):
     """set_outlier_rejection's arguments -> None (off) or the checked (reject_px, min_inliers)."""
     if reject_px is None:
         return None
-    from .triangulation import _checked_rejection
-    return _checked_rejection(reject_px, min_inliers)
+    return triangulation._checked_rejection(reject_px, min_inliers)
 
 
 def _checked_reject(reject, points, poses_3d, who):
@@ -42,8 +44,7 @@ def _refinement(max_iters, huber_px):
     """set_refinement's arguments -> None (off) or the checked (huber_px, max_iters)."""
     if max_iters is None:
         return None
-    from .reprojection import _checked_refinement
-    return _checked_refinement(huber_px, max_iters)
+    return reprojection._checked_refinement(huber_px, max_iters)
 
 
 def _checked_refine(refine, points, poses_3d, who):
@@ -60,12 +61,85 @@ def _checked_refine(refine, points, poses_3d, who):
     return refine
 
 
+class InitialJoints:
+    """Where the initial joints of a loop's next scene(s) come from: `check` refuses or returns a plan, nothing written yet;
+    `write` then does the plan's launches.  Explicit `points` are taken as they are.  `points=None`: the joints are the DLT
+    triangulation of `poses_2d` (triangulation.triangulate_sequence) -- behind outlier rejection and in front of the refinement
+    (reprojection.refine_triangulation) where the loop has them switched on --, or, with `poses_3d`, the
+    reprojection-error-weighted mean of the views' 3D predictions (initial_guess.fuse_predictions)."""
+
+    @classmethod
+    def check(cls, who, points, poses_2d, poses_3d, shape, reject, refine, proj, device):
+        """`who`: the caller, for the refusal texts.  `shape` = (F, V, J): what the inputs must be -- `points` (F,J,3), `poses_2d`
+        (F,V,J,>=2), `poses_3d` (F,V,J,3); F = None is the one-frame form, the same without the frame axis.  `reject`, `refine`: the
+        loop's set_outlier_rejection / set_refinement settings; `proj`: its projection matrices, None for cameras without
+        K / R / T.  The detections are only looked at when they decide the joints (`points=None`).  The plan holds `points`,
+        `p2d`, `p3d` as tensors with the frame axis (F = 1 for the one-frame form), None for what does not enter."""
+        F, V, J = shape
+        one, ax = F is None, "" if F is None else "F,"
+        lead = () if one else (F,)
+        self = cls()
+        self.one, self.proj, self.points, self.p2d, self.p3d = one, proj, None, None, None
+        self.reject, self.refine = _checked_reject(reject, points, poses_3d, who), _checked_refine(refine, points, poses_3d, who)
+        if points is not None:
+            if poses_3d is not None:
+                raise ValueError(f"{who}: poses_3d are fused into the initial joints when points is None; give one of the two")
+            pts = points if torch.is_tensor(points) else torch.as_tensor(np.asarray(points))
+            if tuple(pts.shape) != lead + (J, 3):
+                raise ValueError(f"{who}: points must be ({ax}P,3) = {lead + (J, 3)}, got {tuple(pts.shape)}")
+            self.points = pts[None] if one else pts
+            return self
+        if poses_2d is None:
+            raise ValueError(f"{who}(points=None) triangulates the initial joints from poses_2d: give poses_2d "
+                             "(ready heatmaps do not carry the detections)")
+        if proj is None:
+            raise ValueError(f"{who}(points=None): the cameras carry no K / R / T to build projection matrices from")
+        p2d = torch.as_tensor(poses_2d, device=device)
+        if p2d.dim() != len(lead) + 3 or tuple(p2d.shape[:-1]) != lead + (V, J) or p2d.shape[-1] < 2:
+            raise ValueError(f"{who}: poses_2d must be ({ax}V,J,2) = {lead + (V, J, 2)}, got {tuple(p2d.shape)}")
+        self.p2d = p2d[None] if one else p2d
+        if poses_3d is not None:
+            p3d = torch.as_tensor(poses_3d, device=device)
+            if tuple(p3d.shape) != lead + (V, J, 3):
+                raise ValueError(f"{who}: poses_3d must be ({ax}V,J,3) = {lead + (V, J, 3)}, got {tuple(p3d.shape)}")
+            self.p3d = p3d[None] if one else p3d
+        return self
+
+    @property
+    def estimated(self):
+        """Do the detections decide the joints (`points=None`)?"""
+        return self.points is None
+
+    def write(self, keep, out, consensus=None):
+        """The joints into `out` (F,J,3) float32, in place, on the current stream; returns `out`.  `keep`: None or (F,V,J) bool, the
+        detections that enter (`valid`).  `consensus`: with rejection on, the (inliers (F,V,J) bool, n_consensus (F,J) int32)
+        buffers its launch fills, and the refinement then minimises over those inliers instead of `keep`.  The one-frame form takes
+        all of them without the frame axis."""
+        given = out
+        if self.one:
+            lift = lambda t: None if t is None else t[None]
+            keep, out, consensus = lift(keep), out[None], None if consensus is None else tuple(map(lift, consensus))
+        if self.points is not None:
+            out.copy_(self.points.to(device=out.device, dtype=out.dtype))
+        elif self.p3d is not None:
+            initial_guess.fuse_predictions(self.proj, self.p3d, self.p2d, valid=keep, out=out)
+        else:
+            reject_px, min_inliers = self.reject
+            if reject_px is None:
+                consensus = None
+            triangulation.triangulate_sequence(self.proj, self.p2d, valid=keep, out=out, reject_px=reject_px,
+                                               min_inliers=min_inliers, out_inliers=consensus)
+            if self.refine is not None:      # one more launch in the same place, in place on the joints
+                reprojection.refine_triangulation(self.proj, self.p2d, out, valid=keep if consensus is None else consensus[0],
+                                                  huber_px=self.refine[0], max_iters=self.refine[1], out=out)
+        return given
+
+
 def _sequence_reprojection(loop, N):
     """optimize_sequence's `reprojection`: None for a loop whose reprojection report is off (set_reprojection_report)."""
-    if not getattr(loop, "_reproject", False):
+    if not loop._reproject:
         return None
-    from .reprojection import SequenceReprojection
-    return SequenceReprojection(N, loop.V, loop.P, loop.device)
+    return reprojection.SequenceReprojection(N, loop.V, loop.P, loop.device)
 
 
 def _smoothing(loop, half_window, degree, taper, use_covariance, cov_floor, groups):
@@ -85,7 +159,7 @@ def _smoothing(loop, half_window, degree, taper, use_covariance, cov_floor, grou
 def _sequence_smoothing(loop, N, who):
     """optimize_sequence's smoothing settings with `groups` as an (N,) int32 tensor on the loop's device (uploaded on the caller's
     stream); None for a loop whose smoothing is off (set_smoothing)."""
-    s = getattr(loop, "_smooth", None)      # (a loop without the switch: off)
+    s = loop._smooth
     if s is None:
         return None
     if s["use_covariance"] and not loop.keep_gaussians:
@@ -201,6 +275,92 @@ def _debug_frames(loop, frames):
     return chosen
 
 
+class JointSwitches:
+    """The switches of the initial joints (InitialJoints), for MultiViewLoop, FrameBatchLoop and FramePipeline alike: each checks
+    its arguments once and then sets the loops this object drives -- a loop itself, a pipeline's `loops` -- so a refused call
+    changes none of them.  The settings live on the loops, as `_reject` and `_refine`.  Every switch returns the object it
+    was called on."""
+
+    def _driven(self):
+        """The loops this object drives: a loop, itself (FramePipeline returns its `loops`)."""
+        return (self,)
+
+    def _set(self, name, value):
+        for loop in self._driven():
+            setattr(loop, name, value)
+        return self
+
+    def set_outlier_rejection(self, reject_px=None, min_inliers=3):
+        """From now on new_scene / new_scenes / optimize_sequence with `points=None` (and without `poses_3d`) reject outlier
+        detections while they triangulate the initial joints: exhaustive two-view consensus within `reject_px` pixels, at least
+        `min_inliers` (2 .. 64) views for a consensus (triangulation.triangulate_sequence's `reject_px`, `min_inliers`: one more
+        launch in the same place, the kept views still the ones it starts from).  The views each joint was solved from and the
+        winners' counts are then kept on the device, in buffers allocated once: a loop's `inliers` and `n_consensus` per scene
+        or batch, and per sequence `seq_inliers` (N,V,J) bool / `seq_n_consensus` (N,J) int32 of a FrameBatchLoop, `inliers` /
+        `n_consensus` of a pipeline, each batch's rows copied on its own stream (None after a sequence without rejection).  The
+        heat-maps are NOT changed: a rejected detection still draws its plane.  A caller who wants it dropped takes two steps,
+        both on the device: `pts, inl, _ = triangulate_sequence(proj, p2d, reject_px=.., return_inliers=True)`, then
+        `new_scenes(pts, p2d, drop_masks=~inl)`.  While it is on, explicit points or `poses_3d` are refused; `reject_px=None`
+        switches it off."""
+        return self._set("_reject", _rejection(reject_px, min_inliers))
+
+    def set_refinement(self, max_iters=16, huber_px=None):
+        """From now on new_scene / new_scenes / optimize_sequence with `points=None` (and without `poses_3d`) follow the
+        triangulation of the initial joints by one launch that minimises their reprojection error from there
+        (reprojection.refine_triangulation: at most `max_iters` (1 .. 16) damped Gauss-Newton trips per joint, plain squares or,
+        with `huber_px`, the Huber cost), in place, on the same stream, in front of the heat-map factors that read the joints.
+        It minimises over the kept views (`valid = ~drop_masks`), or, with outlier rejection on, over the consensus' `inliers`.
+        While it is on, explicit points or `poses_3d` are refused; `max_iters=None` switches it off."""
+        return self._set("_refine", _refinement(max_iters, huber_px))
+
+
+class SequenceSwitches(JointSwitches):
+    """JointSwitches plus what an `optimize_sequence` of a FrameBatchLoop or a FramePipeline keeps: the settings live on the loops
+    as `_reproject`, `_smooth` and `_debug_frames`, the results arrive on the object that ran the sequence (SequenceRun.publish),
+    a pipeline's batches each on their own stream."""
+
+    def set_reprojection_report(self, on=True):
+        """From now on every `optimize_sequence` measures the reprojection error of each batch's initial and final joints against
+        the batch's detections (reprojection.reproject: one launch each, on the batch's own stream, nothing is read back) into
+        `self.reprojection`, a reprojection.SequenceReprojection -- the ground-truth-free figure of the sequence; None after a
+        sequence without it.  The optimiser's steps and captured graphs are untouched.  `False`: off again."""
+        return self._set("_reproject", bool(on))
+
+    def set_smoothing(self, half_window=None, degree=2, taper="tricube", use_covariance=True, cov_floor=0.0, groups=None):
+        """From now on every `optimize_sequence` smooths the joints it returns over time once all batches are taken
+        (smoothing.smooth_sequence: one launch on the caller's stream -- a pipeline's behind its wait for every batch's stream --,
+        nothing is read back) into `self.smoothed`, a smoothing.Smoothed of joints, velocity, cov6 and n_used for all N frames;
+        None after a sequence without it.
+        `half_window` frames on each side (None: off again), `degree` 0 .. 2, `taper` "box" or "tricube".  `use_covariance`: every
+        frame of a joint is weighted by the inverse of its optimised Gaussian's covariance -- one joint_uncertainty launch in
+        front, on loops built with keep_gaussians=True (refused otherwise) --, with `cov_floor` mm^2 added to the diagonals;
+        False: unit weights.  `groups` (N,) integers, host or device: a window never crosses from one recording into the next
+        (checked against the next sequence's length).  A joint that ended NaN ("Unobserved joints") is filled from the frames
+        around it.  The joints `optimize_sequence` returns, `gaussians`, `report` and every other output are untouched, as are the
+        optimiser's steps and captured graphs.  What the covariance weights gain on real sequences depends on how well the
+        optimised covariances are calibrated (uncertainty.calibration) and has not been measured."""
+        return self._set("_smooth", _smoothing(self._driven()[0], half_window, degree, taper, use_covariance, cov_floor, groups))
+
+    def set_debug_images(self, frames):
+        """The reference's debug pictures (configs/*.yaml `debug.save_images`, train.py:113-114, 143-144, 236-237) for the frames
+        with these sequence indices, from now on: every `optimize_sequence` fills `self.images` (a preview.SequenceImages) with
+        each chosen frame's heat-map picture and the picture of its render before the first and after the last iteration, all
+        on the device -- the heat-maps and the first render enqueued right behind the batch's new_scenes, the last render where
+        the joints are copied, on the batch's own stream; nothing is read back until `images.save(dir)`.  The pictures stay
+        outside the captured graphs and a group's launch sequence is the same with and without them.  With them on, a batch that
+        holds a chosen frame enqueues one heat-map picture of all its views and two dense forwards per chosen frame (a debug
+        path: preview.SequenceImages says what that is); other batches enqueue nothing more.  `None` switches them off: nothing
+        is allocated or enqueued and `images` is None after the next sequence."""
+        return self._set("_debug_frames", _debug_frames(self._driven()[0], frames))
+
+    def set_ground_truth(self, gt):
+        """The ground truth of the NEXT batch or sequence (loops with `report_steps`): (F,P,3) for `new_scenes`, (N,P,3) for
+        `optimize_sequence`, float32 on the loops' device.  The next of those calls on this object takes it -- the errors it
+        reports are against it -- and forgets it; None withdraws one that has not been taken."""
+        self._gt_next = _accept_gt(self._driven()[0], gt)
+        return self
+
+
 class SequenceRun:
     """One optimize_sequence call: N frames through batches of F.  The constructor checks the arguments against `loop`'s settings
     (a FrameBatchLoop; a pipeline gives its first) and allocates what the sequence fills, on the caller's stream; the drivers then
@@ -218,7 +378,7 @@ class SequenceRun:
         self.pts, self.p2d, self.N = _sequence_inputs(points, poses_2d)
         self.p3d = _sequence_predictions(points, poses_3d, self.N)
         _checked_reject(loop._reject, points, poses_3d, who)
-        _checked_refine(getattr(loop, "_refine", None), points, poses_3d, who)      # (a loop without the switch: off)
+        _checked_refine(loop._refine, points, poses_3d, who)
         self.ids = _sequence_rig_ids(loop._sel, rig_ids, self.N)    # (uploaded on the caller's stream)
         self.inliers, self.n_consensus = _sequence_consensus(loop, loop._reject, self.N) or (None, None)
         self.gt = _checked_gt(loop, gt_next, self.N, who)
@@ -230,6 +390,13 @@ class SequenceRun:
         self.images = _sequence_images(loop, self.N)
         self.reprojection = _sequence_reprojection(loop, self.N)
         self.smoothing = _sequence_smoothing(loop, self.N, who)
+
+    def publish(self, owner, consensus=("inliers", "n_consensus")):
+        """The results this sequence fills, onto the object that runs it, under the names optimize_sequence documents; the
+        consensus pair under the two names given (a FrameBatchLoop keeps `inliers` / `n_consensus` for its batch)."""
+        for name, value in zip(consensus, (self.inliers, self.n_consensus)):
+            setattr(owner, name, value)
+        owner.report, owner.gaussians, owner.images, owner.reprojection = self.report, self.gaussians, self.images, self.reprojection
 
     def smoothed(self):
         """Behind the last take(), on the CALLER's stream once it waits for every batch: None with the smoothing off, else

@@ -8,7 +8,7 @@ expression."""
 import numpy as np
 import torch
 
-from .triangulation import projection_matrices
+from . import _pose_args as _pa
 
 _NORM_DTYPES = {torch.float64: torch.float64, torch.float32: torch.float32, np.float64: torch.float64, np.float32: torch.float32,
                 np.dtype("float64"): torch.float64, np.dtype("float32"): torch.float32}
@@ -59,70 +59,39 @@ def fuse_predictions(proj_or_cameras, poses_3d, poses_2d, valid=None, norm_dtype
     detections and matrices given on the host are uploaded first).  A frame's result does not depend on N, on its place in
     the batch or on the stream.  Predictions on the host (arrays or CPU tensors): the same formula as one float64
     expression over all frames; arrays in, arrays out."""
-    as_array = not torch.is_tensor(poses_3d)
-    X = torch.as_tensor(np.asarray(poses_3d)) if as_array else poses_3d
+    X, as_array = _pa.as_tensor(poses_3d)
     dev = X.device
-    x = (poses_2d if torch.is_tensor(poses_2d) else torch.as_tensor(np.asarray(poses_2d))).to(dev)
+    x = _pa.as_tensor(poses_2d)[0].to(dev)
     try:
         norm = _NORM_DTYPES[norm_dtype]
     except (KeyError, TypeError):
         raise ValueError(f"norm_dtype must be torch.float64 or torch.float32, got {norm_dtype!r}") from None
-    if torch.is_tensor(proj_or_cameras):
-        P = proj_or_cameras.to(device=dev, dtype=torch.float64)
-    elif isinstance(proj_or_cameras, np.ndarray):
-        P = torch.as_tensor(proj_or_cameras, dtype=torch.float64).to(dev)
-    else:
-        seq = list(proj_or_cameras)
-        P = torch.as_tensor(np.asarray(seq) if seq and not hasattr(seq[0], "K") else projection_matrices(seq),
-                            dtype=torch.float64).to(dev)
+    P = _pa.projections(proj_or_cameras, dev)
     single = X.dim() == 3
     if single:
         X = X[None]
         x = x[None] if x.dim() == 3 else x
-        valid = None if valid is None else torch.as_tensor(valid)[None]
     if X.dim() != 4 or X.shape[-1] != 3:
         raise ValueError(f"poses_3d must be (N,V,J,3) or (V,J,3), got {tuple(poses_3d.shape)}")
     N, V, J = X.shape[:3]
     if x.dim() != 4 or tuple(x.shape[:3]) != (N, V, J) or x.shape[-1] < 2:
         raise ValueError(f"poses_2d must be (N,V,J,>=2) = {(N, V, J, 2)} like poses_3d, got {tuple(poses_2d.shape)}")
-    if N < 1 or J < 1:
-        raise ValueError(f"poses_3d {tuple(X.shape)}: at least one frame and one joint")
-    if not 1 <= V <= 64:
-        raise ValueError(f"{V} views: a joint takes 1 .. 64 (SKS_MAX_VIEWS)")
     if not (X.is_floating_point() and x.is_floating_point()):
         raise ValueError("poses_3d and poses_2d must be floating point")
-    if tuple(P.shape) not in ((V, 3, 4), (N, V, 3, 4)):
-        raise ValueError(f"projection matrices must be (V,3,4) = {(V, 3, 4)} or (N,V,3,4) = {(N, V, 3, 4)}, "
-                         f"got {tuple(P.shape)}")
-    if valid is not None:
-        valid = torch.as_tensor(valid).to(device=dev, dtype=torch.bool)
-        if tuple(valid.shape) != (N, V, J):
-            raise ValueError(f"valid must be (N,V,J) = {(N, V, J)}, got {tuple(valid.shape)}")
-    shape = (N, J, 3)
-    if out is not None:
-        want = shape[1:] if single and torch.is_tensor(out) and out.dim() == 2 else shape
-        if (not torch.is_tensor(out) or tuple(out.shape) != want or out.dtype not in (torch.float32, torch.float64)
-                or out.device != dev or not out.is_contiguous()):
-            raise ValueError(f"`out` must be a contiguous float32 or float64 tensor of shape {want} on {dev}")
-        res = out.view(shape)
+    _pa.check_shapes(P, N, V, J)
+    valid = _pa.check_valid(valid, single, dev, (N, V, J))
+    if out is None:
+        res = torch.empty((N, J, 3), dtype=torch.float32, device=dev)
     else:
-        res = torch.empty(shape, dtype=torch.float32, device=dev)
+        res = _pa.check_out(out, (N, J, 3), (torch.float32, torch.float64), dev, single)
     if dev.type == "cuda":
         from . import _lib
-        Xd = (X if X.dtype == torch.float64 else X.to(torch.float32)).contiguous()
-        xd = x[..., :2]
-        xd = (xd if xd.dtype == torch.float64 else xd.to(torch.float32)).contiguous()
-        P = P.contiguous()
-        vd = None if valid is None else valid.contiguous().view(torch.uint8)
+        Xd, xd, P = _pa.as_real(X), _pa.as_real(x[..., :2]), P.contiguous()
         errors = torch.empty((N, V, J), dtype=torch.float64, device=dev) if return_errors else None
         n_used = torch.empty((N, J), dtype=torch.int32, device=dev) if return_n_used else None
-        X64, x64, r64 = Xd.dtype == torch.float64, xd.dtype == torch.float64, res.dtype == torch.float64
         with torch.cuda.device(dev):
-            rc = _lib.load().sks_fuse_predictions(N, V, J, P.data_ptr(), V * 12 if P.dim() == 4 else 0,
-                                                  None if X64 else Xd.data_ptr(), Xd.data_ptr() if X64 else None,
-                                                  None if x64 else xd.data_ptr(), xd.data_ptr() if x64 else None,
-                                                  None if vd is None else vd.data_ptr(), int(norm == torch.float32),
-                                                  None if r64 else res.data_ptr(), res.data_ptr() if r64 else None,
+            rc = _lib.load().sks_fuse_predictions(N, V, J, P.data_ptr(), _pa.rig_stride(P, V), *_pa.pointers(Xd), *_pa.pointers(xd),
+                                                  _pa.byte_pointer(valid), int(norm == torch.float32), *_pa.pointers(res),
                                                   None if errors is None else errors.data_ptr(),
                                                   None if n_used is None else n_used.data_ptr(),
                                                   torch.cuda.current_stream(dev).cuda_stream)
@@ -130,14 +99,4 @@ def fuse_predictions(proj_or_cameras, poses_3d, poses_2d, valid=None, norm_dtype
     else:
         fused, errors, n_used = _fuse_cpu(P, X.to(torch.float64), x[..., :2].to(torch.float64), valid, norm)
         res.copy_(fused)
-    ret = out if out is not None else (res[0] if single else res)
-    if as_array and out is None:
-        ret = ret.numpy()
-    extras = []
-    if return_errors:
-        errors = errors[0] if single else errors
-        extras.append(errors.numpy() if as_array else errors)
-    if return_n_used:
-        n_used = n_used[0] if single else n_used
-        extras.append(n_used.numpy() if as_array else n_used)
-    return (ret, *extras) if extras else ret
+    return _pa.results(res, out, single, as_array, [t for t, asked in ((errors, return_errors), (n_used, return_n_used)) if asked])

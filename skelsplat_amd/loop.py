@@ -14,6 +14,7 @@ on every rank, so the mean uses the reference's summation order and every rank t
 """
 import ctypes
 import os
+from typing import Any, NamedTuple
 
 import numpy as np
 
@@ -22,9 +23,9 @@ import torch.distributed as dist
 
 from . import rasterizer as R
 from ._group import next_group
-from ._sequence import (SequenceRun, _accept_gt, _checked_gt, _checked_refine, _checked_reject, _debug_frames, _refinement, _rejection,
-                        _smoothing)
-from ._sequence import _sequence_predictions, _sequence_rig_ids     # noqa: F401  (callers and tests reach them as loop.<name>)
+from ._sequence import InitialJoints, JointSwitches, SequenceRun, SequenceSwitches, _checked_gt
+# (callers and tests reach these as loop.<name>)
+from ._sequence import _checked_reject, _debug_frames, _rejection, _sequence_predictions, _sequence_rig_ids     # noqa: F401
 from .scene import DATASETS
 
 
@@ -124,31 +125,23 @@ def _optimiser_arrays(cfg, dataset, lambda_consistency):
     return sched, lrs, adam, (ctypes.c_int * 8)(*limbs) if lambda_consistency != 0.0 else None
 
 
-class _GroupLoop:
+class SizeGroup(NamedTuple):
+    """One entry of a loop's `size_groups`: the local view slots of one image size, each one batched launch sequence of the dense
+    path (and of the per-frame heat-map generation)."""
+    slots: list     # local slots (FrameBatchLoop: frame-major)
+    views: Any      # rasterizer.ViewBatch of them (None under a view_grad_fn)
+    gt: Any         # their (Vg,C,H,W) pseudo-GT planes
+    stats: Any      # rasterizer.GtStats of the planes, None where the sparse path is off
+    idx: Any        # the slots as an index tensor on the device
+
+
+class _GroupLoop(JointSwitches):
     """What MultiViewLoop and FrameBatchLoop share: run()'s groups, captured several to a hipGraph (`_enqueue`).  It calls the loop's
     own `step_group()`, `_device_group(group_mask, last_view, n_iters)` and `_all_stopped()`, and `_after_replay()` after every replay.
     Each loop also has `_optimiser_block(group_mask, last_view, n_iters)`: _lib.OPTIMISER_PARAMS of one group, tensors as tensors."""
 
     def _after_replay(self):
         pass
-
-    def set_outlier_rejection(self, reject_px=None, min_inliers=3):
-        """From now on new_scene / new_scenes / optimize_sequence with `points=None` (and without `poses_3d`) reject outlier
-        detections while they triangulate the initial joints: exhaustive two-view consensus within `reject_px` pixels, at least
-        `min_inliers` (2 .. 64) views for a consensus (triangulation.triangulate_sequence's `reject_px`, `min_inliers`).  While
-        it is on, explicit points or `poses_3d` are refused; `reject_px=None` switches it off.  Returns the loop."""
-        self._reject = _rejection(reject_px, min_inliers)
-        return self
-
-    def set_refinement(self, max_iters=16, huber_px=None):
-        """From now on new_scene / new_scenes / optimize_sequence with `points=None` (and without `poses_3d`) follow the
-        triangulation of the initial joints by one launch that minimises their reprojection error from there
-        (reprojection.refine_triangulation: at most `max_iters` (1 .. 16) damped Gauss-Newton trips per joint, plain squares or,
-        with `huber_px`, the Huber cost), in place, in front of the heat-map factors that read the joints.  With outlier
-        rejection on, it minimises over the consensus' `inliers`.  While it is on, explicit points or `poses_3d` are refused;
-        `max_iters=None` switches it off.  Returns the loop."""
-        self._refine = _refinement(max_iters, huber_px)
-        return self
 
     def _enqueue(self, iterations, groups_per_graph, graphs=True):
         """run() without its final synchronisation (FramePipeline drives several loops with it).  With use_graph, while every group
@@ -314,26 +307,23 @@ class MultiViewLoop(_GroupLoop):
                 self.hset.planes[k].copy_(heatmaps[v])
         else:
             self.hset = None
-        # size groups: local slots per image size, each one batched launch sequence of the DENSE path (and of the
-        # per-frame heat-map generation); entries: [slots, ViewBatch, gt (Vg,C,H,W), GtStats or None, slot index tensor]
-        self.size_groups = []
+        self.size_groups = []       # SizeGroup per image size
         if self.hset is not None:
             for key, slots in self.hset.groups.items():
                 vb = (R.ViewBatch.from_cameras([cameras[self.local_ids[k]] for k in slots]) if self.view_grad_fn is None else None)
                 idx = torch.tensor(slots, dtype=torch.long, device=self.device)
-                self.size_groups.append([slots, vb, self.hset.group(key), None, idx])
+                self.size_groups.append(SizeGroup(slots, vb, self.hset.group(key), None, idx))
         single = len(self.size_groups) == 1
-        self.gt = self.size_groups[0][2] if single else None   # single-size convenience (tests, view_grad_fn)
-        self.views = self.size_groups[0][1] if single else None
+        self.gt = self.size_groups[0].gt if single else None   # single-size convenience (tests, view_grad_fn)
+        self.views = self.size_groups[0].views if single else None
 
     def _init_sparse_stats(self):
         """Sparse path: the heat-maps' statistics per size group, and ALL local views in one batch (sizes may differ)."""
         self.views_all = self.stats_all = None
         if self.sparse and self.local_ids:
-            for grp in self.size_groups:
-                grp[3] = R.gt_tile_stats(grp[2])
+            self.size_groups = [grp._replace(stats=R.gt_tile_stats(grp.gt)) for grp in self.size_groups]
             if len(self.size_groups) == 1:
-                self.views_all, self.stats_all = self.size_groups[0][1], self.size_groups[0][3]
+                self.views_all, self.stats_all = self.size_groups[0].views, self.size_groups[0].stats
             else:
                 self.views_all = R.ViewBatch.from_cameras([self.cameras[v] for v in self.local_ids], allow_mixed=True)
                 self.stats_all = R.GtStats.of_set(self.hset)
@@ -468,35 +458,20 @@ class MultiViewLoop(_GroupLoop):
         step counters, V-slot buffer, heat-maps and their tile statistics keep their storage -- so the hipGraphs
         captured for the previous frame are replayed as they are.  Give either `poses_2d` (V,J,2) (the heat-maps are
         generated from the re-initialised Gaussians like general_utils.py:175-304) or ready `heatmaps`.
-        `points=None`: the initial joints are the DLT triangulation of `poses_2d` (triangulation.triangulate_sequence, on
-        the device, on the current stream; with `dropout` the dropped planes' detections stay out of it).  It needs all V
-        views' detections, so a view-sharded loop (world > 1) refuses it; a joint kept in fewer than two views has no
-        triangulation and starts as NaN: it is then UNOBSERVED for the whole loop, on every path of this class (DESIGN.md
-        "Unobserved joints").  The same holds for a NaN row of explicit `points`.
-        `poses_3d` (V,J,3), with `points=None`: the initial joints are instead the reprojection-error-weighted mean of the
-        views' 3D predictions (initial_guess.fuse_predictions, the reference's "metrabs" guess), under the same conditions; a
-        joint whose views are all dropped starts as NaN.  Together with explicit `points` it is refused.
-        After `set_outlier_rejection(reject_px, min_inliers)` the triangulation first rejects outlier detections by two-view
-        consensus (triangulate_sequence's `reject_px`); the views each joint was solved from are then in `self.inliers` (V,J)
-        bool, the consensus counts in `self.n_consensus` (J,).  It acts with `points=None` and without `poses_3d` only:
-        beside either the call is refused.  The heat-maps are not changed: a rejected detection still draws its plane."""
+        `points=None`, optionally with `poses_3d` (V,J,3): the initial joints are estimated from the detections as
+        FrameBatchLoop.new_scenes says, for this one frame, on the device, on the current stream, bit for bit what that frame gets
+        in a batch; with `dropout` the dropped planes' detections stay out of it.  It needs all V views' detections, so a
+        view-sharded loop (world > 1) refuses it; a joint that comes out NaN is then UNOBSERVED for the whole loop, on every
+        path of this class (DESIGN.md "Unobserved joints").  The same holds for a NaN row of explicit `points`.
+        After `set_outlier_rejection` the views each joint was solved from are in `self.inliers` (V,J) bool, the consensus
+        counts in `self.n_consensus` (J,) int32; `set_refinement` acts here as it does there."""
         from .heatmaps import generate_heatmaps
         gm = self.gm
-        reject_px, min_inliers = _checked_reject(self._reject, points, poses_3d, "new_scene")
-        refine = _checked_refine(self._refine, points, poses_3d, "new_scene")
-        if points is not None:
-            if poses_3d is not None:
-                raise ValueError("new_scene: poses_3d are fused into the initial joints when points is None; give one of the two")
-            gm.reset_from_points(points)
-        else:
-            if poses_2d is None:
-                raise ValueError("new_scene(points=None) triangulates the initial joints from poses_2d: give poses_2d "
-                                 "(ready heatmaps do not carry the detections)")
-            if self.world > 1:
-                raise ValueError("new_scene(points=None): a view-sharded loop (world > 1) sees only its own views' "
-                                 "detections; triangulate on one rank (triangulation.triangulate_sequence) and pass points")
-            if self._proj is None:
-                raise ValueError("new_scene(points=None): the cameras carry no K / R / T to build projection matrices from")
+        plan = InitialJoints.check("new_scene", points, poses_2d, poses_3d, (None, self.V, self.P), self._reject, self._refine,
+                                   self._proj, self.device)
+        if plan.estimated and self.world > 1:
+            raise ValueError("new_scene(points=None): a view-sharded loop (world > 1) sees only its own views' "
+                             "detections; triangulate on one rank (triangulation.triangulate_sequence) and pass points")
         with torch.no_grad():
             self.accumulated_grads.zero_()
             if self.device_tail:
@@ -516,32 +491,15 @@ class MultiViewLoop(_GroupLoop):
                     dist.broadcast(buf, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0,
                                    group=self.group)
                     drop = buf.to(device="cpu", dtype=torch.bool)
-            if points is None:
-                from .triangulation import triangulate_sequence
-                p2d = torch.as_tensor(poses_2d, device=self.device)
-                if p2d.dim() != 3 or tuple(p2d.shape[:2]) != (self.V, self.P):
-                    raise ValueError(f"poses_2d must be (V,J,2) = {(self.V, self.P, 2)}, got {tuple(p2d.shape)}")
-                if poses_3d is not None:
-                    from .initial_guess import fuse_predictions
-                    p3d = torch.as_tensor(poses_3d, device=self.device)
-                    if tuple(p3d.shape) != (self.V, self.P, 3):
-                        raise ValueError(f"poses_3d must be (V,J,3) = {(self.V, self.P, 3)}, got {tuple(p3d.shape)}")
-                    gm.reset_from_points(fuse_predictions(self._proj, p3d, p2d, valid=None if drop is None else ~drop))
-                else:
-                    if reject_px is not None and self.inliers is None:
-                        self.inliers = torch.zeros((self.V, self.P), dtype=torch.bool, device=self.device)
-                        self.n_consensus = torch.zeros((self.P,), dtype=torch.int32, device=self.device)
-                    keep = None if drop is None else ~drop
-                    pts = triangulate_sequence(
-                        self._proj, p2d, valid=keep, reject_px=reject_px, min_inliers=min_inliers,
-                        out_inliers=None if reject_px is None else (self.inliers[None], self.n_consensus[None]))
-                    if refine is not None:
-                        from .reprojection import refine_triangulation
-                        refine_triangulation(self._proj, p2d, pts, valid=keep if reject_px is None else self.inliers,
-                                             huber_px=refine[0], max_iters=refine[1], out=pts)
-                    gm.reset_from_points(pts)
-            for grp in self.size_groups:
-                slots, vb, gt, stats, idx = grp
+            if not plan.estimated:
+                gm.reset_from_points(plan.points[0])
+            else:
+                if plan.reject[0] is not None and self.inliers is None:
+                    self.inliers = torch.zeros((self.V, self.P), dtype=torch.bool, device=self.device)
+                    self.n_consensus = torch.zeros((self.P,), dtype=torch.int32, device=self.device)
+                pts = torch.empty((self.P, 3), dtype=torch.float32, device=self.device)
+                gm.reset_from_points(plan.write(None if drop is None else ~drop, pts, (self.inliers, self.n_consensus)))
+            for slots, vb, gt, stats, idx in self.size_groups:
                 ids = [self.local_ids[k] for k in slots]
                 if heatmaps is not None:
                     for i, v in enumerate(ids):
@@ -875,7 +833,7 @@ def _frame_criterion(early_stopping):
     return int(w), float(es.repeat_tolerance)
 
 
-class FrameBatchLoop(_GroupLoop):
+class FrameBatchLoop(_GroupLoop, SequenceSwitches):
     """F independent frames, optimised side by side in the sparse fused step -- seen by the SAME cameras (`cameras=`), or each
     by one rig of a bank (`rigs=` a rigs.RigBank; then `new_scenes(..., rig_ids=)` names every frame's rig).
 
@@ -1015,14 +973,13 @@ class FrameBatchLoop(_GroupLoop):
         else:
             # planes of all F x V views (frame-major) in one flat buffer; views of one size adjacent (H36M: two sizes)
             self.hset = R.HeatmapSet(sizes, self.C, dev)
-            # [slots (frame-major), ViewBatch of them, (Vg,C,H,W) planes, GtStats, slot index tensor]
             for key, slots in self.hset.groups.items():
                 vb = views_of(slots)
                 gt = self.hset.group(key)
                 gt.zero_()
-                self.size_groups.append([slots, vb, gt, R.gt_tile_stats(gt), torch.tensor(slots, dtype=torch.long, device=dev)])
+                self.size_groups.append(SizeGroup(slots, vb, gt, R.gt_tile_stats(gt), torch.tensor(slots, dtype=torch.long, device=dev)))
             if len(self.size_groups) == 1:
-                self.views_all, self.stats_all = self.size_groups[0][1], self.size_groups[0][3]
+                self.views_all, self.stats_all = self.size_groups[0].views, self.size_groups[0].stats
             else:
                 self.views_all = views_of(range(F * V), allow_mixed=True)
                 self.stats_all = R.GtStats.of_set(self.hset)
@@ -1061,27 +1018,18 @@ class FrameBatchLoop(_GroupLoop):
         views' 3D predictions (initial_guess.fuse_predictions, the reference's "metrabs" guess), written into `self.xyz` by one
         launch in the same place with the same `valid = ~drop_masks`; a joint whose views are all dropped starts as NaN.
         Together with explicit `points` it is refused.
-        After `set_outlier_rejection(reject_px, min_inliers)`, with `points=None` and without `poses_3d` (refused otherwise): the
-        triangulation first rejects outlier detections by exhaustive two-view consensus (triangulate_sequence's `reject_px`:
-        one more launch in the same place, `valid = ~drop_masks` still the views it starts from).  The views each joint was solved from are
-        then in `self.inliers` (F,V,J) bool and the winners' counts in `self.n_consensus` (F,J) int32, buffers allocated once.
-        The heat-maps are NOT changed: a rejected detection still draws its plane.  A caller who wants it dropped takes two
-        steps, both on the device: `pts, inl, _ = triangulate_sequence(proj, p2d, reject_px=.., return_inliers=True)`, then
-        `new_scenes(pts, p2d, drop_masks=~inl)`.
+        `set_outlier_rejection` and `set_refinement` say what they add to the triangulation, in the same place: the views each joint
+        was solved from are then in `self.inliers` (F,V,J) bool, the winners' counts in `self.n_consensus` (F,J) int32.
         `rig_ids` (F,) ints, host or device (a loop over a rig bank): frame f is seen by rig rig_ids[f] -- one gather launch on
         the current stream fills the batch's camera rows, per-view scalars, projection matrices and schedule rows in place, in
         front of the triangulation and the heat-map factors that read them.  Host ids are validated here; ids in a device
         tensor are bounds-checked by the kernel, which skips a frame whose id is outside the bank (it keeps the cameras its
         slot had) and raises an error word that `check_rigs()` reports.  None: the frames keep the rigs they have.
-        After `set_refinement(max_iters, huber_px)`, with `points=None` and without `poses_3d` (refused otherwise): one more
-        launch in the same place minimises the triangulated joints' reprojection error in place (reprojection.refine_triangulation),
-        over `valid = ~drop_masks`, or over `self.inliers` with rejection on.
         A loop that reports (`report_steps` / `save_iterations`): the ground truth given to `set_ground_truth` since the last batch,
         (F,P,3), is copied in place -- without one the errors of this batch are NaN, losses and snapshots are reported all the
         same --, the traces and snapshots go back to NaN and one report launch behind everything above writes row 0 and the
         snapshots of iteration 0 from the initial joints."""
         from .heatmaps import generate_heatmaps, heatmap_factors, heatmap_planes
-        from .triangulation import triangulate_sequence
         F, V, P = self.F, self.V, self.P
         if self.factored and heatmaps is not None:
             raise ValueError("ready heat-map planes need FrameBatchLoop(..., factored=False)")
@@ -1090,35 +1038,16 @@ class FrameBatchLoop(_GroupLoop):
         if self._reproject and heatmaps is not None:
             raise ValueError("new_scenes: the reprojection report (set_reprojection_report) measures against detections, and ready "
                              "heatmaps carry none -- give poses_2d, or switch it off with set_reprojection_report(False)")
-        reject_px, min_inliers = _checked_reject(self._reject, points, poses_3d, "new_scenes")
-        refine = _checked_refine(self._refine, points, poses_3d, "new_scenes")
         gt_pose, self._gt_next = _checked_gt(self, self._gt_next, F, "new_scenes"), None      # (`gt` below: heat-map planes)
         with torch.no_grad():
             if self._sel is not None:
                 self._sel.check()       # (an id a device tensor of an earlier batch held outside the bank; never waits)
                 if rig_ids is not None:
                     self._sel.select(rig_ids)
-            if points is None:
-                if poses_2d is None:
-                    raise ValueError("new_scenes(points=None) triangulates the initial joints from poses_2d: give poses_2d "
-                                     "(ready heatmaps do not carry the detections)")
-                if self._proj is None:
-                    raise ValueError("new_scenes(points=None): the cameras carry no K / R / T to build projection matrices from")
-                p2d_dlt = torch.as_tensor(poses_2d, device=self.device)
-                if p2d_dlt.dim() != 4 or tuple(p2d_dlt.shape[:3]) != (F, V, P) or p2d_dlt.shape[3] < 2:
-                    raise ValueError(f"poses_2d must be (F,V,J,2) = {(F, V, P, 2)}, got {tuple(p2d_dlt.shape)}")
-                poses_2d = p2d_dlt[..., :2]
-                if poses_3d is not None:
-                    p3d = torch.as_tensor(poses_3d, device=self.device)
-                    if tuple(p3d.shape) != (F, V, P, 3):
-                        raise ValueError(f"poses_3d must be (F,V,J,3) = {(F, V, P, 3)}, got {tuple(p3d.shape)}")
-            else:
-                if poses_3d is not None:
-                    raise ValueError("new_scenes: poses_3d are fused into the initial joints when points is None; give one of "
-                                     "the two")
-                pts = points if torch.is_tensor(points) else torch.as_tensor(np.asarray(points))
-                if tuple(pts.shape) != (F, P, 3):
-                    raise ValueError(f"points must be (F,P,3) = {(F, P, 3)}, got {tuple(pts.shape)}")
+            plan = InitialJoints.check("new_scenes", points, poses_2d, poses_3d, (F, V, P), self._reject, self._refine, self._proj,
+                                       self.device)
+            if plan.estimated:
+                poses_2d = plan.p2d[..., :2]
             if self._es is not None:
                 # a frame still running may yet write its flag from work enqueued before: let it drain first (once every
                 # frame has stopped, nothing writes a flag any more, and the next frames start at once)
@@ -1126,22 +1055,10 @@ class FrameBatchLoop(_GroupLoop):
                     torch.cuda.current_stream(self.device).synchronize()
                 self._es_flags_np[:] = 0
                 self._es_state.zero_()
-            if points is None:
-                keep = None if drop_masks is None else ~torch.as_tensor(drop_masks).to(device=self.device, dtype=torch.bool)
-                keep = None if keep is None else keep.reshape(F, V, P)
-                if poses_3d is not None:
-                    from .initial_guess import fuse_predictions
-                    fuse_predictions(self._proj, p3d, p2d_dlt, valid=keep, out=self.xyz)
-                else:
-                    triangulate_sequence(self._proj, p2d_dlt, valid=keep, out=self.xyz, reject_px=reject_px,
-                                         min_inliers=min_inliers,
-                                         out_inliers=None if reject_px is None else (self.inliers, self.n_consensus))
-                    if refine is not None:      # one more launch in the same place, in place on the joints
-                        from .reprojection import refine_triangulation
-                        refine_triangulation(self._proj, p2d_dlt, self.xyz, valid=keep if reject_px is None else self.inliers,
-                                             huber_px=refine[0], max_iters=refine[1], out=self.xyz)
-            else:
-                self.xyz.copy_(pts.to(device=self.device, dtype=torch.float32))
+            keep = None
+            if plan.estimated and drop_masks is not None:
+                keep = ~torch.as_tensor(drop_masks).to(device=self.device, dtype=torch.bool).reshape(F, V, P)
+            plan.write(keep, self.xyz, (self.inliers, self.n_consensus))
             self.scaling.copy_(self._init[0].expand(F, P, 3))
             self.rotation.copy_(self._init[1].expand(F, P, 4))
             self.opacity.copy_(self._init[2].expand(F, P, 1))
@@ -1181,42 +1098,6 @@ class FrameBatchLoop(_GroupLoop):
         self.iteration = 0
         return self
 
-    def set_reprojection_report(self, on=True):
-        """From now on every `optimize_sequence` measures the reprojection error of each batch's initial and final joints against
-        the batch's detections (reprojection.reproject: one launch each, on the batch's own stream, nothing is read back) into
-        `self.reprojection`, a reprojection.SequenceReprojection -- the ground-truth-free figure of the sequence; None after a
-        sequence without it.  The optimiser's steps and captured graphs are untouched.  Returns the loop."""
-        self._reproject = bool(on)
-        return self
-
-    def set_smoothing(self, half_window=None, degree=2, taper="tricube", use_covariance=True, cov_floor=0.0, groups=None):
-        """From now on every `optimize_sequence` smooths the joints it returns over time once all batches are taken
-        (smoothing.smooth_sequence: one launch on the caller's stream, nothing is read back) into `self.smoothed`, a
-        smoothing.Smoothed of joints, velocity, cov6 and n_used for all N frames; None after a sequence without it.
-        `half_window` frames on each side (None: off again), `degree` 0 .. 2, `taper` "box" or "tricube".  `use_covariance`: every
-        frame of a joint is weighted by the inverse of its optimised Gaussian's covariance -- one joint_uncertainty launch in
-        front, on a loop built with keep_gaussians=True (refused otherwise) --, with `cov_floor` mm^2 added to the diagonals;
-        False: unit weights.  `groups` (N,) integers, host or device: a window never crosses from one recording into the next
-        (checked against the next sequence's length).  A joint that ended NaN ("Unobserved joints") is filled from the frames
-        around it.  The joints `optimize_sequence` returns, `gaussians`, `report` and every other output are untouched, as are the
-        optimiser's steps and captured graphs.  What the covariance weights gain on real sequences depends on how well the
-        optimised covariances are calibrated (uncertainty.calibration) and has not been measured.  Returns the loop."""
-        self._smooth = _smoothing(self, half_window, degree, taper, use_covariance, cov_floor, groups)
-        return self
-
-    def set_debug_images(self, frames):
-        """The reference's debug pictures (configs/*.yaml `debug.save_images`, train.py:113-114, 143-144, 236-237) for the frames
-        with these sequence indices, from now on: every `optimize_sequence` fills `self.images` (a preview.SequenceImages) with
-        each chosen frame's heat-map picture and the picture of its render before the first and after the last iteration, all
-        on the device -- the heat-maps and the first render enqueued right behind the batch's new_scenes, the last render where
-        the joints are copied, on the batch's own stream; nothing is read back until `images.save(dir)`.  The pictures stay
-        outside the captured graphs and a group's launch sequence is the same with and without them.  With them on, a batch that
-        holds a chosen frame enqueues one heat-map picture of all its views and two dense forwards per chosen frame (a debug
-        path: preview.SequenceImages says what that is); other batches enqueue nothing more.  `None` switches them off: nothing
-        is allocated or enqueued and `images` is None after the next sequence.  Returns the loop."""
-        self._debug_frames = _debug_frames(self, frames)
-        return self
-
     def frame_views(self, i):
         """The ViewBatch of frame i's V views for a dense forward of that frame alone (the debug pictures): the loop's cameras,
         which every frame of a batch shares."""
@@ -1231,20 +1112,13 @@ class FrameBatchLoop(_GroupLoop):
         if self.factored:
             return heatmap_preview(self.factors, self.views_all, return_minmax=True)
         if len(self.size_groups) == 1:
-            return channel_sum_u8(self.size_groups[0][2], return_minmax=True)
+            return channel_sum_u8(self.size_groups[0].gt, return_minmax=True)
         va = self.views_all
         out = torch.zeros((va.V, va.H, va.W), dtype=torch.uint8, device=self.device)
         mm = torch.empty((va.V, 2), dtype=torch.float32, device=self.device)
         for slots, vb, gt, stats, idx in self.size_groups:
             out[idx, :vb.H, :vb.W], mm[idx] = channel_sum_u8(gt, return_minmax=True)
         return out, mm
-
-    def set_ground_truth(self, gt):
-        """The ground truth of the NEXT batch or sequence (a loop with `report_steps`): (F,P,3) for `new_scenes`, (N,P,3) for
-        `optimize_sequence`, float32 on the loop's device.  The next of those calls takes it -- the errors it reports are against
-        it -- and forgets it; None withdraws one that has not been taken.  Returns the loop."""
-        self._gt_next = _accept_gt(self, gt)
-        return self
 
     def _optimiser_block(self, group_mask, last_view, n_iters):
         return (self.accumulated_grads, group_mask, last_view, self.xyz, self.scaling, self.rotation, self.opacity, self.exp_avg,
@@ -1356,27 +1230,17 @@ class FrameBatchLoop(_GroupLoop):
         `rig_ids` (N,) ints, host or device (a loop over a rig bank): the rig of every frame, see new_scenes.
         `poses_3d` (N,V,J,3), with `points=None`: every batch's initial joints are fused from the views' 3D predictions
         instead (new_scenes); a device tensor is never copied to the host.
-        After `set_outlier_rejection(reject_px, min_inliers)`, with `points=None` and without `poses_3d` (refused otherwise): every
-        batch's triangulation rejects outlier detections first (new_scenes); afterwards `self.seq_inliers` (N,V,J) bool and `self.seq_n_consensus` (N,J) int32 hold
-        every frame's views and counts on the device (None after a sequence without rejection).
+        What the switches add -- set_outlier_rejection (`self.seq_inliers`, `self.seq_n_consensus`), set_refinement,
+        set_reprojection_report (`self.reprojection`), set_smoothing (`self.smoothed`), set_debug_images (`self.images`) -- is said
+        there; each result is None after a sequence without its switch.
         A loop that reports: the return value is the same, and `self.report` (a report.SequenceReport) holds the loop's traces,
         final errors, snapshots and step counts for all N frames -- the errors against the (N,P,3) ground truth given to
         `set_ground_truth` before this call, NaN without one.
         A loop built with keep_gaussians=True: afterwards `self.gaussians` (an uncertainty.SequenceGaussians) holds every frame's
         xyz -- the tensor returned --, scaling, rotation and opacity as the frame ended, what scene.save_h36m writes
-        (io.save_ply_arrays) and uncertainty.joint_uncertainty reads; None otherwise.
-        After `set_debug_images(frames)`: `self.images` (a preview.SequenceImages) holds the chosen frames' debug pictures; None
-        otherwise.
-        After `set_refinement(max_iters, huber_px)`, with `points=None` and without `poses_3d` (refused otherwise): every batch's
-        triangulated joints are refined in place by one more launch (new_scenes).  After `set_reprojection_report()`:
-        `self.reprojection` (a reprojection.SequenceReprojection) holds the reprojection errors of every frame's initial and final
-        joints against its detections; None otherwise.
-        After `set_smoothing(half_window, ...)`: `self.smoothed` (a smoothing.Smoothed) holds the returned joints smoothed over
-        time, one launch behind the last batch; None otherwise."""
+        (io.save_ply_arrays) and uncertainty.joint_uncertainty reads; None otherwise."""
         run, self._gt_next = SequenceRun(self, self._gt_next, points, poses_2d, poses_3d, rig_ids, return_initial), None
-        self.seq_inliers, self.seq_n_consensus = run.inliers, run.n_consensus
-        self.report, self.gaussians, self.images = run.report, run.gaussians, run.images
-        self.reprojection = run.reprojection
+        run.publish(self, ("seq_inliers", "seq_n_consensus"))
         for b in run.starts():
             run.begin(self, b)
             self.run(iterations, groups_per_graph)      # (returns self.xyz, which take() copies)
@@ -1386,7 +1250,7 @@ class FrameBatchLoop(_GroupLoop):
         return run.result()
 
 
-class FramePipeline:
+class FramePipeline(SequenceSwitches):
     """A sequence of frames through `streams` FrameBatchLoops of `frames` frames each, one HIP stream per loop.
 
     Inside one FrameBatchLoop a group is two dependent launches: the compositing backward of all its frames, then one
@@ -1413,50 +1277,8 @@ class FramePipeline:
         self.reprojection = None     # set_reprojection_report: reprojection.SequenceReprojection of the last optimize_sequence
         self.smoothed = None         # set_smoothing: smoothing.Smoothed of the last optimize_sequence
 
-    def set_smoothing(self, half_window=None, degree=2, taper="tricube", use_covariance=True, cov_floor=0.0, groups=None):
-        """FrameBatchLoop.set_smoothing of every loop: from now on optimize_sequence smooths the joints it returns over time into
-        `self.smoothed` (a smoothing.Smoothed) by one launch on the caller's stream, behind its wait for every batch's stream --
-        and behind one joint_uncertainty launch with `use_covariance`, which needs keep_gaussians=True (`half_window=None`: off
-        again, and `smoothed` is None after the next sequence).  Returns the pipeline."""
-        for fb in self.loops:
-            fb.set_smoothing(half_window, degree, taper, use_covariance, cov_floor, groups)
-        return self
-
-    def set_outlier_rejection(self, reject_px=None, min_inliers=3):
-        """FrameBatchLoop.set_outlier_rejection of every loop: from now on optimize_sequence(None, detections) rejects outlier
-        detections while it triangulates (None: off again).  Returns the pipeline."""
-        for fb in self.loops:
-            fb.set_outlier_rejection(reject_px, min_inliers)
-        return self
-
-    def set_refinement(self, max_iters=16, huber_px=None):
-        """FrameBatchLoop.set_refinement of every loop: from now on optimize_sequence(None, detections) minimises the triangulated
-        initial joints' reprojection error before it starts (`max_iters=None`: off again).  Returns the pipeline."""
-        for fb in self.loops:
-            fb.set_refinement(max_iters, huber_px)
-        return self
-
-    def set_reprojection_report(self, on=True):
-        """FrameBatchLoop.set_reprojection_report of every loop: from now on optimize_sequence fills `self.reprojection` (a
-        reprojection.SequenceReprojection) with the reprojection errors of every frame's initial and final joints, each batch's
-        on its own stream (False: off again, and `reprojection` is None after the next sequence).  Returns the pipeline."""
-        for fb in self.loops:
-            fb.set_reprojection_report(on)
-        return self
-
-    def set_debug_images(self, frames):
-        """FrameBatchLoop.set_debug_images of every loop: from now on optimize_sequence pictures the frames with these sequence
-        indices into `self.images` (a preview.SequenceImages), each batch's pictures enqueued on its own stream (None: off again,
-        and `images` is None after the next sequence).  Returns the pipeline."""
-        for fb in self.loops:
-            fb.set_debug_images(frames)
-        return self
-
-    def set_ground_truth(self, gt):
-        """The (N,P,3) float32 ground truth, on the device, of the NEXT optimize_sequence (loops with `report_steps`), which takes
-        it and forgets it; None withdraws one that has not been taken.  Returns the pipeline."""
-        self._gt_next = _accept_gt(self.loops[0], gt)
-        return self
+    def _driven(self):
+        return self.loops       # (the switches set every loop: JointSwitches, SequenceSwitches)
 
     def optimize_sequence(self, points, poses_2d, iterations=500, groups_per_graph=25, interleave=100,
                           return_initial=False, rig_ids=None, poses_3d=None):
@@ -1470,27 +1292,12 @@ class FramePipeline:
         FrameBatchLoop.new_scenes; check_rigs() reports an id a device tensor held outside the bank.
         `poses_3d` (N,V,J,3), with `points=None`: every batch's initial joints are fused from the views' 3D predictions
         instead of triangulated, by one launch in the same place (initial_guess.fuse_predictions).
-        After `set_outlier_rejection(reject_px, min_inliers)`, with `points=None` and without `poses_3d` (refused otherwise): every
-        batch's triangulation rejects outlier detections first (FrameBatchLoop.new_scenes); afterwards `self.inliers` (N,V,J) bool and `self.n_consensus` (N,J) int32
-        hold every frame's views and counts, each batch's rows copied on its own stream (None after a sequence without
-        rejection).
-        Loops that report (`report_steps` / `save_iterations`): `self.report` holds traces, final errors, snapshots and step counts
-        of all N frames, copied on each batch's own stream -- the errors against the (N,P,3) ground truth given to
-        `set_ground_truth` before this call, NaN without one.  The return value is the same.
-        Loops built with keep_gaussians=True: `self.gaussians` (an uncertainty.SequenceGaussians) holds every frame's scaling,
-        rotation and opacity next to the joints returned, copied on each batch's own stream; None otherwise.
-        After `set_debug_images(frames)`: `self.images` holds the chosen frames' debug pictures, made on each batch's own stream;
-        None otherwise.
-        After `set_refinement(max_iters, huber_px)`, with `points=None` and without `poses_3d` (refused otherwise): every batch's
-        triangulated joints are refined in place by one more launch on its stream.  After `set_reprojection_report()`:
-        `self.reprojection` (a reprojection.SequenceReprojection) holds the reprojection errors of every frame's initial and final
-        joints against its detections, two launches per batch on its own stream; None otherwise.
-        After `set_smoothing(half_window, ...)`: `self.smoothed` (a smoothing.Smoothed) holds the returned joints smoothed over
-        time, enqueued on the caller's stream once it waits for every batch; None otherwise."""
+        The switches, the loops' reports and kept Gaussians fill the results FrameBatchLoop.optimize_sequence names, here with the
+        consensus pair in `self.inliers` (N,V,J) bool / `self.n_consensus` (N,J) int32; every batch's rows are made or copied on the
+        batch's own stream (the reprojection report: two launches per batch), the smoothing is enqueued on the caller's stream
+        once it waits for every batch.  The return value is the same with and without them."""
         run, self._gt_next = SequenceRun(self.loops[0], self._gt_next, points, poses_2d, poses_3d, rig_ids, return_initial), None
-        self.inliers, self.n_consensus = run.inliers, run.n_consensus
-        self.report, self.gaussians, self.images = run.report, run.gaussians, run.images
-        self.reprojection = run.reprojection
+        run.publish(self)
         cur = torch.cuda.current_stream(self.device)
         es = self.loops[0]._es is not None
         if es:

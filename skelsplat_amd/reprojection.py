@@ -12,9 +12,9 @@ from typing import Any, Optional
 import numpy as np
 import torch
 
-from .triangulation import projection_matrices
+from . import _pose_args as _pa
+from ._pose_args import MAX_VIEWS, as_real as _as_real       # (names other modules and tests read from here)
 
-MAX_VIEWS = 64
 REFINE_MAX_ITERS = 16               # SKS_REFINE_MAX_ITERS
 # the constants of k_refine (csrc/sks_reproject.hip), which the host path shares
 LAMBDA0, LAMBDA_DOWN, LAMBDA_UP, STOP_FRACTION = 1e-3, 0.1, 10.0, 1e-6
@@ -32,52 +32,6 @@ class Reprojection:
     per_view: Optional[Any] = None
     per_frame: Optional[Any] = None
     n_used: Optional[Any] = None
-
-
-def _tensor(a):
-    return a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
-
-
-def _projections(proj_or_cameras, dev):
-    """The forms triangulate_sequence accepts -> a float64 tensor (V,3,4) or (N,V,3,4) on `dev`."""
-    if torch.is_tensor(proj_or_cameras):
-        return proj_or_cameras.to(device=dev, dtype=torch.float64)
-    if isinstance(proj_or_cameras, np.ndarray):
-        return torch.as_tensor(proj_or_cameras, dtype=torch.float64).to(dev)
-    seq = list(proj_or_cameras)
-    return torch.as_tensor(np.asarray(seq) if seq and not hasattr(seq[0], "K") else projection_matrices(seq),
-                           dtype=torch.float64).to(dev)
-
-
-def _checked_shapes(P, N, V, J):
-    if N < 1 or J < 1:
-        raise ValueError(f"N = {N} frames of J = {J} joints: at least one of each")
-    if not 1 <= V <= MAX_VIEWS:
-        raise ValueError(f"{V} views: a joint takes 1 .. {MAX_VIEWS} (SKS_MAX_VIEWS)")
-    if tuple(P.shape) not in ((V, 3, 4), (N, V, 3, 4)):
-        raise ValueError(f"projection matrices must be (V,3,4) = {(V, 3, 4)} or (N,V,3,4) = {(N, V, 3, 4)}, got {tuple(P.shape)}")
-
-
-def _checked_valid(valid, single, dev, shape):
-    if valid is None:
-        return None
-    valid = _tensor(valid).to(device=dev, dtype=torch.bool)
-    valid = valid[None] if single else valid
-    if tuple(valid.shape) != shape:
-        raise ValueError(f"valid must be (N,V,J) = {shape}, got {tuple(valid.shape)}")
-    return valid.contiguous()
-
-
-def _as_real(t):
-    """float64 stays, everything else is read as float32 (the two forms the library takes)."""
-    return (t if t.dtype == torch.float64 else t.to(torch.float32)).contiguous()
-
-
-def _pick(t):
-    """(float pointer, double pointer) of a float32 / float64 tensor, or (None, None)."""
-    if t is None:
-        return None, None
-    return (None, t.data_ptr()) if t.dtype == torch.float64 else (t.data_ptr(), None)
 
 
 # ------------------------------------------------------------------------------------------------ the formulas on the host
@@ -218,8 +172,8 @@ def _launch_reproject(P, X, det, valid, res):
     from . import _lib
     dev, (N, J), V = X.device, X.shape[:2], P.shape[-3]
     with torch.cuda.device(dev):
-        rc = _lib.load().sks_reproject(N, V, J, P.data_ptr(), V * 12 if P.dim() == 4 else 0, *_pick(X), *_pick(det),
-                                       None if valid is None else valid.view(torch.uint8).data_ptr(),
+        rc = _lib.load().sks_reproject(N, V, J, P.data_ptr(), _pa.rig_stride(P, V), *_pa.pointers(X), *_pa.pointers(det),
+                                       _pa.byte_pointer(valid),
                                        *[res[k].data_ptr() if k in res else None for k in FIELDS],
                                        torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, "sks_reproject")
@@ -243,24 +197,23 @@ def reproject(proj_or_cameras, xyz, poses_2d=None, valid=None, want=FIELDS):
     want = tuple(want)
     if not want or any(w not in FIELDS for w in want):
         raise ValueError(f"want: a non-empty selection of {FIELDS}, got {want}")
-    as_array = not torch.is_tensor(xyz)
-    X = _tensor(xyz)
+    X, as_array = _pa.as_tensor(xyz)
     dev = X.device
     single = X.dim() == 2
     X = X[None] if single else X
     if X.dim() != 3 or X.shape[-1] != 3:
         raise ValueError(f"xyz must be (N,J,3) or (J,3), got {tuple(X.shape)}")
     N, J = X.shape[:2]
-    P = _projections(proj_or_cameras, dev)
+    P = _pa.projections(proj_or_cameras, dev)
     det = None
     if poses_2d is not None:
-        det = _tensor(poses_2d).to(dev)
+        det = _pa.as_tensor(poses_2d)[0].to(dev)
         det = det[None] if single else det
         if det.dim() != 4 or det.shape[-1] < 2 or det.shape[0] != N or det.shape[2] != J:
             raise ValueError(f"poses_2d must be (N,V,J,>=2) with N = {N}, J = {J}, got {tuple(det.shape)}")
     V = det.shape[1] if det is not None else P.shape[-3] if P.dim() in (3, 4) else 0
-    _checked_shapes(P, N, V, J)
-    valid = _checked_valid(valid, single, dev, (N, V, J))
+    _pa.check_shapes(P, N, V, J)
+    valid = _pa.check_valid(valid, single, dev, (N, V, J))
     if dev.type == "cuda":
         Xd = _as_real(X)
         dd = None if det is None else _as_real(det[..., :2])
@@ -276,11 +229,7 @@ def reproject(proj_or_cameras, xyz, poses_2d=None, valid=None, want=FIELDS):
         host = reproject_host(P.numpy(), X.numpy().astype(np.float64), None if det is None else det[..., :2].numpy().astype(np.float64),
                               None if valid is None else valid.numpy())
         res = {k: torch.as_tensor(host[k]) for k in want}
-    if single:
-        res = {k: t[0] for k, t in res.items()}
-    if as_array:
-        res = {k: t.numpy() for k, t in res.items()}
-    return Reprojection(**res)
+    return Reprojection(**{k: _pa.finish(t, single, as_array) for k, t in res.items()})
 
 
 def _checked_refinement(huber_px, max_iters):
@@ -312,30 +261,22 @@ def refine_triangulation(proj_or_cameras, poses_2d, xyz0, valid=None, huber_px=N
     joint's result does not depend on N, on its place in the batch or on the stream.  Arrays or CPU tensors: the same formulas
     in numpy."""
     huber, max_iters = _checked_refinement(huber_px, max_iters)
-    as_array = not torch.is_tensor(poses_2d)
-    x = _tensor(poses_2d)
+    x, as_array = _pa.as_tensor(poses_2d)
     dev = x.device
     single = x.dim() == 3
     x = x[None] if single else x
     if x.dim() != 4 or x.shape[-1] < 2:
         raise ValueError(f"poses_2d must be (N,V,J,>=2) or (V,J,>=2), got {tuple(x.shape)}")
     N, V, J = x.shape[:3]
-    P = _projections(proj_or_cameras, dev)
-    _checked_shapes(P, N, V, J)
-    valid = _checked_valid(valid, single, dev, (N, V, J))
-    X0 = _tensor(xyz0).to(dev)
+    P = _pa.projections(proj_or_cameras, dev)
+    _pa.check_shapes(P, N, V, J)
+    valid = _pa.check_valid(valid, single, dev, (N, V, J))
+    X0 = _pa.as_tensor(xyz0)[0].to(dev)
     X0 = X0[None] if single and X0.dim() == 2 else X0
     if tuple(X0.shape) != (N, J, 3):
         raise ValueError(f"xyz0 must be (N,J,3) = {(N, J, 3)}, got {tuple(X0.shape)}")
     X0 = _as_real(X0)
-    if out is not None:
-        shape = (J, 3) if single and out.dim() == 2 else (N, J, 3)
-        if (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != X0.dtype or out.device != dev
-                or not out.is_contiguous()):
-            raise ValueError(f"`out` must be a contiguous {X0.dtype} tensor of shape {shape} on {dev}")
-        res = out.view(N, J, 3)
-    else:
-        res = torch.empty_like(X0)
+    res = torch.empty_like(X0) if out is None else _pa.check_out(out, (N, J, 3), (X0.dtype,), dev, single)
     cost = torch.empty((N, J, 2), dtype=torch.float64, device=dev) if return_cost else None
     iters = torch.empty((N, J), dtype=torch.int32, device=dev) if return_iters else None
     if dev.type == "cuda":
@@ -343,9 +284,9 @@ def refine_triangulation(proj_or_cameras, poses_2d, xyz0, valid=None, huber_px=N
         xd = _as_real(x[..., :2])
         P = P.contiguous()
         with torch.cuda.device(dev):
-            rc = _lib.load().sks_triangulate_refine(N, V, J, P.data_ptr(), V * 12 if P.dim() == 4 else 0, *_pick(xd),
-                                                    None if valid is None else valid.view(torch.uint8).data_ptr(), *_pick(X0),
-                                                    huber, max_iters, *_pick(res), None if cost is None else cost.data_ptr(),
+            rc = _lib.load().sks_triangulate_refine(N, V, J, P.data_ptr(), _pa.rig_stride(P, V), *_pa.pointers(xd),
+                                                    _pa.byte_pointer(valid), *_pa.pointers(X0), huber, max_iters,
+                                                    *_pa.pointers(res), None if cost is None else cost.data_ptr(),
                                                     None if iters is None else iters.data_ptr(),
                                                     torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(rc, "sks_triangulate_refine")
@@ -358,15 +299,7 @@ def refine_triangulation(proj_or_cameras, poses_2d, xyz0, valid=None, huber_px=N
             cost.copy_(torch.as_tensor(cn))
         if iters is not None:
             iters.copy_(torch.as_tensor(it))
-    ret = out if out is not None else (res[0] if single else res)
-    if as_array and out is None:
-        ret = ret.numpy()
-    extra = []
-    for t in (cost, iters):
-        if t is not None:
-            t = t[0] if single else t
-            extra.append(t.numpy() if as_array else t)
-    return (ret, *extra) if extra else ret
+    return _pa.results(res, out, single, as_array, [t for t in (cost, iters) if t is not None])
 
 
 def evaluate_sequence_reprojection(err, groups=None, n_groups=None):
@@ -376,8 +309,7 @@ def evaluate_sequence_reprojection(err, groups=None, n_groups=None):
     NaN, NaN where there are none.  `groups`: optional (N) ints (ids outside 0 .. n_groups - 1 enter row 0 only); `n_groups`
     defaults to max(groups) + 1, which reads the ids back -- give it to stay on the device.  A tensor on a ROCm device: one launch
     of sks_eval_reprojection on the current stream; an array or a CPU tensor: numpy."""
-    as_array = not torch.is_tensor(err)
-    e = _tensor(err)
+    e, as_array = _pa.as_tensor(err)
     if e.dim() != 3 or e.shape[0] < 1 or e.shape[2] < 1 or not 1 <= e.shape[1] <= MAX_VIEWS:
         raise ValueError(f"err must be (N,V,J) with 1 .. {MAX_VIEWS} views, got {tuple(e.shape)}")
     N, V, J = e.shape
@@ -387,7 +319,7 @@ def evaluate_sequence_reprojection(err, groups=None, n_groups=None):
             raise ValueError(f"n_groups = {n_groups} without groups")
         n_groups, g = 0, None
     else:
-        g = _tensor(groups).to(device=dev, dtype=torch.int32).contiguous()
+        g = _pa.as_tensor(groups)[0].to(device=dev, dtype=torch.int32).contiguous()
         if tuple(g.shape) != (N,):
             raise ValueError(f"groups must be (N,) = {(N,)}, got {tuple(g.shape)}")
         if n_groups is None:

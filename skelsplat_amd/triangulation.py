@@ -7,9 +7,10 @@ batched DLT kernel (sks_triangulate), on the host by one batched SVD.  With `rej
 picks the views that agree first (sks_triangulate_robust on the device, consensus_cpu on the host)."""
 import itertools
 
-
 import numpy as np
 import torch
+
+from . import _pose_args as _pa
 
 
 def projection_matrices(cameras):
@@ -155,75 +156,38 @@ def triangulate_sequence(proj_or_cameras, poses_2d, valid=None, out=None, homoge
         reject_px, min_inliers = _checked_rejection(reject_px, min_inliers)
     elif return_inliers or out_inliers is not None:
         raise ValueError("return_inliers / out_inliers need reject_px: without rejection every kept view enters (inliers == valid)")
-    as_array = not torch.is_tensor(poses_2d)
-    x = torch.as_tensor(np.asarray(poses_2d)) if as_array else poses_2d
+    x, as_array = _pa.as_tensor(poses_2d)
     dev = x.device
-    if torch.is_tensor(proj_or_cameras):
-        P = proj_or_cameras.to(device=dev, dtype=torch.float64)
-    elif isinstance(proj_or_cameras, np.ndarray):
-        P = torch.as_tensor(proj_or_cameras, dtype=torch.float64).to(dev)
-    else:
-        seq = list(proj_or_cameras)
-        P = torch.as_tensor(np.asarray(seq) if seq and not hasattr(seq[0], "K") else projection_matrices(seq),
-                            dtype=torch.float64).to(dev)
+    P = _pa.projections(proj_or_cameras, dev)
     single = x.dim() == 3
-    if single:
-        x = x[None]
-        valid = None if valid is None else torch.as_tensor(valid)[None]
+    x = x[None] if single else x
     if x.dim() != 4 or x.shape[-1] < 2:
         raise ValueError(f"poses_2d must be (N,V,J,>=2) or (V,J,>=2), got {tuple(poses_2d.shape)}")
     N, V, J = x.shape[:3]
-    if N < 1 or J < 1:
-        raise ValueError(f"poses_2d {tuple(x.shape)}: at least one frame and one joint")
-    if not 1 <= V <= 64:
-        raise ValueError(f"{V} views: a joint's system takes 1 .. 64 (SKS_MAX_VIEWS)")
-    if tuple(P.shape) not in ((V, 3, 4), (N, V, 3, 4)):
-        raise ValueError(f"projection matrices must be (V,3,4) = {(V, 3, 4)} or (N,V,3,4) = {(N, V, 3, 4)}, "
-                         f"got {tuple(P.shape)}")
-    if valid is not None:
-        valid = torch.as_tensor(valid).to(device=dev, dtype=torch.bool)
-        if tuple(valid.shape) != (N, V, J):
-            raise ValueError(f"valid must be (N,V,J) = {(N, V, J)}, got {tuple(valid.shape)}")
+    _pa.check_shapes(P, N, V, J)
+    valid = _pa.check_valid(valid, single, dev, (N, V, J))
     shape, dtype = ((N, J, 4), torch.float64) if homogeneous else ((N, J, 3), torch.float32)
-    if out is not None:
-        want = shape[1:] if single and out.dim() == 2 else shape
-        if (not torch.is_tensor(out) or tuple(out.shape) != want or out.dtype != dtype or out.device != dev
-                or not out.is_contiguous()):
-            raise ValueError(f"`out` must be a contiguous {dtype} tensor of shape {want} on {dev}")
-        res = out.view(shape)
-    else:
-        res = torch.empty(shape, dtype=dtype, device=dev)
+    res = torch.empty(shape, dtype=dtype, device=dev) if out is None else _pa.check_out(out, shape, (dtype,), dev, single)
     inl = n_cons = None
-    if robust:
-        if out_inliers is not None:
-            inl, n_cons = out_inliers
-            if (not torch.is_tensor(inl) or tuple(inl.shape) != (N, V, J) or inl.dtype not in (torch.bool, torch.uint8)
-                    or inl.device != dev or not inl.is_contiguous()):
-                raise ValueError(f"`out_inliers[0]` must be a contiguous bool or uint8 tensor of shape {(N, V, J)} on {dev}")
-            if (not torch.is_tensor(n_cons) or tuple(n_cons.shape) != (N, J) or n_cons.dtype != torch.int32
-                    or n_cons.device != dev or not n_cons.is_contiguous()):
-                raise ValueError(f"`out_inliers[1]` must be a contiguous int32 tensor of shape {(N, J)} on {dev}")
-        else:
-            inl = torch.empty((N, V, J), dtype=torch.bool, device=dev)
-            n_cons = torch.empty((N, J), dtype=torch.int32, device=dev)
+    if robust and out_inliers is not None:
+        inl = _pa.check_out(out_inliers[0], (N, V, J), (torch.bool, torch.uint8), dev, name="`out_inliers[0]`")
+        n_cons = _pa.check_out(out_inliers[1], (N, J), (torch.int32,), dev, name="`out_inliers[1]`")
+    elif robust:
+        inl = torch.empty((N, V, J), dtype=torch.bool, device=dev)
+        n_cons = torch.empty((N, J), dtype=torch.int32, device=dev)
     if dev.type == "cuda":
         from . import _lib
-        xd = x[..., :2]
-        xd = (xd if xd.dtype == torch.float64 else xd.to(torch.float32)).contiguous()
-        P = P.contiguous()
-        vd = None if valid is None else valid.contiguous().view(torch.uint8)
+        xd, P = _pa.as_real(x[..., :2]), P.contiguous()
         n_used = torch.empty((N, J), dtype=torch.int32, device=dev) if return_n_used else None
-        f64 = xd.dtype == torch.float64
-        lib, rig = _lib.load(), V * 12 if P.dim() == 4 else 0
-        det = (None if f64 else xd.data_ptr(), xd.data_ptr() if f64 else None, None if vd is None else vd.data_ptr())
-        outs = (None if homogeneous else res.data_ptr(), res.data_ptr() if homogeneous else None,
-                None if n_used is None else n_used.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        lib = _lib.load()
+        det = (*_pa.pointers(xd), _pa.byte_pointer(valid))
+        outs = (*_pa.pointers(res), None if n_used is None else n_used.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
         with torch.cuda.device(dev):
             if robust:
-                rc = lib.sks_triangulate_robust(N, V, J, P.data_ptr(), rig, *det, reject_px, min_inliers, inl.data_ptr(),
-                                                n_cons.data_ptr(), *outs)
+                rc = lib.sks_triangulate_robust(N, V, J, P.data_ptr(), _pa.rig_stride(P, V), *det, reject_px, min_inliers,
+                                                inl.data_ptr(), n_cons.data_ptr(), *outs)
             else:
-                rc = lib.sks_triangulate(N, V, J, P.data_ptr(), rig, *det, *outs)
+                rc = lib.sks_triangulate(N, V, J, P.data_ptr(), _pa.rig_stride(P, V), *det, *outs)
         _lib.check(rc, "sks_triangulate_robust" if robust else "sks_triangulate")
     else:
         x64 = x[..., :2].to(torch.float64)
@@ -232,27 +196,18 @@ def triangulate_sequence(proj_or_cameras, poses_2d, valid=None, out=None, homoge
             inl.copy_(keep)
             n_cons.copy_(n_c)
             valid = keep
-        A, n_used = _systems_cpu(P, x64, valid)
+        S, n_used = _systems_cpu(P, x64, valid)
         # (no consensus over a NaN detection: the joint is NaN as on the device, where LAPACK would refuse the batch)
-        bad = ~torch.isfinite(A).all(dim=(-1, -2)) if robust else None
+        bad = ~torch.isfinite(S).all(dim=(-1, -2)) if robust else None
         if bad is not None and bool(bad.any()):
-            A = torch.where(bad[..., None, None], torch.zeros((), dtype=A.dtype), A)
-        X = torch.linalg.svd(A)[2][..., -1, :]
+            S = torch.where(bad[..., None, None], torch.zeros((), dtype=S.dtype), S)
+        X = torch.linalg.svd(S)[2][..., -1, :]
         X = X / X[..., 3:4]
         X = torch.where((n_used >= 2)[..., None], X, torch.full((), float("nan"), dtype=X.dtype))
         if bad is not None:
             X = torch.where(bad[..., None], torch.full((), float("nan"), dtype=X.dtype), X)
         res.copy_(X if homogeneous else X[..., :3])
-    ret = out if out is not None else (res[0] if single else res)
-    if as_array and out is None:
-        ret = ret.numpy()
-    extra = []
-    if return_n_used:
-        n_used = n_used[0] if single else n_used
-        extra.append(n_used.numpy() if as_array else n_used)
+    extras = [n_used] if return_n_used else []
     if return_inliers:
-        inl = inl if inl.dtype == torch.bool else inl.view(torch.bool)
-        for t in (inl, n_cons):
-            t = t[0] if single else t
-            extra.append(t.numpy() if as_array else t)
-    return (ret, *extra) if extra else ret
+        extras += [inl if inl.dtype == torch.bool else inl.view(torch.bool), n_cons]
+    return _pa.results(res, out, single, as_array, extras)

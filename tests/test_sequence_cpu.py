@@ -21,7 +21,8 @@ class StubLoop(types.SimpleNamespace):
         super().__init__(F=F, V=V, P=P, device=torch.device("cpu"), xyz=z(F, P, 3), scaling=z(F, P, 3), rotation=z(F, P, 4),
                          opacity=z(F, P, 1), inliers=z(F, V, P, dtype=torch.bool), n_consensus=z(F, P, dtype=torch.int32),
                          counters=z(F, 2, dtype=torch.int32), _es_state=z(F, 2, dtype=torch.int32), _gt_next=None, _report=None,
-                         _sel=None, _reject=None, _debug_frames=None, keep_gaussians=False, calls=[])
+                         _sel=None, _reject=None, _refine=None, _reproject=False, _smooth=None, _debug_frames=None,
+                         keep_gaussians=False, calls=[])
         self.__dict__.update(kw)
 
     def new_scenes(self, points, poses_2d=None, rig_ids=None, poses_3d=None):
