@@ -4,7 +4,11 @@ other, train.py:74-99) -- but many frames per launch: noisy 2D detections of N f
 iterations of the multi-view loop for every frame (loop.FramePipeline) -> MPJPE per frame.
 python examples/optimize_sequence.py [--frames 64] [--per-launch 16] [--streams 2] [--iters 500] [--init host|device|fuse] [--rigs R]
     [--report] [--uncertainty] [--reject-px PX] [--corrupt K] [--refine [--huber-px D]] [--images DIR [--image-frames 0,31,63]]
-    [--smooth H [--smooth-degree D]] [--motion wobble|smooth]
+    [--smooth H [--smooth-degree D]] [--motion wobble|smooth] [--view-weights scale|select [--view-threshold T]]
+--view-weights scale|select [--view-threshold T]: the optimiser step of every frame weights each view's joint gradient by its
+agreement with the other views' (pipe.set_view_weighting; DESIGN.md "View agreement"; T: select's cosine threshold, default 0.5).
+With --report: each view's mean final weight, and with --corrupt the mean weight of the corrupted (view, joint) detections
+against the clean ones.
 --rigs R: the frames cycle through R jittered ring rigs (SyntheticScene seeds 0 .. R-1), as a dataset whose scenes bring their own
 cameras does; one rigs.RigBank holds them on the device and every batch names its frames' rigs (rig_ids).
 --init host (default): the DLT runs on the host, frame by frame, and its points are uploaded; --init device: the detections
@@ -82,6 +86,8 @@ def main(argv=None):
     ap.add_argument("--smooth", type=int, default=None, metavar="H")
     ap.add_argument("--smooth-degree", type=int, default=2, metavar="D")
     ap.add_argument("--motion", choices=("wobble", "smooth"), default="wobble")
+    ap.add_argument("--view-weights", choices=("scale", "select"), default=None)
+    ap.add_argument("--view-threshold", type=float, default=None, metavar="T")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     sc = SyntheticScene(args.dataset, n_views=args.views, seed=0, device=dev)
@@ -99,10 +105,14 @@ def main(argv=None):
                        for f in range(args.frames)])
     p2d = np.stack([np.stack([project_points(c, gt[f]) + rng.normal(0, 3.0, (sc.n_points, 2)) for c in rigs[rig_of[f]]])
                     for f in range(args.frames)]).astype(np.float32)
+    corrupted = np.zeros((args.frames, args.views, sc.n_points), dtype=bool)
     for f in range(args.frames if args.corrupt else 0):
         for k in rng.choice(args.views * sc.n_points, size=args.corrupt, replace=False):
             r, th = rng.uniform(80.0, 300.0), rng.uniform(0.0, 2.0 * np.pi)
             p2d[f, k // sc.n_points, k % sc.n_points] += (r * np.cos(th), r * np.sin(th))
+            corrupted[f, k // sc.n_points, k % sc.n_points] = True
+    if args.view_threshold is not None and args.view_weights is None:
+        ap.error("--view-threshold is the cosine threshold of --view-weights select")
     if args.uncertainty and not args.report:
         ap.error("--uncertainty measures against --report's ground truth: use the two together")
     if args.smooth is not None and not args.report:
@@ -154,6 +164,8 @@ def main(argv=None):
             return pipe.optimize_sequence(init, p2d, iterations=args.iters, **ids), init
     if args.smooth is not None:
         pipe.set_smoothing(args.smooth, degree=args.smooth_degree, use_covariance=args.uncertainty)
+    if args.view_weights is not None:
+        pipe.set_view_weighting(args.view_weights, 0.5 if args.view_threshold is None else args.view_threshold)
     if args.report:
         pipe.set_reprojection_report()
         gt_dev = torch.as_tensor(gt.astype(np.float32), device=dev)
@@ -224,6 +236,13 @@ def main(argv=None):
         for name, t in (("initial", tables["initial"][0].tolist()), ("optimised", tables["final"][0].tolist())):
             print(f"reprojection error of the {name} joints: mean {t[0]:.3f} px; per view "
                   + " ".join(f"{x:.3f}" for x in t[1:1 + args.views]))
+    if args.report and args.view_weights is not None:
+        w = pipe.view_weights.double()              # (frames, views, joints): every frame's weights at its last step
+        print(f"view weights ({args.view_weights}), mean per view: " + " ".join(f"{x:.3f}" for x in w.mean(dim=(0, 2)).tolist()))
+        if args.corrupt:
+            bad = torch.as_tensor(corrupted[:, :, :sc.n_joints], device=dev)
+            print(f"  mean weight of the {int(bad.sum())} corrupted (view, joint) detections {float(w[bad].mean()):.3f}, "
+                  f"of the clean ones {float(w[~bad].mean()):.3f}")
     if args.smooth is not None:
         from skelsplat_amd.report import evaluate_sequence
         from skelsplat_amd.smoothing import sequence_accel, smooth_sequence

@@ -788,6 +788,72 @@ int sks_loop_fused_step_es_dv(int V, int P, int C, int W, int H, const float* vi
                               int frames, const float* const* hm_factors /*HOST 4 or NULL*/, int* es_state, int es_window,
                               float es_tolerance, int* es_host_flags /*pinned HOST frames or NULL*/, void* stream);
 
+/* View agreement: each view's xyz gradient weighted by how well it agrees with the others' (csrc/sks_loop_dev.h; added to
+ * sks_version 14: the number did not move).  The reference keeps the views' position gradients apart until the optimiser step
+ * (train.py:121,175,215-217) for the sake of utils/similarity_utils.py -- pairwise_cosine_similarity, compute_scaling_weights /
+ * weight_function, identify_consistent_views -- which weight or select views PER JOINT; these three entry points run them inside
+ * the step's own launch, where the plain ones take the mean of the V slots.  Scaling / rotation / opacity gradients stay
+ * last_view's.
+ *
+ * One fixed fp32 sequence (no contraction, IEEE division and square root), applied to joint j AFTER the group's slots are
+ * refreshed, so it sees the slots exactly as the plain mean does: the limb gradient every slot carries, the stale slots of views
+ * outside group_mask (quirk Q8), the slots an early stop leaves.  For views a, b in [0, V):
+ *   g_a = slot (a, j, :);  n_a = sqrtf((g0*g0 + g1*g1) + g2*g2) + 1e-8f;  u_a = g_a / n_a, component by component;
+ *   c_ab = (u_a0*u_b0 + u_a1*u_b1) + u_a2*u_b2 for a != b, c_aa = 1                              (pairwise_cosine_similarity)
+ * vw_mode 1, "scale" (compute_scaling_weights):
+ *   s_a = (sum over b != a, ascending, of c_ab) / (float)(V - 1), clamped to [-1, 1]; a NaN s_a gives w_a = 0;
+ *   s_a < 0: w_a = 0.8f * (s_a + 1.0f); otherwise w_a = (float)(0.54 * (log(2.0 + (double)s_a) / log(3.0)) + 0.46), in double;
+ *   xyz.grad = (sum over a, ascending, of w_a * g_a) / (float)V.  V < 2: every weight is 1.
+ * vw_mode 2, "select" (identify_consistent_views):
+ *   k_a = the number of b != a with c_ab >= vw_threshold; view a is kept when k_a >= 2; with n >= 1 views kept
+ *   xyz.grad = (sum over kept a, ascending, of g_a) / (float)n; with none kept (always so for V < 3) the plain mean, in the same
+ *   bits as the plain entry points.  The weights written out are 1.0 / 0.0.
+ * vw_mode 0: off, bit-identical to the entry point without _vw; anything else is an error.
+ * Two deviations from the reference's text: it divides by a hard-coded 3 (right for four views), here by V - 1; and its
+ * weight_function gives weight 0 where s rounds above 1 -- views in perfect agreement -- hence the clamp.
+ * No atomics; every sum has the order above, so results are bitwise reproducible.  The device's double log is not correctly
+ * rounded: a "scale" weight may differ from a correctly rounded evaluation by one fp32 ulp.
+ *
+ * Parameters: those of sks_loop_adam_step_es / sks_loop_fused_step_es / sks_loop_fused_step_es_dv with four more in front of
+ * `stream`; es_state == NULL is the step without a criterion (es_window, es_tolerance, the flags and -- sks_loop_adam_step_vw --
+ * loss_sums are then not read), so one entry serves both forms.
+ * vw_weights (frames,V,P) and vw_similarity (frames,P,V,V) -- frames = 1 for sks_loop_adam_step_vw, V the views of one frame --:
+ * optional device outputs of the step taken, written by the same launch; either may be NULL; a frame that has stopped writes
+ * nothing.  Shapes with V * P * 3 <= 8192 (4 x 17, 5 x 15, 31 x 19) spread the pairwise work over the workgroup from LDS; larger
+ * ones take a per-joint walk with the same results. */
+int sks_loop_adam_step_vw(int V, int P, const float* grads, float* slots, unsigned long long group_mask, int last_view,
+                          float* xyz, float* scaling, float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq,
+                          int* counters, int acc_steps, const double* lr_sched /*HOST 5*/, const double* lrs /*HOST 3*/,
+                          const double* adam /*HOST 3*/, float lambda_consistency, const int* limb /*HOST 8 or NULL*/,
+                          int shard_world, const double* loss_sums, int* es_state /*NULL: no criterion*/, int es_window,
+                          float es_tolerance, int* es_host_flag /*pinned HOST int or NULL*/, int vw_mode, float vw_threshold,
+                          float* vw_weights, float* vw_similarity, void* stream);
+int sks_loop_fused_step_vw(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                           const float* tanfovx /*HOST V*/, const float* tanfovy /*HOST V*/, const float* features,
+                           float scale_modifier, unsigned flags, int* radii, void* geom, const float* gt,
+                           const double* gt_totals, void* accum, double* loss_sums, float* packed, float* slots,
+                           unsigned long long group_mask, int last_view, float* xyz, float* scaling, float* rotation,
+                           float* opacity, float* exp_avg, float* exp_avg_sq, int* counters, int acc_steps,
+                           const double* lr_sched /*HOST 5*/, const double* lrs /*HOST 3*/, const double* adam /*HOST 3*/,
+                           float lambda_consistency, const int* limb /*HOST 8 or NULL*/,
+                           const int* view_wh /*HOST V x {W,H} or NULL*/, const size_t* gt_offsets /*HOST V or NULL*/,
+                           int frames, const float* const* hm_factors /*HOST 4 or NULL*/,
+                           int* es_state /*NULL: no criterion*/, int es_window, float es_tolerance,
+                           int* es_host_flags /*pinned HOST frames or NULL*/, int vw_mode, float vw_threshold,
+                           float* vw_weights, float* vw_similarity, void* stream);
+int sks_loop_fused_step_vw_dv(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                              const void* views_dev, const float* features, float scale_modifier, unsigned flags, int* radii,
+                              void* geom, const float* gt, const double* gt_totals, void* accum, double* loss_sums,
+                              float* packed, float* slots, unsigned long long group_mask, int last_view, float* xyz,
+                              float* scaling, float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq, int* counters,
+                              int acc_steps, const double* lr_sched_dev, const double* lrs /*HOST 3*/,
+                              const double* adam /*HOST 3*/, float lambda_consistency, const int* limb /*HOST 8 or NULL*/,
+                              const int* view_wh /*HOST V x {W,H} or NULL*/, const size_t* gt_offsets /*HOST V or NULL*/,
+                              int frames, const float* const* hm_factors /*HOST 4 or NULL*/,
+                              int* es_state /*NULL: no criterion*/, int es_window, float es_tolerance,
+                              int* es_host_flags /*pinned HOST frames or NULL*/, int vw_mode, float vw_threshold,
+                              float* vw_weights, float* vw_similarity, void* stream);
+
 /* What the reference reports about a pose while and after it optimises it (train.py:184-213, 227-229, 239-242; eval.py:115-142),
  * on the device (csrc/sks_report.hip; added to sks_version 14).  One launch each on `stream`, nothing synchronises, no atomics;
  * every sum has a fixed order, so every result is bitwise the same from run to run.  Device memory unless marked HOST.

@@ -127,6 +127,24 @@ STEP_PARAMS = {"sks_loop_adam_step": LOOP_ADAM_STEP_PARAMS, "sks_loop_adam_step_
 DV_PARAMS = {"sks_rig_select": RIG_SELECT_PARAMS, "sks_geometry_dv": GEOMETRY_DV_PARAMS,
              "sks_heatmap_factors_dv": HEATMAP_FACTORS_DV_PARAMS, "sks_heatmap_totals_dv": HEATMAP_TOTALS_DV_PARAMS,
              "sks_loop_fused_step_dv": LOOP_FUSED_STEP_DV_PARAMS, "sks_loop_fused_step_es_dv": LOOP_FUSED_STEP_ES_DV_PARAMS}
+# View agreement (include/skelsplat_hip.h "View agreement"): the early-stopping prototypes with VW_PARAMS in front of `stream`;
+# es_state == NULL there is the step without a criterion, vw_mode 0 the plain mean.  tests/test_view_weights_cpu.py holds the tables
+# to the header.
+VW_PARAMS = (("vw_mode", _i), ("vw_threshold", _f), ("vw_weights", _vp), ("vw_similarity", _vp))
+VW_MODES = {None: 0, "scale": 1, "select": 2}
+LOOP_ADAM_STEP_VW_PARAMS = LOOP_ADAM_STEP_ES_PARAMS[:-1] + VW_PARAMS + (("stream", _vp),)
+LOOP_FUSED_STEP_VW_PARAMS = LOOP_FUSED_STEP_ES_PARAMS[:-1] + VW_PARAMS + (("stream", _vp),)
+LOOP_FUSED_STEP_VW_DV_PARAMS = LOOP_FUSED_STEP_ES_DV_PARAMS[:-1] + VW_PARAMS + (("stream", _vp),)
+VW_STEP_PARAMS = {"sks_loop_adam_step_vw": LOOP_ADAM_STEP_VW_PARAMS, "sks_loop_fused_step_vw": LOOP_FUSED_STEP_VW_PARAMS,
+                  "sks_loop_fused_step_vw_dv": LOOP_FUSED_STEP_VW_DV_PARAMS}
+
+
+def vw_mode(view_weighting):
+    """The C ABI's vw_mode of a `view_weighting` keyword (None | "scale" | "select")."""
+    if view_weighting not in VW_MODES:
+        raise ValueError(f"view_weighting = {view_weighting!r}: expected None, 'scale' or 'select'")
+    return VW_MODES[view_weighting]
+
 
 # symbol -> (restype, argtypes); mirrors include/skelsplat_hip.h (tests check every declared symbol is exported)
 SIGNATURES = {
@@ -176,7 +194,7 @@ SIGNATURES = {
     "sks_smooth_sequence": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "sks_smooth_launch": (_i, [_i, _i, _i, _vp]),
     "sks_eval_accel": (_i, [_i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
-    **{name: (_i, [ct for _, ct in params]) for name, params in {**STEP_PARAMS, **DV_PARAMS}.items()},
+    **{name: (_i, [ct for _, ct in params]) for name, params in {**STEP_PARAMS, **DV_PARAMS, **VW_STEP_PARAMS}.items()},
     "sks_pose_errors": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "sks_loop_report": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "sks_eval_sequence": (_i, [_i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
@@ -224,6 +242,8 @@ def load(build_if_missing=True):
         if override and name in _PREFILL_SYMBOLS and not hasattr(lib, name):
             HAS_PREFILL = False      # an A/B against a build from before the prefill pair: its Workspace keeps one output set
             continue
+        if override and name in VW_STEP_PARAMS and not hasattr(lib, name):
+            continue                 # an A/B against a build from before view agreement: only view_weighting=None runs on it
         fn = getattr(lib, name)  # AttributeError = ABI drift, fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -341,6 +341,18 @@ class SequenceSwitches(JointSwitches):
         optimised covariances are calibrated (uncertainty.calibration) and has not been measured."""
         return self._set("_smooth", _smoothing(self._driven()[0], half_window, degree, taper, use_covariance, cov_floor, groups))
 
+    def set_view_weighting(self, mode, threshold=0.5):
+        """From now on the optimiser step of every frame weights each view's xyz gradient per joint by its agreement with the
+        other views' (`mode` "scale" or "select" with the cosine `threshold`; None: the plain mean again) -- the loops'
+        `view_weighting` keyword, set after construction.  Every `optimize_sequence` then keeps each frame's final weights in
+        `view_weights` (N,V,P) (a FrameBatchLoop: `seq_view_weights`), each batch's rows copied on the batch's own stream; None
+        after a sequence without it.  Captured graphs hold the step's entry point: they are dropped and captured again."""
+        from . import _lib
+        _lib.vw_mode(mode)
+        for loop in self._driven():
+            loop._set_view_weighting(mode, threshold)
+        return self
+
     def set_debug_images(self, frames):
         """The reference's debug pictures (configs/*.yaml `debug.save_images`, train.py:113-114, 143-144, 236-237) for the frames
         with these sequence indices, from now on: every `optimize_sequence` fills `self.images` (a preview.SequenceImages) with
@@ -390,12 +402,19 @@ class SequenceRun:
         self.images = _sequence_images(loop, self.N)
         self.reprojection = _sequence_reprojection(loop, self.N)
         self.smoothing = _sequence_smoothing(loop, self.N, who)
+        # view agreement on: every frame's final weights (N,V,P), each batch's rows copied on its own stream (take)
+        self.view_weights = (torch.zeros((self.N, loop.V, loop.P), dtype=torch.float32, device=loop.device)
+                             if getattr(loop, "_vw_mode", 0) else None)
 
     def publish(self, owner, consensus=("inliers", "n_consensus")):
         """The results this sequence fills, onto the object that runs it, under the names optimize_sequence documents; the
         consensus pair under the two names given (a FrameBatchLoop keeps `inliers` / `n_consensus` for its batch)."""
         for name, value in zip(consensus, (self.inliers, self.n_consensus)):
             setattr(owner, name, value)
+        if hasattr(owner, "loops"):      # (a pipeline: a FrameBatchLoop's own `view_weights` is its batch's)
+            owner.view_weights = self.view_weights
+        else:
+            owner.seq_view_weights = self.view_weights
         owner.report, owner.gaussians, owner.images, owner.reprojection = self.report, self.gaussians, self.images, self.reprojection
 
     def smoothed(self):
@@ -440,6 +459,8 @@ class SequenceRun:
         self.out[b:b + n] = loop.xyz[:n]
         if self.stopped_at is not None:
             self.stopped_at[b:b + n] = loop._es_state[:n, 1]        # (0: the frame ran to the end)
+        if self.view_weights is not None:
+            self.view_weights[b:b + n] = loop.view_weights[:n]
         for kept in (self.gaussians, self.images, self.report, self.reprojection):
             if kept is not None:
                 kept.take(loop, b, n)

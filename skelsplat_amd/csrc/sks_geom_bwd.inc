@@ -553,8 +553,11 @@ __global__ void k_mean_views(int V, int P, const float* __restrict__ dmeans3D, f
 // ------------------------------------------------------------------------------------------------------------
 // VT = ViewTan: the per-view scalars by value.  VT = ViewTanDev (sks_loop_fused_step_dv): they are read from the device table, and
 // frame f's LR schedule is row f of vt.sched instead of the one schedule in `aa`.
-template <bool ES = false, class VT = ViewTan>
-__global__ __launch_bounds__(256) void k_step_tail(GeomBwdArgs ga, VT vt, sksloop::AdamArgs aa, int V, Geom g, int* radii)
+// VW (k_step_tail_vw): phase B weights the views by their agreement (sks_loop_dev.h); frame f's rows of vw.weights (frames,V,P) and
+// vw.similarity (frames,P,V,V) are written by the step it takes, never by a frame that has stopped.
+template <bool ES, class VT, bool VW>
+__device__ __forceinline__ void step_tail_body(GeomBwdArgs& ga, VT& vt, sksloop::AdamArgs& aa, int V, Geom& g, int* radii,
+                                               sksloop::ViewWeightArgs* vw)
 {
     __shared__ float s_xyz[256 * 3];
     __shared__ float s_hyp[6];
@@ -571,6 +574,10 @@ __global__ __launch_bounds__(256) void k_step_tail(GeomBwdArgs ga, VT vt, sksloo
         aa.grads += (size_t)vb * P * 11; aa.slots += (size_t)vb * P * 3;
         aa.xyz += (size_t)f * P * 3; aa.scaling += (size_t)f * P * 3; aa.rotation += (size_t)f * P * 4; aa.opacity += (size_t)f * P;
         aa.m += (size_t)f * P * 11; aa.vv += (size_t)f * P * 11; aa.counters += 2 * f;
+    }
+    if constexpr (VW) {
+        if (vw->weights) vw->weights += (size_t)vb * P;
+        if (vw->similarity) vw->similarity += (size_t)vb * P * V;
     }
     if constexpr (std::is_same<VT, ViewTanDev>::value) {
         // the frame's own schedule (frames of different rigs: lr = position_lr x that rig's extent), {log lr_init, log lr_final,
@@ -630,9 +637,21 @@ __global__ __launch_bounds__(256) void k_step_tail(GeomBwdArgs ga, VT vt, sksloo
         }
     }
     const sksloop::AdamLdsParams mirror{ s_np, s_np + 3 * P, s_np + 6 * P, s_np + 10 * P };
-    sksloop::adam_block_finish(aa, s_xyz, s_hyp, s_d, s_it, &mirror, /*step_sizes_ready=*/true);
+    sksloop::adam_block_finish<VW>(aa, s_xyz, s_hyp, s_d, s_it, &mirror, /*step_sizes_ready=*/true, vw);
     __syncthreads();   // the parameters are updated
     for (int v = wv; v < V; v += 4)
         geom_fwd_one(P, vt, ga.vms, ga.pms, mirror.xyz, mirror.opacity, mirror.scaling, mirror.rotation, nullptr,
                      ga.smod, ga.flags, g, radii, vb + v, lane, lane < P);
+}
+
+template <bool ES = false, class VT = ViewTan>
+__global__ __launch_bounds__(256) void k_step_tail(GeomBwdArgs ga, VT vt, sksloop::AdamArgs aa, int V, Geom g, int* radii)
+{
+    step_tail_body<ES, VT, false>(ga, vt, aa, V, g, radii, nullptr);
+}
+template <bool ES = false, class VT = ViewTan>
+__global__ __launch_bounds__(256) void k_step_tail_vw(GeomBwdArgs ga, VT vt, sksloop::AdamArgs aa, int V, Geom g, int* radii,
+                                                      sksloop::ViewWeightArgs vw)
+{
+    step_tail_body<ES, VT, true>(ga, vt, aa, V, g, radii, &vw);
 }

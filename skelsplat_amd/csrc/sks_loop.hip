@@ -65,7 +65,11 @@ __global__ void k_loop_pack(int V, int P, const float* __restrict__ g_means, con
 
 using sksloop::AdamArgs;
 
-__global__ __launch_bounds__(256) void k_loop_adam(AdamArgs a)
+using sksloop::ViewWeightArgs;
+
+// k_loop_adam's body.  VW: the view-agreement instantiation (k_loop_adam_vw), which alone reads `vw`.
+template <bool VW>
+__device__ __forceinline__ void loop_adam_body(AdamArgs& a, const ViewWeightArgs* vw)
 {
     __shared__ float s_xyz[256 * 3];
     __shared__ float s_hyp[6];
@@ -87,8 +91,11 @@ __global__ __launch_bounds__(256) void k_loop_adam(AdamArgs a)
     }
     sksloop::adam_block_begin(a, s_xyz, s_d, s_it);
     __syncthreads();
-    sksloop::adam_block_finish(a, s_xyz, s_hyp, s_d, s_it);
+    sksloop::adam_block_finish<VW>(a, s_xyz, s_hyp, s_d, s_it, nullptr, false, vw);
 }
+
+__global__ __launch_bounds__(256) void k_loop_adam(AdamArgs a) { loop_adam_body<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void k_loop_adam_vw(AdamArgs a, ViewWeightArgs vw) { loop_adam_body<true>(a, &vw); }
 
 
 // torch.optim.Adam's step for up to ADAM_MULTI_MAX parameter tensors in ONE launch (the reference's optimiser has six parameter
@@ -137,21 +144,43 @@ int sks_loop_pack_grads(int V, int P, const float* dL_dmeans3D, const float* dL_
     return 0;
 }
 
+// sks_loop_adam_step{,_es,_vw}: one host implementation.  es_state == nullptr: no criterion; vw_mode == 0: the plain mean
+// (k_loop_adam, the launch the first two always make).
+static int loop_adam_step_impl(int V, int P, const float* grads, const sksloop::Optimiser& opt, int shard_world,
+                               const double* loss_sums, int* es_state, int es_window, float es_tolerance, int* es_host_flag,
+                               int vw_mode, float vw_threshold, float* vw_weights, float* vw_similarity, void* stream)
+{
+    if (V < 1 || V > SKS_MAX_VIEWS || P < 1 || P > SKS_SMALL_P) return fail3(-1, "loop_adam: V or P out of range");
+    if (es_state) {
+        if (es_window < 1 || es_window > sksloop::ES_MAX_WINDOW) return fail3(-1, "loop_adam_es: window out of range [1, 16]");
+        if (shard_world == 1 && !loss_sums) return fail3(-2, "loop_adam_es: loss_sums is required on one rank");
+    }
+    if (vw_mode < 0 || vw_mode > 2) return fail3(-1, "loop_adam_vw: vw_mode must be 0 (off), 1 (scale) or 2 (select)");
+    AdamArgs a;
+    if (const char* err = sksloop::fill_adam_args(a, V, P, grads, opt, shard_world)) return fail3(-2, err);
+    if (es_state) {
+        a.es_state = es_state; a.es_window = es_window; a.es_tol = es_tolerance; a.es_sums = loss_sums; a.es_host_flag = es_host_flag;
+        if (shard_world > 1 && !loss_sums) a.rank_stride = sksloop::es_tail_offset(a.vmax, P) + 4ll * a.vmax;
+    }
+    if (vw_mode == 0) hipLaunchKernelGGL(k_loop_adam, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    else {
+        const ViewWeightArgs vw{ vw_mode, vw_threshold, vw_weights, vw_similarity };
+        hipLaunchKernelGGL(k_loop_adam_vw, dim3(1), dim3(256), 0, (hipStream_t)stream, a, vw);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail3((int)e, hipGetErrorString(e));
+    return 0;
+}
+
 int sks_loop_adam_step(int V, int P, const float* grads, float* slots, unsigned long long group_mask, int last_view,
                        float* xyz, float* scaling, float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq,
                        int* counters, int acc_steps, const double* lr_sched /*HOST 5: init, final, delay_mult, delay_steps, max_steps*/,
                        const double* lrs /*HOST 3: scaling, rotation, opacity*/, const double* adam /*HOST 3: beta1, beta2, eps*/,
                        float lambda_consistency, const int* limb /*HOST 8 or NULL*/, int shard_world, void* stream)
 {
-    if (V < 1 || V > SKS_MAX_VIEWS || P < 1 || P > SKS_SMALL_P) return fail3(-1, "loop_adam: V or P out of range");
-    AdamArgs a;
     sksloop::Optimiser opt;
     SKS_TAKE_OPTIMISER(opt, lr_sched);
-    if (const char* err = sksloop::fill_adam_args(a, V, P, grads, opt, shard_world)) return fail3(-2, err);
-    hipLaunchKernelGGL(k_loop_adam, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail3((int)e, hipGetErrorString(e));
-    return 0;
+    return loop_adam_step_impl(V, P, grads, opt, shard_world, nullptr, nullptr, 0, 0.0f, nullptr, 0, 0.0f, nullptr, nullptr, stream);
 }
 
 int sks_loop_adam_step_es(int V, int P, const float* grads, float* slots, unsigned long long group_mask, int last_view,
@@ -162,18 +191,23 @@ int sks_loop_adam_step_es(int V, int P, const float* grads, float* slots, unsign
 {
     if (V < 1 || V > SKS_MAX_VIEWS || P < 1 || P > SKS_SMALL_P) return fail3(-1, "loop_adam: V or P out of range");
     if (!es_state) return fail3(-2, "loop_adam_es: es_state is required (sks_loop_adam_step is the step without a criterion)");
-    if (es_window < 1 || es_window > sksloop::ES_MAX_WINDOW) return fail3(-1, "loop_adam_es: window out of range [1, 16]");
-    if (shard_world == 1 && !loss_sums) return fail3(-2, "loop_adam_es: loss_sums is required on one rank");
-    AdamArgs a;
     sksloop::Optimiser opt;
     SKS_TAKE_OPTIMISER(opt, lr_sched);
-    if (const char* err = sksloop::fill_adam_args(a, V, P, grads, opt, shard_world)) return fail3(-2, err);
-    a.es_state = es_state; a.es_window = es_window; a.es_tol = es_tolerance; a.es_sums = loss_sums; a.es_host_flag = es_host_flag;
-    if (shard_world > 1 && !loss_sums) a.rank_stride = sksloop::es_tail_offset(a.vmax, P) + 4ll * a.vmax;
-    hipLaunchKernelGGL(k_loop_adam, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail3((int)e, hipGetErrorString(e));
-    return 0;
+    return loop_adam_step_impl(V, P, grads, opt, shard_world, loss_sums, es_state, es_window, es_tolerance, es_host_flag,
+                               0, 0.0f, nullptr, nullptr, stream);
+}
+
+int sks_loop_adam_step_vw(int V, int P, const float* grads, float* slots, unsigned long long group_mask, int last_view,
+                          float* xyz, float* scaling, float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq,
+                          int* counters, int acc_steps, const double* lr_sched, const double* lrs, const double* adam,
+                          float lambda_consistency, const int* limb, int shard_world, const double* loss_sums, int* es_state,
+                          int es_window, float es_tolerance, int* es_host_flag, int vw_mode, float vw_threshold,
+                          float* vw_weights, float* vw_similarity, void* stream)
+{
+    sksloop::Optimiser opt;
+    SKS_TAKE_OPTIMISER(opt, lr_sched);
+    return loop_adam_step_impl(V, P, grads, opt, shard_world, loss_sums, es_state, es_window, es_tolerance, es_host_flag,
+                               vw_mode, vw_threshold, vw_weights, vw_similarity, stream);
 }
 
 int sks_adam_multi(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,

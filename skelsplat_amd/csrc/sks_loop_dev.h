@@ -188,8 +188,62 @@ __device__ __forceinline__ void adam_step_sizes(const AdamArgs& a, const double*
     s_hyp[4] = (float)sqrt(1.0 - s_d[3]);
 }
 
+// View agreement (include/skelsplat_hip.h "View agreement"): the per-view weights of the xyz gradient's mean.
+// weights (V,P) / similarity (P,V,V): optional outputs of the step taken, this scene's (a frame's own slice); either may be null.
+struct ViewWeightArgs {
+    int mode;          // 1 scale, 2 select (0 never reaches the weighted instantiations: the host launches the plain ones)
+    float threshold;   // select: a view agrees with another at c >= threshold
+    float* weights;
+    float* similarity;
+};
+constexpr int VW_SCALE = 1, VW_SELECT = 2;
+
+// n_a, u_a of one slot: n = sqrtf((g0 g0 + g1 g1) + g2 g2) + 1e-8f, u = g / n
+__device__ __forceinline__ void vw_unit(const float* g, float* u)
+{
+    const float n = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]) + 1e-8f;
+    u[0] = g[0] / n; u[1] = g[1] / n; u[2] = g[2] / n;
+}
+__device__ __forceinline__ float vw_cos(const float* ua, const float* ub) { return (ua[0] * ub[0] + ua[1] * ub[1]) + ua[2] * ub[2]; }
+// view a's weight from the sum of its cosines with the others (ascending b != a) and the number of them >= threshold
+__device__ __forceinline__ float vw_weight(int mode, float csum, int agree, int V)
+{
+    if (mode == VW_SELECT) return agree >= 2 ? 1.0f : 0.0f;
+    if (V < 2) return 1.0f;
+    float s = csum / (float)(V - 1);
+    if (s != s) return 0.0f;
+    s = s < -1.0f ? -1.0f : (s > 1.0f ? 1.0f : s);    // (views in perfect agreement round above 1: the reference's weight there is 0)
+    if (s < 0.0f) return 0.8f * (s + 1.0f);
+    return (float)(0.54 * (log(2.0 + (double)s) / 1.0986122886681098 /* log(3.0) */) + 0.46);
+}
+// the merged xyz gradient of one joint: views fed in ascending order, then finish()
+struct VwMerge {
+    float acc[3] = { 0.0f, 0.0f, 0.0f }, plain[3] = { 0.0f, 0.0f, 0.0f };
+    int kept = 0;
+    __device__ __forceinline__ void add(int mode, float w, const float* g)
+    {
+        if (mode == VW_SCALE) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) acc[c] += w * g[c];
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; c++) { plain[c] += g[c]; if (w != 0.0f) acc[c] += g[c]; }
+            kept += w != 0.0f;
+        }
+    }
+    __device__ __forceinline__ void finish(int mode, int V, float* out) const
+    {
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+            out[c] = mode == VW_SCALE ? acc[c] / (float)V : (kept >= 1 ? acc[c] / (float)kept : plain[c] / (float)V);
+    }
+};
+
+// VW: the mean over the V slots is weighted by the views' agreement (`vw`); VW = false is the plain mean, and `vw` is not read.
+template <bool VW = false>
 __device__ __forceinline__ void adam_block_finish(const AdamArgs& a, float* s_xyz, float* s_hyp, double* s_d, int* s_it,
-                                                  const AdamLdsParams* mirror = nullptr, bool step_sizes_ready = false)
+                                                  const AdamLdsParams* mirror = nullptr, bool step_sizes_ready = false,
+                                                  const ViewWeightArgs* vw = nullptr)
 {
     const int p = threadIdx.x;
     const int P = a.P, V = a.V;
@@ -240,7 +294,8 @@ __device__ __forceinline__ void adam_block_finish(const AdamArgs& a, float* s_xy
     constexpr int SLOT_LDS = 8192;
     __shared__ float s_gc[256 * 3];
     __shared__ float s_slot[SLOT_LDS];
-    const bool wide = V > 8 && V * P * 3 <= SLOT_LDS;   // (block-uniform)
+    // (block-uniform.  VW: the pairwise work reads every view's slot of a joint V times over: parked whenever they fit)
+    const bool wide = (VW || V > 8) && V * P * 3 <= SLOT_LDS;
     if (wide) {
         if (live) { s_gc[3 * p] = gc[0]; s_gc[3 * p + 1] = gc[1]; s_gc[3 * p + 2] = gc[2]; }
         __syncthreads();
@@ -261,8 +316,78 @@ __device__ __forceinline__ void adam_block_finish(const AdamArgs& a, float* s_xy
         }
         __syncthreads();
     }
+    if constexpr (VW) {
+        // The weights of every (view, joint), the workgroup's threads side by side from the parked slots: a pass that leaves the
+        // unit vectors in LDS, then one thread per (a, j) walks row a of joint j's cosine matrix (V dot products from LDS, the
+        // row's sum in ascending b) and forms w_a; the joint's own thread then only adds V weighted slots.  Stride 3 floats
+        // between neighbouring joints: no bank is hit twice by one access.
+        __shared__ float s_unit[SLOT_LDS];
+        __shared__ float s_w[SLOT_LDS / 3 + 2];
+        const int mode = vw->mode;
+        if (wide) {
+            for (int i = p; i < V * P; i += (int)blockDim.x) vw_unit(s_slot + 3 * i, s_unit + 3 * i);
+            __syncthreads();
+            for (int i = p; i < V * P; i += (int)blockDim.x) {
+                const int va = i / P, j = i - va * P;
+                const float ua[3] = { s_unit[3 * i], s_unit[3 * i + 1], s_unit[3 * i + 2] };
+                float* sim = vw->similarity ? vw->similarity + ((size_t)j * V + va) * V : nullptr;
+                float csum = 0.0f;
+                int agree = 0;
+                for (int vb = 0; vb < V; vb++) {
+                    float c = vw_cos(ua, s_unit + 3 * (vb * P + j));
+                    if (vb == va) c = 1.0f;
+                    else { csum += c; agree += c >= vw->threshold; }
+                    if (sim) sim[vb] = c;
+                }
+                const float w = vw_weight(mode, csum, agree, V);
+                s_w[i] = w;
+                if (vw->weights) vw->weights[i] = w;
+            }
+            __syncthreads();
+            if (live) {
+                VwMerge mg;
+                for (int v = 0; v < V; v++) mg.add(mode, s_w[v * P + p], s_slot + 3 * (v * P + p));
+                mg.finish(mode, V, g11);
+            }
+        } else if (live) {
+            // the slots do not fit (V * P * 3 > SLOT_LDS): the joint's thread refreshes its own slots and walks the pairs itself,
+            // forming each unit vector again from the slot where it is needed (same operations: same bits)
+            for (int v = 0; v < V; v++) {
+                if ((a.group_mask >> v) & 1ull) {
+                    float* sl = a.slots + ((size_t)v * P + p) * 3;
+                    const float* gr = grad_rows(a, v) + (size_t)p * 11;
+#pragma unroll
+                    for (int c = 0; c < 3; c++) sl[c] = gr[c] + gc[c];
+                }
+            }
+            VwMerge mg;
+            for (int va = 0; va < V; va++) {
+                const float* sa = a.slots + ((size_t)va * P + p) * 3;
+                const float ga[3] = { sa[0], sa[1], sa[2] };
+                float ua[3];
+                vw_unit(ga, ua);
+                float* sim = vw->similarity ? vw->similarity + ((size_t)p * V + va) * V : nullptr;
+                float csum = 0.0f;
+                int agree = 0;
+                for (int vb = 0; vb < V; vb++) {
+                    const float* sb = a.slots + ((size_t)vb * P + p) * 3;
+                    const float gb[3] = { sb[0], sb[1], sb[2] };
+                    float ub[3];
+                    vw_unit(gb, ub);
+                    float c = vw_cos(ua, ub);
+                    if (vb == va) c = 1.0f;
+                    else { csum += c; agree += c >= vw->threshold; }
+                    if (sim) sim[vb] = c;
+                }
+                const float w = vw_weight(mode, csum, agree, V);
+                if (vw->weights) vw->weights[(size_t)va * P + p] = w;
+                mg.add(mode, w, ga);
+            }
+            mg.finish(mode, V, g11);
+        }
+    }
     if (live) {
-        for (int v = 0; v < V; v++) {
+        for (int v = 0; !VW && v < V; v++) {
             if (wide) {
 #pragma unroll
                 for (int c = 0; c < 3; c++) g11[c] += s_slot[3 * (v * P + p) + c];
@@ -277,8 +402,10 @@ __device__ __forceinline__ void adam_block_finish(const AdamArgs& a, float* s_xy
 #pragma unroll
             for (int c = 0; c < 3; c++) g11[c] += sl[c];   // mean over the V slots, view order (train.py:215-217)
         }
+        if constexpr (!VW) {
 #pragma unroll
-        for (int c = 0; c < 3; c++) g11[c] /= (float)V;
+            for (int c = 0; c < 3; c++) g11[c] /= (float)V;
+        }
         const float* gl = grad_rows(a, a.last_view) + (size_t)p * 11;
 #pragma unroll
         for (int c = 3; c < 11; c++) g11[c] = gl[c];

@@ -105,9 +105,10 @@ struct StepHeatmaps { const int* view_wh; const size_t* gt_offsets; int frames; 
 struct EarlyStop { int* es_state; int es_window; float es_tolerance; int* es_host_flags; };
 // LOOP_FUSED_STEP{,_ES,_DV,_ES_DV}_PARAMS.  views_dev: the _dv entries' device view table, else null; opt: OPTIMISER_PARAMS (_dv:
 // opt.lr_sched is NO_SCHED and every frame's schedule row is read in the kernel from lr_sched_dev)
+// vw: the *_vw entries' view agreement (mode 0: off, the plain entries; weights (frames,Vf,P) / similarity (frames,P,Vf,Vf) or null)
 struct StepCall {
     Cameras cam; const void* views_dev; StepRender r; sksloop::Optimiser opt; const double* lr_sched_dev; StepHeatmaps hm; EarlyStop es;
-    hipStream_t stream;
+    hipStream_t stream; sksloop::ViewWeightArgs vw;
 };
 
 int check_common(int V, int P, int C, int W, int H)
@@ -797,6 +798,9 @@ int loop_fused_step_impl(const StepCall& c)
     if (int rc = check_common(cam)) return rc;
     if (P < 1 || P > 64) return fail(-1, "fused step needs 1 <= P <= 64 (got %d)", P);
     if (int rc = check_frames(V, frames)) return rc;
+    if (c.vw.mode < 0 || c.vw.mode > 2) return fail(-1, "fused step: vw_mode = %d, expected 0 (off), 1 (scale) or 2 (select)", c.vw.mode);
+    if (c.es.es_state && (c.es.es_window < 1 || c.es.es_window > sksloop::ES_MAX_WINDOW))
+        return fail(-1, "fused step: early-stopping window %d out of range [1, %d]", c.es.es_window, sksloop::ES_MAX_WINDOW);
     const int Vf = V / frames;   // views of one frame: the optimiser's V (slots, group mask, last_view are per frame)
     if (int rc = require({ cam.viewmatrix, cam.projmatrix, cam.tanfovx, cam.tanfovy, c.r.features, c.r.radii, c.r.geom,
                            c.r.gt ? (const void*)c.r.gt : (const void*)hm_factors, c.r.gt_totals, c.r.accum, c.r.loss_sums, c.r.packed }))
@@ -826,7 +830,15 @@ int loop_fused_step_impl(const StepCall& c)
     GeomBwdArgs ga{ P, C, W, H, flags, cam.viewmatrix, cam.projmatrix, opt.xyz, opt.opacity, opt.scaling, opt.rotation, nullptr, c.r.scale_modifier,
                     c.r.radii, (const float*)c.r.accum, BWD_SPLITS, c.r.gt_totals, c.r.loss_sums, c.r.packed, nullptr, nullptr, nullptr, nullptr,
                     nullptr, nullptr, nullptr };
-    if (c.views_dev) {
+    if (c.vw.mode) {   // the view-agreement instantiations: the same four forms with the weights' record behind the arguments
+        const sksloop::ViewWeightArgs vw = c.vw;
+        if (c.views_dev) {
+            const ViewTanDev vd = views_dev_from(c.views_dev, c.lr_sched_dev);
+            if (es) hipLaunchKernelGGL((k_step_tail_vw<true, ViewTanDev>), dim3(frames), dim3(256), 0, st, ga, vd, aa, Vf, g, c.r.radii, vw);
+            else hipLaunchKernelGGL((k_step_tail_vw<false, ViewTanDev>), dim3(frames), dim3(256), 0, st, ga, vd, aa, Vf, g, c.r.radii, vw);
+        } else if (es) hipLaunchKernelGGL(k_step_tail_vw<true>, dim3(frames), dim3(256), 0, st, ga, vt, aa, Vf, g, c.r.radii, vw);
+        else hipLaunchKernelGGL(k_step_tail_vw<false>, dim3(frames), dim3(256), 0, st, ga, vt, aa, Vf, g, c.r.radii, vw);
+    } else if (c.views_dev) {
         const ViewTanDev vd = views_dev_from(c.views_dev, c.lr_sched_dev);
         if (es) hipLaunchKernelGGL((k_step_tail<true, ViewTanDev>), dim3(frames), dim3(256), 0, st, ga, vd, aa, Vf, g, c.r.radii);
         else hipLaunchKernelGGL((k_step_tail<false, ViewTanDev>), dim3(frames), dim3(256), 0, st, ga, vd, aa, Vf, g, c.r.radii);
@@ -1244,6 +1256,47 @@ int sks_loop_fused_step_es_dv(int V, int P, int C, int W, int H, const float* vi
     SKS_TAKE_STEP_CALL(c, NO_SCHED);
     c.views_dev = views_dev, c.lr_sched_dev = lr_sched_dev;
     SKS_TAKE_ES(c.es);
+    return loop_fused_step_impl(c);
+}
+
+// The view-agreement forms: es_state == NULL is the step without a criterion, vw_mode == 0 the plain mean (loop_fused_step_impl)
+#define SKS_TAKE_VW(r) ((r).mode = vw_mode, (r).threshold = vw_threshold, (r).weights = vw_weights, (r).similarity = vw_similarity)
+int sks_loop_fused_step_vw(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                           const float* tanfovx, const float* tanfovy, const float* features, float scale_modifier,
+                           unsigned flags, int* radii, void* geom, const float* gt, const double* gt_totals, void* accum,
+                           double* loss_sums, float* packed, float* slots, unsigned long long group_mask, int last_view,
+                           float* xyz, float* scaling, float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq,
+                           int* counters, int acc_steps, const double* lr_sched, const double* lrs, const double* adam,
+                           float lambda_consistency, const int* limb, const int* view_wh, const size_t* gt_offsets, int frames,
+                           const float* const* hm_factors, int* es_state, int es_window, float es_tolerance,
+                           int* es_host_flags, int vw_mode, float vw_threshold, float* vw_weights, float* vw_similarity,
+                           void* stream)
+{
+    StepCall c{};
+    SKS_TAKE_STEP_CALL(c, lr_sched);
+    if (es_state) SKS_TAKE_ES(c.es);
+    SKS_TAKE_VW(c.vw);
+    return loop_fused_step_impl(c);
+}
+
+int sks_loop_fused_step_vw_dv(int V, int P, int C, int W, int H, const float* viewmatrix, const float* projmatrix,
+                              const void* views_dev, const float* features, float scale_modifier, unsigned flags, int* radii,
+                              void* geom, const float* gt, const double* gt_totals, void* accum, double* loss_sums,
+                              float* packed, float* slots, unsigned long long group_mask, int last_view, float* xyz,
+                              float* scaling, float* rotation, float* opacity, float* exp_avg, float* exp_avg_sq, int* counters,
+                              int acc_steps, const double* lr_sched_dev, const double* lrs, const double* adam,
+                              float lambda_consistency, const int* limb, const int* view_wh, const size_t* gt_offsets,
+                              int frames, const float* const* hm_factors, int* es_state, int es_window, float es_tolerance,
+                              int* es_host_flags, int vw_mode, float vw_threshold, float* vw_weights, float* vw_similarity,
+                              void* stream)
+{
+    if (!views_dev || !lr_sched_dev) return fail(-2, "loop_fused_step_vw_dv: views_dev and lr_sched_dev are required");
+    const float *const tanfovx = NO_TAN, *const tanfovy = NO_TAN;
+    StepCall c{};
+    SKS_TAKE_STEP_CALL(c, NO_SCHED);
+    c.views_dev = views_dev, c.lr_sched_dev = lr_sched_dev;
+    if (es_state) SKS_TAKE_ES(c.es);
+    SKS_TAKE_VW(c.vw);
     return loop_fused_step_impl(c);
 }
 

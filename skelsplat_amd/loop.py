@@ -143,6 +143,19 @@ class _GroupLoop(JointSwitches):
     def _after_replay(self):
         pass
 
+    def _init_view_weighting(self, view_weighting, view_threshold):
+        """`view_weighting` = None | "scale" | "select": each view's xyz gradient weighted by its agreement with the others' in the
+        optimiser step (include/skelsplat_hip.h "View agreement").  `view_weights` / `view_similarity`: the last step's, None when off."""
+        from . import _lib
+        self.view_weighting = view_weighting
+        self._vw_mode = _lib.vw_mode(view_weighting)
+        self.view_threshold = float(view_threshold)
+        self.view_weights = self.view_similarity = None
+
+    def _view_weight_args(self):
+        """sparse.loop_fused_step's `view_weights`."""
+        return (self._vw_mode, self.view_threshold, self.view_weights, self.view_similarity) if self._vw_mode else None
+
     def _enqueue(self, iterations, groups_per_graph, graphs=True):
         """run() without its final synchronisation (FramePipeline drives several loops with it).  With use_graph, while every group
         is the same one (all views, acc_steps iterations), G = `groups_per_graph` of them are ONE hipGraph: an eager group warms
@@ -188,15 +201,20 @@ class MultiViewLoop(_GroupLoop):
     the optimiser kernel (sks_loop_adam_step_es): no loss is read back, the group stays a fixed launch sequence (use_graph works,
     view-sharded ranks decide identically from the gathered sums -- they ride in the step's one all_gather), and the host learns
     the stopping iteration from a pinned flag it polls without waiting (run() synchronises once, at its end).  Any other
-    callable is a host decision: one read-back per group, no use_graph."""
+    callable is a host decision: one read-back per group, no use_graph.
+    `view_weighting`: None (the reference's plain mean of the V slots), "scale" or "select": each view's xyz gradient is weighted
+    per joint by its agreement with the other views' (utils/similarity_utils.py; DESIGN.md "View agreement"), inside the step's own
+    launch on the device tail and by the same definition in tensor ops on the host tail; `view_threshold`: select's cosine
+    threshold.  `view_weights` (V,P) and `view_similarity` (P,V,V) hold the last step's."""
 
     def __init__(self, gaussians, cameras, heatmaps, dataset="h36m", accumulation_steps=4, lambda_consistency=1e-5,
                  bg=None, antialiasing=False, loss_grad=None, group=None, view_grad_fn=None, device_tail=None,
                  use_graph=False, sparse=None, fused_tail=None, shard_views=True, graph_collectives=None,
-                 early_stopping="no_stopping", rigs=None):
+                 early_stopping="no_stopping", rigs=None, view_weighting=None, view_threshold=0.5):
         self.gm = gaussians
         self.dataset = dataset
         self.V = len(cameras)
+        self._init_view_weighting(view_weighting, view_threshold)
         self.acc_steps = int(accumulation_steps)
         self.lambda_consistency = float(lambda_consistency)
         self.antialiasing = antialiasing
@@ -336,6 +354,9 @@ class MultiViewLoop(_GroupLoop):
         self.exp_avg = torch.zeros((P, 11), device=dev)
         self.exp_avg_sq = torch.zeros((P, 11), device=dev)
         self.counters = torch.zeros(2, dtype=torch.int32, device=dev)
+        if self._vw_mode:       # the step's own launch writes them (persistent: a captured graph keeps their addresses)
+            self.view_weights = torch.zeros((self.V, P), device=dev)
+            self.view_similarity = torch.zeros((P, self.V, self.V), device=dev)
         self._es_state = self._es_flag = None
         if self._es_device:
             w = self.early_stopping.window_size
@@ -626,6 +647,11 @@ class MultiViewLoop(_GroupLoop):
             step, what = lib.sks_loop_adam_step_es, "sks_loop_adam_step_es"
             args += (None if world > 1 else self._sums.data_ptr(), self._es_state.data_ptr(), int(es.window_size),
                      float(es.repeat_tolerance), self._es_flag.data_ptr())
+        if self._vw_mode:       # (one entry for both forms: es_state == NULL is the step without a criterion)
+            if not self._es_device:
+                args += (None, None, 0, 0.0, None)
+            step, what = lib.sks_loop_adam_step_vw, "sks_loop_adam_step_vw"
+            args += (self._vw_mode, self.view_threshold, self.view_weights.data_ptr(), self.view_similarity.data_ptr())
         _lib.check(step(*args, stream), what)
 
     def _optimiser_block(self, group_mask, last_view, n_iters):
@@ -645,7 +671,7 @@ class MultiViewLoop(_GroupLoop):
                     self._geom_valid = True
                 packed, sums = self._fbuf
                 R.loop_fused_step(self._fstate, self.stats_all, feats, packed, sums,
-                                  *self._optimiser_block(group_mask, last_view, n_iters))
+                                  *self._optimiser_block(group_mask, last_view, n_iters), view_weights=self._view_weight_args())
                 self.last_losses = (sums[:, 0], sums[:, 1])
                 return
             if self.local_ids:
@@ -786,7 +812,12 @@ class MultiViewLoop(_GroupLoop):
         gm._scaling.grad = full[last, :, 3:6].contiguous()
         gm._rotation.grad = full[last, :, 6:10].contiguous()
         gm._opacity.grad = full[last, :, 10:11].contiguous()
-        gm._xyz.grad = self.accumulated_grads.mean(dim=0)                  # train.py:215-218
+        if self._vw_mode:                                                  # the same definition as the device tail's, in tensor ops
+            from .view_agreement import weighted_mean
+            gm._xyz.grad, self.view_weights, self.view_similarity = weighted_mean(self.accumulated_grads, self.view_weighting,
+                                                                                   self.view_threshold)
+        else:
+            gm._xyz.grad = self.accumulated_grads.mean(dim=0)              # train.py:215-218
         gm.update_learning_rate(grp.end)                                   # quirk Q9: schedule indexed by iteration
         with torch.no_grad():
             gm.optimizer.step()
@@ -865,13 +896,18 @@ class FrameBatchLoop(_GroupLoop, SequenceSwitches):
 
     `keep_gaussians=True`: `optimize_sequence` keeps every frame's scaling, rotation and opacity next to its joints
     (`self.gaussians`, an uncertainty.SequenceGaussians) -- the Gaussian per joint the reference saves per scene, and what
-    skelsplat_amd/uncertainty.py reads back as the pose's uncertainty.  Off (default): nothing is allocated or enqueued for it."""
+    skelsplat_amd/uncertainty.py reads back as the pose's uncertainty.  Off (default): nothing is allocated or enqueued for it.
+
+    `view_weighting` / `view_threshold`: as MultiViewLoop's, per frame, inside the fused step's tail (sks_loop_fused_step_vw);
+    `view_weights` (F,V,P) and `view_similarity` (F,P,V,V) hold each frame's last step's.  A frame's trajectory stays bit-identical
+    to a MultiViewLoop with the same keyword running it alone."""
 
     def __init__(self, gaussians, cameras=None, frames=None, dataset="h36m", accumulation_steps=4, lambda_consistency=1e-5,
                  antialiasing=False, use_graph=False, factored=True, early_stopping="no_stopping", rigs=None, report_steps=0,
-                 save_iterations=(), keep_gaussians=False):
+                 save_iterations=(), keep_gaussians=False, view_weighting=None, view_threshold=0.5):
         from .report import check_report_args
         check_report_args(report_steps, save_iterations)
+        self._init_view_weighting(view_weighting, view_threshold)
         if (cameras is None) == (rigs is None):
             raise ValueError("FrameBatchLoop takes either cameras= (one rig for all frames) or rigs= (a RigBank)")
         if frames is None:
@@ -909,6 +945,9 @@ class FrameBatchLoop(_GroupLoop, SequenceSwitches):
         self.exp_avg_sq = torch.zeros((F, P, 11), device=dev)
         self.counters = torch.zeros((F, 2), dtype=torch.int32, device=dev)
         self.accumulated_grads = torch.zeros((F, V, P, 3), device=dev)    # train.py:121, one V-slot buffer per frame
+        if self._vw_mode:       # each frame's weights and cosines of its last step (a stopped frame's rows stay as its last step left them)
+            self.view_weights = torch.zeros((F, V, P), device=dev)
+            self.view_similarity = torch.zeros((F, P, V, V), device=dev)
         # per-frame early stopping on the device: (window, tolerance) or None; the state of every frame's criterion (the
         # layout of sks_loop_adam_step_es's, one row per frame) and the pinned flags the tail writes the stopping iteration to
         self._es = _frame_criterion(early_stopping)
@@ -960,6 +999,7 @@ class FrameBatchLoop(_GroupLoop, SequenceSwitches):
         self.inliers = torch.ones((F, V, self.P), dtype=torch.bool, device=dev)
         self.n_consensus = torch.zeros((F, self.P), dtype=torch.int32, device=dev)
         self.seq_inliers = self.seq_n_consensus = None     # optimize_sequence with rejection: the same for its N frames
+        self.seq_view_weights = None                       # optimize_sequence with view weighting: (N,V,P) final weights
         sizes = [(int(c.image_width), int(c.image_height)) for c in cams_all]
         # factored (default): the pseudo-GT stays in its separable form (rasterizer.HeatmapFactors) -- the fused step
         # evaluates the pixels it needs, the per-view loss constants come from the factors (sks_heatmap_totals), and no
@@ -1124,6 +1164,14 @@ class FrameBatchLoop(_GroupLoop, SequenceSwitches):
         return (self.accumulated_grads, group_mask, last_view, self.xyz, self.scaling, self.rotation, self.opacity, self.exp_avg,
                 self.exp_avg_sq, self.counters, n_iters, self._sched, self._lrs, self._adam, self.lambda_consistency, self._limb)
 
+    def _set_view_weighting(self, mode, threshold):
+        """set_view_weighting for this loop: the step's entry point changes, so the captured graphs go."""
+        self._init_view_weighting(mode, threshold)
+        if self._vw_mode:
+            self.view_weights = torch.zeros((self.F, self.V, self.P), device=self.device)
+            self.view_similarity = torch.zeros((self.F, self.P, self.V, self.V), device=self.device)
+        self._graph = self._multi = None
+
     def _device_group(self, group_mask, last_view, n_iters):
         with torch.no_grad():
             if not self._geom_valid:
@@ -1134,7 +1182,7 @@ class FrameBatchLoop(_GroupLoop, SequenceSwitches):
             es = {} if self._es is None else dict(es_state=self._es_state, es_window=self._es[0], es_tolerance=self._es[1],
                                                   es_flags=self._es_flags)
             R.loop_fused_step(self._fstate, self.stats_all, self.features, self._packed, self._sums,
-                              *self._optimiser_block(group_mask, last_view, n_iters), **es)
+                              *self._optimiser_block(group_mask, last_view, n_iters), **es, view_weights=self._view_weight_args())
             if self._report is not None:
                 self._report.launch(self)
         s = self._sums.view(self.F, self.V, 2)
@@ -1276,6 +1324,7 @@ class FramePipeline(SequenceSwitches):
         self.inliers = self.n_consensus = None     # optimize_sequence with rejection: (N,V,J) bool, (N,J) int32
         self.reprojection = None     # set_reprojection_report: reprojection.SequenceReprojection of the last optimize_sequence
         self.smoothed = None         # set_smoothing: smoothing.Smoothed of the last optimize_sequence
+        self.view_weights = None     # view weighting on: (N,V,P) final weights of the last optimize_sequence
 
     def _driven(self):
         return self.loops       # (the switches set every loop: JointSwitches, SequenceSwitches)

@@ -1,5 +1,7 @@
 """The sparse fused training step (sks_gt_tile_stats / sks_geometry / sks_backward_fused_loss / sks_loop_fused_step): the geometry
 stage alone, and render + clamp + masked L2 + backward on the tiles the Gaussians cover -- no dense image is written."""
+import math
+
 import torch
 
 from . import _lib
@@ -213,7 +215,7 @@ def _check_heatmaps(views, C, stats):
 
 def loop_fused_step(st: ForwardState, stats: GtStats, features, packed, sums, slots, group_mask, last_view, xyz, scaling,
                     rotation, opacity, exp_avg, exp_avg_sq, counters, acc_steps, lr_sched, lrs, adam, lambda_consistency, limb,
-                    es_state=None, es_window=0, es_tolerance=0.0, es_flags=None):
+                    es_state=None, es_window=0, es_tolerance=0.0, es_flags=None, view_weights=None):
     """sks_loop_fused_step: fused-loss compositing backward + (geometry backward, Adam step, geometry forward of the
     updated parameters) for one accumulation group; `st` must describe the current parameters and is left describing the
     updated ones.  lr_sched / lrs / adam / limb: ctypes arrays as for sks_loop_adam_step.  A state made with
@@ -221,7 +223,10 @@ def loop_fused_step(st: ForwardState, stats: GtStats, features, packed, sums, sl
     es_state: (F, 2 + 2 * es_window) int32 device tensor -> sks_loop_fused_step_es, the reference's opt_early_stopping per
     frame on the device (es_flags: (F,) pinned int32 host tensor that receives each frame's stopping iteration, or None).
     Views with a device `table` (a frame batch over a rig bank): `lr_sched` is the (frames,5) float64 DEVICE tensor of per-frame
-    schedule rows and the step goes through sks_loop_fused_step_dv / _es_dv."""
+    schedule rows and the step goes through sks_loop_fused_step_dv / _es_dv.
+    view_weights: None, or (vw_mode 1 | 2, threshold, weights (F,Vf,P) float32 or None, similarity (F,P,Vf,Vf) float32 or None) ->
+    sks_loop_fused_step_vw / _vw_dv: the views weighted by their agreement (include/skelsplat_hip.h "View agreement"), with or
+    without the criterion."""
     lib = _lib.load()
     dev = xyz.device
     V, P, C = st.views.V, st.P, st.C
@@ -250,20 +255,40 @@ def loop_fused_step(st: ForwardState, stats: GtStats, features, packed, sums, sl
             opacity.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), counters.data_ptr(), acc_steps, lr_sched, lrs,
             adam, float(lambda_consistency), limb, st.views.wh, stats.offsets, st.frames,
             None if stats.factors is None else stats.factors.ptrs)
-    if es_state is None:
+    if es_state is None and view_weights is None:
         with torch.cuda.device(dev):
             rc = step(*args, stream)
         _lib.check(rc, "sks_loop_fused_step")
         return
+    if es_state is None:
+        es = (None, 0, 0.0, None)
+    else:
+        es = _es_args(st, dev, es_state, es_window, es_tolerance, es_flags)
+    if view_weights is not None:
+        mode, threshold, weights, similarity = view_weights
+        Vf = V // st.frames
+        for name, t, shape in (("weights", weights, (st.frames, Vf, P)), ("similarity", similarity, (st.frames, P, Vf, Vf))):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != math.prod(shape)):
+                raise ValueError(f"view_weights: {name} must be a contiguous float32 {shape} tensor on {dev}")
+        with torch.cuda.device(dev):
+            rc = (lib.sks_loop_fused_step_vw_dv if dv else lib.sks_loop_fused_step_vw)(
+                *args, *es, int(mode), float(threshold), None if weights is None else weights.data_ptr(),
+                None if similarity is None else similarity.data_ptr(), stream)
+        _lib.check(rc, "sks_loop_fused_step_vw")
+        return
+    with torch.cuda.device(dev):
+        rc = step_es(*args, *es, stream)
+    _lib.check(rc, "sks_loop_fused_step_es")
+
+
+def _es_args(st, dev, es_state, es_window, es_tolerance, es_flags):
+    """The criterion's four arguments of the fused step's early-stopping forms, checked."""
     if es_state.dtype != torch.int32 or not es_state.is_contiguous() or es_state.device != dev \
             or tuple(es_state.shape) != (st.frames, 2 + 2 * int(es_window)):
         raise ValueError(f"es_state must be a contiguous int32 ({st.frames}, {2 + 2 * int(es_window)}) tensor on {dev}")
     if es_flags is not None and (es_flags.dtype != torch.int32 or es_flags.numel() != st.frames or es_flags.device.type != "cpu"):
         raise ValueError(f"es_flags must be a pinned int32 host tensor of {st.frames} ints")
-    with torch.cuda.device(dev):
-        rc = step_es(*args, es_state.data_ptr(), int(es_window), float(es_tolerance),
-                     None if es_flags is None else es_flags.data_ptr(), stream)
-    _lib.check(rc, "sks_loop_fused_step_es")
+    return (es_state.data_ptr(), int(es_window), float(es_tolerance), None if es_flags is None else es_flags.data_ptr())
 
 
 def backward_fused_loss(st: ForwardState, stats: GtStats, means3D, features, opacities, scales, rotations, cov3D_precomp,
