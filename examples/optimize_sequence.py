@@ -4,7 +4,8 @@ other, train.py:74-99) -- but many frames per launch: noisy 2D detections of N f
 iterations of the multi-view loop for every frame (loop.FramePipeline) -> MPJPE per frame.
 python examples/optimize_sequence.py [--frames 64] [--per-launch 16] [--streams 2] [--iters 500] [--init host|device|fuse] [--rigs R]
     [--report] [--uncertainty] [--reject-px PX] [--corrupt K] [--refine [--huber-px D]] [--images DIR [--image-frames 0,31,63]]
-    [--smooth H [--smooth-degree D]] [--motion wobble|smooth] [--view-weights scale|select [--view-threshold T]]
+    [--smooth H [--smooth-degree D]] [--motion wobble|smooth|articulated] [--view-weights scale|select [--view-threshold T]]
+    [--bones [--bones-symmetric]]
 --view-weights scale|select [--view-threshold T]: the optimiser step of every frame weights each view's joint gradient by its
 agreement with the other views' (pipe.set_view_weighting; DESIGN.md "View agreement"; T: select's cosine threshold, default 0.5).
 With --report: each view's mean final weight, and with --corrupt the mean weight of the corrupted (view, joint) detections
@@ -47,6 +48,17 @@ with --uncertainty for both weightings, next to the calibration table that says 
 --motion smooth: the skeleton moves on low-frequency sinusoids per joint instead of the default `wobble`, whose ground truth jumps
 independently by 5 mm per frame -- a signal no temporal filter can beat.  What the covariance weights gain on real sequences has not
 been measured.
+--motion articulated: ground truth that keeps its bone lengths -- forward kinematics over the dataset's skeleton tree
+(scene.articulated_motion): every bone has the template's length and its direction turns on low-frequency sinusoids, the drift is
+the other motions'.  `wobble` and `smooth` move every joint on its own, so THEIR ground truth has no constant lengths.
+--bones [--bones-symmetric] (with --report's ground truth): the sequence is held to constant limb lengths on the device once it is
+through (pipe.set_bone_constraint, skelsplat_amd/skeleton.py): the median length of every bone of the dataset's tree over the
+sequence, then every frame projected onto those lengths -- under the covariance of its optimised Gaussians with --uncertainty,
+else under the identity; after --smooth, the smoothed joints under the fit's covariance.  --bones-symmetric makes left and right
+arms and legs equal first.  Printed: per bone the median and the MAD of the optimised sequence, the largest relative MAD before and
+after the constraint, and MPJPE, PA-MPJPE and Accel of the constrained joints.  The constraint reaches A pose on the lengths by
+successive covariance-closest projections, not the closest one; on `wobble` and `smooth` it holds the poses to lengths their ground
+truth does not keep and must not be expected to help.  What it gains on real sequences has not been measured.
 The curve falls from the reference's default start, --init fuse (21.7 -> 14.3 mm); from the DLT start (--init host / device) it
 RISES from 13.4 to 14.3 mm in the first steps: on this synthetic sequence (3 px of detection noise, exact cameras) the DLT already
 sits below the optimiser's fixed point, and the curve shows it."""
@@ -85,7 +97,9 @@ def main(argv=None):
     ap.add_argument("--image-frames", default=None, metavar="I,J,..")
     ap.add_argument("--smooth", type=int, default=None, metavar="H")
     ap.add_argument("--smooth-degree", type=int, default=2, metavar="D")
-    ap.add_argument("--motion", choices=("wobble", "smooth"), default="wobble")
+    ap.add_argument("--motion", choices=("wobble", "smooth", "articulated"), default="wobble")
+    ap.add_argument("--bones", action="store_true")
+    ap.add_argument("--bones-symmetric", action="store_true")
     ap.add_argument("--view-weights", choices=("scale", "select"), default=None)
     ap.add_argument("--view-threshold", type=float, default=None, metavar="T")
     args = ap.parse_args(argv)
@@ -98,6 +112,9 @@ def main(argv=None):
     if args.motion == "wobble":
         gt = np.stack([sc.pose_3d_gt + np.array([8.0 * f, 3.0 * f, 0.0]) + rng.normal(0, 5.0, sc.pose_3d_gt.shape)
                        for f in range(args.frames)])
+    elif args.motion == "articulated":      # the same drift; bones of constant length whose directions turn on sinusoids
+        from skelsplat_amd.scene import articulated_motion
+        gt = articulated_motion(args.dataset, args.frames, sc.pose_3d_gt)
     else:       # the same drift, and per joint and coordinate a sinusoid of 20-60 mm with a period of 25-100 frames
         mrng = np.random.default_rng(2)
         amp, period, phase = (mrng.uniform(lo, hi, sc.pose_3d_gt.shape) for lo, hi in ((20.0, 60.0), (25.0, 100.0), (0.0, 2.0 * np.pi)))
@@ -117,6 +134,10 @@ def main(argv=None):
         ap.error("--uncertainty measures against --report's ground truth: use the two together")
     if args.smooth is not None and not args.report:
         ap.error("--smooth prints its errors against --report's ground truth: use the two together")
+    if args.bones and not args.report:
+        ap.error("--bones prints its errors against --report's ground truth: use the two together")
+    if args.bones_symmetric and not args.bones:
+        ap.error("--bones-symmetric is an option of --bones")
     if args.reject_px is not None and args.init != "device":
         ap.error("--reject-px rejects while triangulating on the device: use it with --init device")
     if args.refine and args.init != "device":
@@ -164,6 +185,9 @@ def main(argv=None):
             return pipe.optimize_sequence(init, p2d, iterations=args.iters, **ids), init
     if args.smooth is not None:
         pipe.set_smoothing(args.smooth, degree=args.smooth_degree, use_covariance=args.uncertainty)
+    if args.bones:
+        pipe.set_bone_constraint("dataset", use_covariance=args.uncertainty or args.smooth is not None,
+                                 symmetric=args.bones_symmetric)
     if args.view_weights is not None:
         pipe.set_view_weighting(args.view_weights, 0.5 if args.view_threshold is None else args.view_threshold)
     if args.report:
@@ -254,6 +278,32 @@ def main(argv=None):
             acc = sequence_accel(x, gt_dev)
             print(f"  {name:30s} MPJPE {float(evaluate_sequence(x, gt_dev)['abs']):7.3f} mm   Accel {float(acc['accel']):7.3f}   "
                   f"Accel error {float(acc['accel_error']):7.3f}  (mm per frame^2)")
+    if args.bones:
+        from skelsplat_amd import skeleton
+        from skelsplat_amd.report import evaluate_sequence, evaluate_sequence_aligned
+        from skelsplat_amd.scene import DATASETS
+        from skelsplat_amd.smoothing import sequence_accel
+        bl, con = pipe.bone_lengths, pipe.constrained
+        after = skeleton.bone_lengths(con.joints, DATASETS[args.dataset]["bones"])
+        truth = skeleton.bone_lengths(gt_dev, DATASETS[args.dataset]["bones"])
+        src = "smoothed" if args.smooth is not None else "optimised"
+        print(f"constant limb lengths ({args.motion} motion), the {src} joints under "
+              + ("their covariance" if args.uncertainty or args.smooth is not None else "the identity")
+              + (", left and right limbs made equal" if args.bones_symmetric else "") + ":")
+        print("  bone (parent, child)   median      MAD   frames   ground truth's median")
+        for i, (p, c) in enumerate(DATASETS[args.dataset]["bones"]):
+            print(f"  {p:6d} {c:6d} {float(bl.length[0, i]):14.2f} {float(bl.mad[0, i]):8.3f} {int(bl.n_used[0, i]):8d} "
+                  f"{float(truth.length[0, i]):14.2f}")
+        rel = lambda b: float((b.mad / b.length).max())
+        print(f"  largest MAD / median over the bones: {rel(bl):.5f} before -> {rel(after):.2e} after the constraint "
+              f"(ground truth: {rel(truth):.2e}); trips per frame: mean {float(con.n_trips.double().mean()):.2f}, "
+              f"max {int(con.n_trips.max())}; frames with residual > 1e-3 mm: {int((~(con.residual <= 1e-3)).sum())}")
+        base = pipe.smoothed.joints if args.smooth is not None else out
+        for name, x in ((src, base), ("constrained", con.joints)):
+            acc = sequence_accel(x, gt_dev)
+            print(f"  {name:12s} MPJPE {float(evaluate_sequence(x, gt_dev)['abs']):7.3f} mm   PA-MPJPE "
+                  f"{float(evaluate_sequence_aligned(x, gt_dev)['pa_mpjpe']):7.3f} mm   Accel {float(acc['accel']):7.3f}   "
+                  f"Accel error {float(acc['accel_error']):7.3f}")
     if args.uncertainty:
         from skelsplat_amd.uncertainty import calibration
         unc = pipe.gaussians.uncertainty(gt_dev)
@@ -267,6 +317,8 @@ def main(argv=None):
     res = dict(joints=out, gt=gt_dev, activities=acts, aligned=eva) if args.report else None
     if args.smooth is not None:
         res["smoothed"] = pipe.smoothed
+    if args.bones:
+        res["bone_lengths"], res["constrained"] = pipe.bone_lengths, pipe.constrained
     return res
 
 

@@ -548,6 +548,95 @@ int sks_smooth_sequence(int N, int J, const float* xyz, const float* cov6, const
 int sks_smooth_launch(int N, int J, int half_window, int* out /*HOST SKS_SMOOTH_LAUNCH_INTS*/);
 int sks_eval_accel(int N, int J, const float* xyz, const float* gt, const int* group_ids, int n_groups, double* out, void* stream);
 
+/* Constant limb lengths over a sequence (csrc/sks_bones.hip; added to sks_version 14: the number did not move).  The reference
+ * optimises every frame on its own and knows the skeleton only through the left/right symmetry prior of its loss; this is what a
+ * consumer of its poses runs afterwards: measure every bone in every frame, take a recording's median lengths, and move every
+ * frame onto them with each joint's optimised 3x3 covariance (sks_joint_uncertainty's cov6, or the smoothing's) saying which end
+ * of a wrong bone moves, and where to.  WHAT THE FIT IS: a pose that meets the lengths, reached by successive Sigma-closest
+ * projections onto the linearised constraints.  It is NOT the Sigma-closest feasible pose (that needs the constraints' curvature
+ * and a (3J+B)-sized KKT solve; MEASUREMENTS.md "Constant limb lengths" says how far above it the cost ends), and no covariance
+ * of the projected pose is given.  What it gains on real sequences has NOT been measured.  One launch each on `stream`, nothing
+ * synchronises, no floating-point atomics, no scratch.  Device memory unless marked HOST.
+ *
+ * COMMON.  bones: HOST (B,2) ints, (parent, child) joint of bone b; 2 <= J <= SKS_BONES_MAX_JOINTS, 1 <= B <=
+ * SKS_BONES_MAX_JOINTS - 1, every index in 0 .. J-1, and the bones must form a FOREST (no cycle, which also rules out a bone from
+ * a joint to itself and a repeated pair): checked on the host with a union-find over the bones in index order and refused
+ * otherwise -- with it A has full row rank and S below is positive definite.  1 <= N <= 2^26.  groups: (N) ints, the recording of
+ * every frame, with 1 <= n_groups <= SKS_BONES_MAX_GROUPS, or NULL with n_groups = 1 (one group, id 0); a frame whose id lies
+ * outside 0 .. n_groups-1 enters no group's statistic and is copied by the projection.  An END (a joint of a frame) is USABLE when
+ * its three floats are finite and valid[f,j] != 0 (valid (N,J) bytes, optional).  All arithmetic below is IEEE float64, one rounding
+ * per operation, no fused multiply-add.  For a symmetric 3x3 M = {xx, xy, xz, yy, yz, zz} and 3-vectors a, b:
+ *     M b = w with w_r = (M_r0 * b_0 + M_r1 * b_1) + M_r2 * b_2;      a^T M b = (a_0 * w_0 + a_1 * w_1) + a_2 * w_2.
+ *
+ * sks_bone_measure: measured (N,B) floats.  Per (frame f, bone b = (p, c)), coordinates widened to float64:
+ *     d_k = x_c,k - x_p,k (k = x, y, z);  n = sqrt((d_0 * d_0 + d_1 * d_1) + d_2 * d_2);  measured[f,b] = (float)n.
+ *   NaN when an end is not usable.  With cov6 ((N,J,6) floats; then max_sigma_mm must be finite and >= 0): u_k = d_k / n,
+ *   Sigma = cov6[f,p] + cov6[f,c] entry by entry (widened), var = u^T Sigma u as above, and the measure is NaN unless
+ *   var <= max_sigma_mm * max_sigma_mm (a NaN variance -- a non-finite covariance, n = 0 -- leaves the frame out).  cov6 NULL: no
+ *   gate, max_sigma_mm is not read.  One lane per (frame, bone).
+ * sks_bone_lengths: per (group g, bone b) the lower median and the MAD of the group's measures.  A measure is USABLE when it is
+ *   finite and its sign bit is clear (sks_bone_measure writes nothing else except NaN and, on float overflow, +inf).  With n
+ *   usable measures in the group and k = (n - 1) / 2 (integer division): length[g,b] = the k-th smallest (0-based) of them;
+ *   mad[g,b] = the k-th smallest of |l - length[g,b]| over the same measures, the subtraction and the absolute value in FLOAT32;
+ *   n_used[g,b] = n.  n = 0: NaN, NaN, 0.  Both are SELECTED by integer counts (an MSB-first radix select over the bit patterns,
+ *   eight bits a pass, a 256-bin histogram in LDS filled by integer atomics; one workgroup of 256 threads per (group, bone), a
+ *   group longer than 256 frames takes several trips per pass), so each is one of the inputs resp. one of the float32 deviations,
+ *   exactly, whatever the order the frames are counted in.  length, mad (n_groups,B) floats, n_used (n_groups,B) ints.
+ * sks_bone_project: per frame, from its joints y (widened) and the lengths L_b = (double)lengths[g,b] of its group g, the iterate
+ *   x starts at y.  Sigma_j = the identity without cov6, else cov6[f,j] widened with cov_floor (finite, >= 0, mm^2) added to xx,
+ *   yy, zz.  A joint is FIT when it is usable and, with cov6, its six entries of Sigma_j are finite and the three pivots of
+ *   Sigma_j's LDL^T (sks_smooth_sequence's sequence above: d0, l10, l20, d1, e, z1, l21, d2) are finite and > 0.  Bone b is
+ *   ACTIVE when both ends are fit, L_b is finite and > 0 and its frame's group id is in range; it turns inactive for the rest of
+ *   the frame at the first trip that finds n_b == 0.  One TRIP, at most max_iters (1 .. SKS_BONES_MAX_ITERS) of them:
+ *     1. per active bone b = (p, c):  d = x_c - x_p;  n_b = sqrt((d_0 * d_0 + d_1 * d_1) + d_2 * d_2);  n_b == 0: inactive, else
+ *        u_b = d / n_b (three divisions) and r_b = n_b - L_b.  rho = the largest of |r_b| over the active bones (+inf for an
+ *        r_b that is not finite), n_active = their number.  n_active == 0: the frame ENDS and keeps the rho of the trip before (NaN at the first).
+ *        rho <= tol_mm (finite, >= 0) or max_iters trips done: the frame ENDS.  This test is the same in every lane of the
+ *        wavefront.
+ *     2. S (B x B, lower triangle): for a >= b, both active, starting from s = 0 and in this order:  if p_a == p_b:
+ *        s = s + u_a^T Sigma_(p_a) u_b;  if p_a == c_b: s = s - u_a^T Sigma_(p_a) u_b;  if c_a == p_b: s = s - u_a^T Sigma_(c_a) u_b;
+ *        if c_a == c_b: s = s + u_a^T Sigma_(c_a) u_b  (row a of A holds +u_a at c_a and -u_a at p_a; the diagonal is the same
+ *        rule with a == b).  An inactive bone's row and column are the identity's (1 on the diagonal, 0 elsewhere) and its
+ *        right-hand side is 0; y_b = r_b for an active one.
+ *     3. LDL^T of S in place on the lower triangle with the right-hand side, then the two substitutions: sks_smooth_sequence's
+ *        three loops above with m = B.  A pivot S[j][j] that is not finite and > 0 when step j reads it ENDS the frame at the
+ *        current x (it cannot happen in exact arithmetic).  lambda = y.
+ *     4. per joint j, g = (0, 0, 0), then over the ACTIVE bones b = 0 .. B-1 in index order:  if c_b == j: g_k = g_k + lambda_b *
+ *        u_b,k;  if p_b == j: g_k = g_k - lambda_b * u_b,k.  A joint no active bone touches is left alone; any other:
+ *        x_j,k = x_j,k - ((Sigma_j,k0 * g_0 + Sigma_j,k1 * g_1) + Sigma_j,k2 * g_2).
+ *   This is x <- x - Sigma A^T (A Sigma A^T)^-1 (n(x) - L): the Sigma-metric closest point to x on the constraints linearised at
+ *   x.  (The trip that re-solves from y each time is the textbook SQP step without curvature; it does not converge once the
+ *   covariances are needles: DESIGN.md "Constant limb lengths".)  Outputs: out_xyz (N,J,3) floats, must not overlap xyz: a joint
+ *   that step 4 moved at least once is (float)x_j, every other joint is its input BIT FOR BIT (NaN payloads included; DESIGN.md
+ *   "Unobserved joints"), so a frame with no active bone is a copy; residual (N) floats = (float) of the last rho computed, NaN when no
+ *   bone was ever active; n_trips (N) ints = the trips that moved the frame (0 .. max_iters); n_active (N) ints at the
+ *   end.  A frame CONVERGED when residual <= tol_mm.  A bone that turns inactive at a trip after the first has already moved its
+ *   ends: the bit-for-bit promise holds for joints whose bones were inactive from the start, the only case input data can reach
+ *   by construction (coincident joints, NaN, masks, bad covariances, bad lengths).  One wavefront (a workgroup of 64 threads)
+ *   per frame; x, Sigma, u, S and y live in LDS; lane b owns bone b and row b, lane j joint j.
+ * sks_bones_launch: HOST only, no GPU call: the workgroups, threads per workgroup and LDS bytes per workgroup of the three launches
+ *   for a call of this N, J, B and n_groups, at the SKS_BONES_* indices below (the measure uses no LDS). */
+#define SKS_BONES_MAX_JOINTS   32
+#define SKS_BONES_MAX_GROUPS   256
+#define SKS_BONES_MAX_ITERS    16
+#define SKS_BONES_MEASURE_GROUPS     0
+#define SKS_BONES_MEASURE_THREADS    1
+#define SKS_BONES_LENGTHS_GROUPS     2
+#define SKS_BONES_LENGTHS_THREADS    3
+#define SKS_BONES_LENGTHS_LDS_BYTES  4
+#define SKS_BONES_PROJECT_GROUPS     5
+#define SKS_BONES_PROJECT_THREADS    6
+#define SKS_BONES_PROJECT_LDS_BYTES  7
+#define SKS_BONES_LAUNCH_INTS        8
+int sks_bone_measure(int N, int J, int B, const int* bones /*HOST (B,2)*/, const float* xyz, const float* cov6,
+                     const unsigned char* valid, double max_sigma_mm, float* measured, void* stream);
+int sks_bone_lengths(int N, int B, const float* measured, const int* groups, int n_groups, float* length, float* mad, int* n_used,
+                     void* stream);
+int sks_bone_project(int N, int J, int B, const int* bones /*HOST (B,2)*/, const float* xyz, const float* cov6,
+                     const unsigned char* valid, const int* groups, int n_groups, const float* lengths, double cov_floor,
+                     int max_iters, double tol_mm, float* out_xyz, float* residual, int* n_trips, int* n_active, void* stream);
+int sks_bones_launch(int N, int J, int B, int n_groups, int* out /*HOST SKS_BONES_LAUNCH_INTS*/);
+
 /* Replaces fusedssim (submodules/fused-ssim/ssim.cu:368-404, binding ext.cpp): img1, img2, ssim_map and the three
  * optional partial-derivative maps (train == true) are (B,CH,H,W) fp32; "same" zero padding. */
 int sks_fused_ssim_fwd(int B, int CH, int H, int W, float C1, float C2, const float* img1, const float* img2,

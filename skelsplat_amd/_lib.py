@@ -34,6 +34,10 @@ SKS_SMOOTH_MAX_JOINTS = 256
 SKS_SMOOTH_MAX_HALF_WINDOW = 32
 SKS_SMOOTH_BOX, SKS_SMOOTH_TRICUBE = 0, 1
 SKS_SMOOTH_LAUNCH_INTS = 4
+SKS_BONES_MAX_JOINTS = 32
+SKS_BONES_MAX_GROUPS = 256
+SKS_BONES_MAX_ITERS = 16
+SKS_BONES_LAUNCH_INTS = 8
 SKS_ALIGN_RIGID, SKS_ALIGN_SIMILARITY, SKS_ALIGN_SCALE = 0, 1, 2
 SKS_PREVIEW_LAUNCH_INTS = 4
 SKS_HEATMAP_MAX_RADIUS = 1 << 18     # a truncation radius beyond it draws no impulse (sks_heatmap_factors, DESIGN.md "Degenerate footprints")
@@ -194,6 +198,10 @@ SIGNATURES = {
     "sks_smooth_sequence": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "sks_smooth_launch": (_i, [_i, _i, _i, _vp]),
     "sks_eval_accel": (_i, [_i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "sks_bone_measure": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp]),
+    "sks_bone_lengths": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "sks_bone_project": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, C.c_double, _i, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "sks_bones_launch": (_i, [_i, _i, _i, _i, _vp]),
     **{name: (_i, [ct for _, ct in params]) for name, params in {**STEP_PARAMS, **DV_PARAMS, **VW_STEP_PARAMS}.items()},
     "sks_pose_errors": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "sks_loop_report": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
@@ -323,6 +331,20 @@ def smooth_launch(N, J, half_window):
     out = (_i * SKS_SMOOTH_LAUNCH_INTS)()
     check(load().sks_smooth_launch(N, J, half_window, C.cast(out, _vp)), "sks_smooth_launch")
     return {name: out[i] for i, name in enumerate(SMOOTH_LAUNCH_FIELDS)}
+
+
+# sks_bones_launch's record: field name -> index (include/skelsplat_hip.h, SKS_BONES_*)
+BONES_LAUNCH_FIELDS = ("measure_groups", "measure_threads", "lengths_groups", "lengths_threads", "lengths_lds_bytes",
+                       "project_groups", "project_threads", "project_lds_bytes")
+
+
+def bones_launch(N, J, B, n_groups=1):
+    """The three launches of sks_bone_measure / sks_bone_lengths / sks_bone_project for N frames of J joints, B bones and
+    n_groups recordings, as a dict over BONES_LAUNCH_FIELDS: workgroups, threads per workgroup and a workgroup's LDS bytes (host
+    only: sks_bones_launch)."""
+    out = (_i * SKS_BONES_LAUNCH_INTS)()
+    check(load().sks_bones_launch(N, J, B, n_groups, C.cast(out, _vp)), "sks_bones_launch")
+    return {name: out[i] for i, name in enumerate(BONES_LAUNCH_FIELDS)}
 
 
 def prefill_planes(V, P, C_, W, H, flags=0):

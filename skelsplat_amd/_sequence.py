@@ -175,6 +175,65 @@ def _sequence_smoothing(loop, N, who):
     return s
 
 
+def _bone_constraint(loop, bones, use_covariance, cov_floor, symmetric, groups, max_sigma_mm, max_iters):
+    """set_bone_constraint's arguments -> None (off) or the checked settings as a dict; `groups` stays as given until a
+    sequence's length is known (_sequence_bones).  `pairs`: the (left, right) bone indices made equal, or None."""
+    if bones is None:
+        return None
+    from . import skeleton
+    from .scene import DATASETS
+    who = "set_bone_constraint"
+    d = DATASETS.get(loop.dataset)
+    if isinstance(bones, str):
+        if bones != "dataset" or d is None:
+            raise ValueError(f"{who}: bones = {bones!r}: (B,2) integers, or 'dataset' for the tree of a loop built for one of "
+                             f"{sorted(DATASETS)}")
+        bones = d["bones"]
+    bn = skeleton.checked_bones(bones, loop.P, who)
+    floor, iters, _ = skeleton._projection_settings(cov_floor, max_iters, 0.0, who)
+    if max_sigma_mm is not None:
+        if not use_covariance:
+            raise ValueError(f"{who}: max_sigma_mm gates a frame by the variance of its length, which needs use_covariance=True")
+        max_sigma_mm = skeleton._max_sigma(max_sigma_mm, True, who)
+    pairs = None
+    if symmetric:
+        if d is None:
+            raise ValueError(f"{who}: symmetric=True pairs the arm and leg `limbs` of scene.DATASETS, which has no {loop.dataset!r}")
+        try:
+            l_arm, r_arm, l_leg, r_leg = skeleton.bone_index(bn, d["limbs"])
+        except KeyError as e:
+            raise ValueError(f"{who}: symmetric=True needs the dataset's limb {e.args[0]} among the bones") from None
+        pairs = ((l_arm, r_arm), (l_leg, r_leg))
+    if use_covariance and not loop.keep_gaussians and loop._smooth is None:
+        raise ValueError(f"{who}: use_covariance=True takes every joint's covariance from the frame's optimised Gaussians, which "
+                         "this loop does not keep -- build it with FrameBatchLoop / FramePipeline(..., keep_gaussians=True), or "
+                         "pass use_covariance=False for the identity")
+    return dict(bones=bn, use_covariance=bool(use_covariance), cov_floor=floor, pairs=pairs, groups=groups,
+                max_sigma_mm=max_sigma_mm, max_iters=iters)
+
+
+def _sequence_bones(loop, N, who):
+    """optimize_sequence's bone-constraint settings with `groups` as an (N,) int32 tensor on the loop's device and `n_groups` from
+    the HOST ids (a device tensor of ids: one number is read back on the caller's stream); None for a loop whose constraint is
+    off (set_bone_constraint)."""
+    s = getattr(loop, "_bones", None)       # (a loop from before the switch has none)
+    if s is None:
+        return None
+    if s["use_covariance"] and not loop.keep_gaussians and loop._smooth is None:
+        raise ValueError(f"{who}: set_bone_constraint(use_covariance=True) needs the Gaussians this loop does not keep "
+                         "(keep_gaussians), or the smoothing's covariance (set_smoothing)")
+    s = dict(s, n_groups=1)
+    g = s["groups"]
+    if g is not None:
+        g = g if torch.is_tensor(g) else torch.as_tensor(np.asarray(g))
+        if g.dim() != 1 or g.shape[0] != N or g.is_floating_point() or g.dtype == torch.bool:
+            raise ValueError(f"{who}: the groups given to set_bone_constraint must be ({N},) integers, one per frame of this "
+                             f"sequence, got {tuple(g.shape)} {g.dtype}")
+        s["n_groups"] = int(g.max()) + 1
+        s["groups"] = g.to(device=loop.device, dtype=torch.int32)
+    return s
+
+
 def _sequence_consensus(loop, reject, N):
     """optimize_sequence's (inliers (N,V,J) bool, n_consensus (N,J) int32) on the device, None without rejection."""
     if reject is None:
@@ -316,7 +375,7 @@ class JointSwitches:
 
 class SequenceSwitches(JointSwitches):
     """JointSwitches plus what an `optimize_sequence` of a FrameBatchLoop or a FramePipeline keeps: the settings live on the loops
-    as `_reproject`, `_smooth` and `_debug_frames`, the results arrive on the object that ran the sequence (SequenceRun.publish),
+    as `_reproject`, `_smooth`, `_bones` and `_debug_frames`, the results arrive on the object that ran the sequence (SequenceRun.publish),
     a pipeline's batches each on their own stream."""
 
     def set_reprojection_report(self, on=True):
@@ -340,6 +399,28 @@ class SequenceSwitches(JointSwitches):
         optimiser's steps and captured graphs.  What the covariance weights gain on real sequences depends on how well the
         optimised covariances are calibrated (uncertainty.calibration) and has not been measured."""
         return self._set("_smooth", _smoothing(self._driven()[0], half_window, degree, taper, use_covariance, cov_floor, groups))
+
+    def set_bone_constraint(self, bones=None, use_covariance=True, cov_floor=0.0, symmetric=False, groups=None, max_sigma_mm=None,
+                            max_iters=16):
+        """From now on every `optimize_sequence` holds the sequence to constant limb lengths once all batches are taken: three
+        launches on the caller's stream behind the smoothing, if that is on -- skeleton.bone_lengths (measure, then the medians
+        per recording) and skeleton.project_to_lengths onto those medians --, nothing is read back.  The results arrive as
+        `self.bone_lengths` (a skeleton.BoneLengths: length, mad, n_used per recording and bone, measured per frame; the lengths
+        the frames were projected onto are `length`, made symmetric when asked) and `self.constrained` (a skeleton.Projected:
+        joints, residual, n_trips, n_active); both None after a sequence without it.
+        `bones` (B,2) host integers (parent, child), or "dataset" for scene.DATASETS[...]["bones"]; None: off again.  With the
+        smoothing on, the SMOOTHED joints are constrained, under the fit's own cov6; otherwise the joints optimize_sequence
+        returns, under the covariance of each frame's kept Gaussians (one joint_uncertainty launch in front; loops built with
+        keep_gaussians=True, refused otherwise).  `use_covariance=False`: the identity, both ends of a wrong bone move alike.
+        `cov_floor` mm^2 is added to the covariances' diagonals, `max_sigma_mm` leaves a frame out of a bone's median when the
+        standard deviation of its length is larger, `symmetric=True` sets the dataset's left and right arm and leg `limbs` to
+        their mean before projecting, `groups` (N,) integers, host or device, are the recordings (checked against the next
+        sequence's length), `max_iters` 1 .. 16 trips per frame.  The joints `optimize_sequence` returns, `smoothed`, `gaussians`,
+        `report` and every other output are untouched, as are the optimiser's steps and captured graphs.  The result is A pose on
+        the lengths, reached by successive covariance-closest projections, not the closest one (skeleton.project_to_lengths);
+        what it gains on real sequences has not been measured."""
+        return self._set("_bones", _bone_constraint(self._driven()[0], bones, use_covariance, cov_floor, symmetric, groups,
+                                                    max_sigma_mm, max_iters))
 
     def set_view_weighting(self, mode, threshold=0.5):
         """From now on the optimiser step of every frame weights each view's xyz gradient per joint by its agreement with the
@@ -384,7 +465,8 @@ class SequenceRun:
       out, initial  (N,P,3) optimised joints; the initial joints, None unless `return_initial`
       inliers, n_consensus, report, gaussians, images, reprojection   what optimize_sequence documents under these names, None where the loop
                     has the feature off;  stopped_at: None, or the (N,) int64 zeros of a pipeline with early stopping
-      smoothing     None or set_smoothing's settings for this sequence; smoothed() makes the result once every batch is taken"""
+      smoothing     None or set_smoothing's settings for this sequence; smoothed() makes the result once every batch is taken
+      bones         None or set_bone_constraint's settings for this sequence; constrained(smoothed) makes the results behind it"""
 
     def __init__(self, loop, gt_next, points, poses_2d, poses_3d, rig_ids, return_initial, who="optimize_sequence"):
         self.pts, self.p2d, self.N = _sequence_inputs(points, poses_2d)
@@ -402,6 +484,7 @@ class SequenceRun:
         self.images = _sequence_images(loop, self.N)
         self.reprojection = _sequence_reprojection(loop, self.N)
         self.smoothing = _sequence_smoothing(loop, self.N, who)
+        self.bones = _sequence_bones(loop, self.N, who)
         # view agreement on: every frame's final weights (N,V,P), each batch's rows copied on its own stream (take)
         self.view_weights = (torch.zeros((self.N, loop.V, loop.P), dtype=torch.float32, device=loop.device)
                              if getattr(loop, "_vw_mode", 0) else None)
@@ -427,6 +510,26 @@ class SequenceRun:
         kw = dict(self.smoothing)
         cov6 = self.gaussians.uncertainty().cov6 if kw.pop("use_covariance") else None
         return smooth_sequence(self.out, cov6, **kw)
+
+    def constrained(self, smoothed):
+        """Behind smoothed(), on the caller's stream: (None, None) with the bone constraint off, else (skeleton.BoneLengths,
+        skeleton.Projected) of the smoothed joints under the fit's cov6 when `smoothed` is given, of `out` under the kept
+        Gaussians' covariance otherwise -- measure, lengths, project: three launches, behind one joint_uncertainty launch where
+        the Gaussians' covariance enters.  Reads its inputs, writes none of them."""
+        s = self.bones
+        if s is None:
+            return None, None
+        from . import skeleton
+        xyz = self.out if smoothed is None else smoothed.joints
+        cov6 = None
+        if s["use_covariance"]:
+            cov6 = self.gaussians.uncertainty().cov6 if smoothed is None else smoothed.cov6
+        lengths = skeleton.bone_lengths(xyz, s["bones"], cov6, groups=s["groups"], max_sigma_mm=s["max_sigma_mm"],
+                                        n_groups=s["n_groups"])
+        if s["pairs"] is not None:
+            lengths = lengths._replace(length=skeleton.symmetrize(lengths.length, s["pairs"]))
+        return lengths, skeleton.project_to_lengths(xyz, s["bones"], lengths.length, cov6, groups=s["groups"],
+                                                    cov_floor=s["cov_floor"], max_iters=s["max_iters"])
 
     def starts(self):
         return range(0, self.N, self.F)     # the first frame of every batch

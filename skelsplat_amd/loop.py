@@ -995,6 +995,8 @@ class FrameBatchLoop(_GroupLoop, SequenceSwitches):
         self.reprojection = None    # optimize_sequence's reprojection.SequenceReprojection of the last sequence
         self._smooth = None         # set_smoothing's settings
         self.smoothed = None        # optimize_sequence's smoothing.Smoothed of the last sequence
+        self._bones = None          # set_bone_constraint's settings
+        self.bone_lengths = self.constrained = None     # optimize_sequence's skeleton.BoneLengths / Projected of the last sequence
         # new_scenes(points=None) with rejection: the views each joint of the batch was triangulated from, the winners' counts
         self.inliers = torch.ones((F, V, self.P), dtype=torch.bool, device=dev)
         self.n_consensus = torch.zeros((F, self.P), dtype=torch.int32, device=dev)
@@ -1279,7 +1281,8 @@ class FrameBatchLoop(_GroupLoop, SequenceSwitches):
         `poses_3d` (N,V,J,3), with `points=None`: every batch's initial joints are fused from the views' 3D predictions
         instead (new_scenes); a device tensor is never copied to the host.
         What the switches add -- set_outlier_rejection (`self.seq_inliers`, `self.seq_n_consensus`), set_refinement,
-        set_reprojection_report (`self.reprojection`), set_smoothing (`self.smoothed`), set_debug_images (`self.images`) -- is said
+        set_reprojection_report (`self.reprojection`), set_smoothing (`self.smoothed`), set_bone_constraint (`self.bone_lengths`,
+        `self.constrained`), set_debug_images (`self.images`) -- is said
         there; each result is None after a sequence without its switch.
         A loop that reports: the return value is the same, and `self.report` (a report.SequenceReport) holds the loop's traces,
         final errors, snapshots and step counts for all N frames -- the errors against the (N,P,3) ground truth given to
@@ -1294,6 +1297,7 @@ class FrameBatchLoop(_GroupLoop, SequenceSwitches):
             self.run(iterations, groups_per_graph)      # (returns self.xyz, which take() copies)
             run.take(self, b)
         self.smoothed = run.smoothed()
+        self.bone_lengths, self.constrained = run.constrained(self.smoothed)
         self.check_rigs()
         return run.result()
 
@@ -1324,6 +1328,7 @@ class FramePipeline(SequenceSwitches):
         self.inliers = self.n_consensus = None     # optimize_sequence with rejection: (N,V,J) bool, (N,J) int32
         self.reprojection = None     # set_reprojection_report: reprojection.SequenceReprojection of the last optimize_sequence
         self.smoothed = None         # set_smoothing: smoothing.Smoothed of the last optimize_sequence
+        self.bone_lengths = self.constrained = None     # set_bone_constraint: skeleton.BoneLengths / Projected of the last one
         self.view_weights = None     # view weighting on: (N,V,P) final weights of the last optimize_sequence
 
     def _driven(self):
@@ -1358,6 +1363,7 @@ class FramePipeline(SequenceSwitches):
         for st in self.streams:
             cur.wait_stream(st)
         self.smoothed = run.smoothed()
+        self.bone_lengths, self.constrained = run.constrained(self.smoothed)
         self.check_rigs()
         return run.result()
 

@@ -125,23 +125,68 @@ _OP = [  # 0 pelvis 1-3 R leg 4-6 L leg 7 thorax 8 head 9-11 L arm 12-14 R arm
     (0, 0, 1400), (0, 0, 1650), (180, 0, 1400), (460, 0, 1400), (720, 0, 1400), (-180, 0, 1400),
     (-460, 0, 1400), (-720, 0, 1400)]
 
+def _tree(parents):
+    """A parent array (-1: the root) as (parent, child) pairs in child order."""
+    return tuple((p, j) for j, p in enumerate(parents) if p >= 0)
+
+
+# The skeleton trees over the joint orders stated at the templates, from the datasets' published orders: every joint but the root
+# hangs on its parent by one bone (skeleton.bone_lengths / project_to_lengths take them as `bones`).
+_H36M_PARENTS = [-1, 0, 1, 2, 0, 4, 5, 0, 7, 8, 9, 8, 11, 12, 8, 14, 15]                     # root: the pelvis
+_PANOPTIC_PARENTS = [2, 0, -1, 0, 3, 4, 2, 6, 7, 0, 9, 10, 2, 12, 13, 1, 15, 1, 17]          # root: the body centre
+_OP_PARENTS = [-1, 0, 1, 2, 0, 4, 5, 0, 7, 7, 9, 10, 7, 12, 13]                              # root: the pelvis
+
 DATASETS = {
     # name: (template, limb-end joints scaled by scaling_modifier (gaussian_model.py:173-178),
-    #        limb pairs of utils/loss_utils.py:226-250 as (l_arm, r_arm, l_leg, r_leg), W, H, rasterizer key)
+    #        limb pairs of utils/loss_utils.py:226-250 as (l_arm, r_arm, l_leg, r_leg), W, H, rasterizer key,
+    #        bones: the skeleton tree as (parent, child) pairs)
     "h36m": dict(template=_H36M, limb_ends=[3, 6, 12, 13, 15, 16],
                  limbs=((12, 13), (15, 16), (5, 6), (2, 3)), W=1000, H=1000, fx=1145.0, ring=5000.0,
-                 rendering="diff-gaussian-rasterization-h36m"),
+                 rendering="diff-gaussian-rasterization-h36m", bones=_tree(_H36M_PARENTS)),
     "panoptic": dict(template=_PANOPTIC, limb_ends=[8, 14, 4, 5, 10, 11],
                      limbs=((4, 5), (10, 11), (7, 8), (13, 14)), W=1920, H=1080, fx=1400.0, ring=3000.0,
-                     rendering="diff-gaussian-rasterization-panoptic"),
+                     rendering="diff-gaussian-rasterization-panoptic", bones=_tree(_PANOPTIC_PARENTS)),
     "occlusion-person": dict(template=_OP, limb_ends=[3, 6, 10, 11, 13, 14],
                              limbs=((10, 11), (13, 14), (5, 6), (2, 3)), W=1280, H=720, fx=1145.0, ring=5000.0,
-                             rendering="diff-gaussian-rasterization-op"),
+                             rendering="diff-gaussian-rasterization-op", bones=_tree(_OP_PARENTS)),
 }
 
 
 def skeleton_template(dataset):
     return np.asarray(DATASETS[dataset]["template"], dtype=np.float64)
+
+
+def articulated_motion(dataset, frames, pose=None, seed=2, swing=(0.1, 0.4), period=(25.0, 100.0), drift=(8.0, 3.0, 0.0)):
+    """(frames, J, 3) float64: a skeleton that keeps its bone lengths while it moves -- forward kinematics over the dataset's tree.
+    Every bone keeps the length it has in `pose` (default: the template) and its direction is the pose's, turned by a rotation
+    vector whose three components are sinusoids of `swing` radians amplitude and `period` frames; the root drifts by `drift` mm per
+    frame.  Bone lengths are constant up to the rounding of the float64 kinematics."""
+    d = DATASETS[dataset]
+    pose = skeleton_template(dataset) if pose is None else np.asarray(pose, dtype=np.float64)
+    bones = list(d["bones"])
+    children = {p: [] for p, _ in bones}
+    for p, c in bones:
+        children[p].append(c)
+    root = (set(p for p, _ in bones) - set(c for _, c in bones)).pop()
+    order, todo = [], [root]
+    while todo:                                     # parents before children
+        j = todo.pop(0)
+        for c in children.get(j, []):
+            order.append((j, c))
+            todo.append(c)
+    rng = np.random.default_rng(seed)
+    amp, per, phase = (rng.uniform(lo, hi, (len(order), 3)) for lo, hi in (swing, period, (0.0, 2.0 * np.pi)))
+    out = np.zeros((frames,) + pose.shape)
+    for f in range(frames):
+        out[f, root] = pose[root] + np.asarray(drift) * f
+        for i, (p, c) in enumerate(order):
+            w = amp[i] * np.sin(2.0 * np.pi * f / per[i] + phase[i])
+            th = np.linalg.norm(w)
+            k = w / th if th > 0 else w
+            K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+            R = np.eye(3) + np.sin(th) * K + (1.0 - np.cos(th)) * (K @ K)      # Rodrigues
+            out[f, c] = out[f, p] + R @ (pose[c] - pose[p])
+    return out
 
 
 def ring_cameras(V, W, H, radius, fx, rng, height=1500.0, target=(0.0, 0.0, 900.0), device="cpu"):
