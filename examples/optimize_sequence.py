@@ -5,7 +5,13 @@ iterations of the multi-view loop for every frame (loop.FramePipeline) -> MPJPE 
 python examples/optimize_sequence.py [--frames 64] [--per-launch 16] [--streams 2] [--iters 500] [--init host|device|fuse] [--rigs R]
     [--report] [--uncertainty] [--reject-px PX] [--corrupt K] [--refine [--huber-px D]] [--images DIR [--image-frames 0,31,63]]
     [--smooth H [--smooth-degree D]] [--motion wobble|smooth|articulated] [--view-weights scale|select [--view-threshold T]]
-    [--bones [--bones-symmetric]]
+    [--bones [--bones-symmetric]] [--people K [--assoc-px PX]]
+--people K [--assoc-px PX]: K synthetic skeletons on a grid walk through the views; every view's detector returns them in a slot
+order that is shuffled per frame.  The detections go to the device once and the front end runs there (skelsplat_amd/people.py):
+associate (pairs within PX pixels of mean epipolar distance, default 15) -> triangulate -> track -> to_tracks -> the pipeline of
+--init device over the K single-person sequences, smoothed per track through the `groups` to_tracks returns (--smooth H, default
+2).  Printed: how many frames were associated and tracked correctly against the known permutation, and the MPJPE of every track.
+The other switches do not apply.
 --view-weights scale|select [--view-threshold T]: the optimiser step of every frame weights each view's joint gradient by its
 agreement with the other views' (pipe.set_view_weighting; DESIGN.md "View agreement"; T: select's cosine threshold, default 0.5).
 With --report: each view's mean final weight, and with --corrupt the mean weight of the corrupted (view, joint) detections
@@ -76,6 +82,67 @@ from skelsplat_amd.loop import FramePipeline
 from skelsplat_amd.scene import GaussianModel, SyntheticScene, project_points
 
 
+def people_main(args):
+    """--people K: detections of K people in shuffled slots -> associate -> triangulate -> track -> to_tracks -> the pipeline."""
+    from skelsplat_amd import people
+    from skelsplat_amd.scene import articulated_motion
+    dev = torch.device("cuda:0")
+    K, N, V = args.people, args.frames, args.views
+    sc = SyntheticScene(args.dataset, n_views=V, seed=0, device=dev)
+    J = sc.n_joints
+    rng = np.random.default_rng(1)
+    side = int(np.ceil(np.sqrt(K)))
+    off = np.array([[((k % side) - (side - 1) / 2) * 1200.0, ((k // side) - (side - 1) / 2) * 1200.0, 0.0] for k in range(K)])
+    gt = np.stack([articulated_motion(args.dataset, N, seed=2 + k, drift=(4.0, 2.0, 0.0)) + off[k] for k in range(K)], axis=1)      # (N,K,J,3)
+    det = np.zeros((N, V, K, J, 2), dtype=np.float32)
+    perm = np.stack([[rng.permutation(K) for _ in range(V)] for _ in range(N)])       # perm[n, v, k]: the slot of person k
+    for n in range(N):
+        for v, cam in enumerate(sc.cameras):
+            for k in range(K):
+                det[n, v, perm[n, v, k]] = project_points(cam, gt[n, k]) + rng.normal(0, 3.0, (J, 2))
+    gm = GaussianModel().create_from_points(gt[0, 0].astype(np.float32), sc.spatial_lr_scale, J, scene_type=args.dataset, device=dev)
+    gm.training_setup()
+    pipe = FramePipeline(gm, sc.cameras, frames=args.per_launch, streams=args.streams, dataset=args.dataset, accumulation_steps=V)
+    det_dev = torch.as_tensor(det, device=dev)
+
+    def run():
+        a = people.associate(sc.cameras, det_dev, max_px=args.assoc_px, max_people=K)
+        p2d = a.poses_2d.reshape(N * K, V, J, 2)
+        joints = triangulation.triangulate_sequence(sc.cameras, p2d, valid=people.kept(p2d)).reshape(N, K, J, 3)
+        t = people.track(joints, max_mm=300.0, max_gap=5, min_joints=5)
+        tracks, groups = people.to_tracks(t.track_id, a.poses_2d, K)
+        pipe.set_smoothing(2 if args.smooth is None else args.smooth, degree=args.smooth_degree, use_covariance=False, groups=groups)
+        out = pipe.optimize_sequence(None, tracks.reshape(K * N, V, J, 2), iterations=args.iters)
+        return a, t, out
+    run()                                                             # captures the hipGraphs
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    a, t, out = run()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    assign, tid = a.assign.cpu().numpy(), t.track_id.cpu().numpy()
+    # person p is row k of frame n when the row holds p's slot in every view
+    who = np.full((N, K), -1)
+    for n in range(N):
+        for k in range(K):
+            hit = np.nonzero((perm[n].T == assign[n, k]).all(axis=1))[0]
+            who[n, k] = hit[0] if len(hit) else -1
+    associated = int(sum(sorted(who[n]) == list(range(K)) for n in range(N)))
+    track_of = {int(who[0, k]): int(tid[0, k]) for k in range(K)}
+    tracked = int(sum(all(who[n, k] >= 0 and tid[n, k] == track_of[int(who[n, k])] for k in range(K)) for n in range(N)))
+    print(f"{args.dataset} V={V}: {K} people x {N} frames, slots shuffled per frame: {associated} / {N} frames associated correctly, "
+          f"{tracked} / {N} tracked correctly ({int(t.n_tracks[0])} tracks, {int(t.n_dropped[0])} dropped, "
+          f"{int(a.n_unassigned.sum())} detections unassigned); front end + {args.iters} iterations in {dt * 1e3:.1f} ms")
+    pred = out.reshape(K, N, J, 3).cpu().numpy()
+    smoothed = pipe.smoothed.joints.reshape(K, N, J, 3).cpu().numpy()
+    for p in range(K):
+        if p in track_of and 0 <= track_of[p] < K:
+            e = np.mean([io.mpjpe(pred[track_of[p], n], gt[n, p]) for n in range(N)])
+            es = np.mean([io.mpjpe(smoothed[track_of[p], n], gt[n, p]) for n in range(N)])
+            print(f"  person {p} = track {track_of[p]}: mean MPJPE {e:.2f} mm, smoothed within the track {es:.2f} mm")
+    return dict(associated=associated, tracked=tracked, frames=N, joints=out)
+
+
 def main(argv=None):
     """Runs the example; with --report returns what the report lines were printed from (device tensors), else None."""
     ap = argparse.ArgumentParser()
@@ -102,7 +169,13 @@ def main(argv=None):
     ap.add_argument("--bones-symmetric", action="store_true")
     ap.add_argument("--view-weights", choices=("scale", "select"), default=None)
     ap.add_argument("--view-threshold", type=float, default=None, metavar="T")
+    ap.add_argument("--people", type=int, default=None, metavar="K")
+    ap.add_argument("--assoc-px", type=float, default=15.0, metavar="PX")
     args = ap.parse_args(argv)
+    if args.people is not None:
+        if not 1 <= args.people <= 8:
+            ap.error("--people K: 1 .. 8 people a frame")
+        return people_main(args)
     dev = torch.device("cuda:0")
     sc = SyntheticScene(args.dataset, n_views=args.views, seed=0, device=dev)
     rigs = [sc.cameras] + [SyntheticScene(args.dataset, n_views=args.views, seed=r, device=dev).cameras for r in range(1, args.rigs)]

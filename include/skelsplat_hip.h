@@ -637,6 +637,83 @@ int sks_bone_project(int N, int J, int B, const int* bones /*HOST (B,2)*/, const
                      int max_iters, double tol_mm, float* out_xyz, float* residual, int* n_trips, int* n_active, void* stream);
 int sks_bones_launch(int N, int J, int B, int n_groups, int* out /*HOST SKS_BONES_LAUNCH_INTS*/);
 
+/* People (csrc/sks_people.hip; added to sks_version 14: the number did not move).  A 2D detector returns an unordered list of
+ * skeletons per image; every other pose entry point takes (N,V,J,2), one person whose detections are already matched across the
+ * views.  These two put several people in front of them: ASSOCIATION decides per frame which detections of different views show
+ * the same person, TRACKING decides over the frames which person of frame t is which person of frame t-1.  One launch each on
+ * `stream` (tracking: a memset in front of it), nothing synchronises, no global atomics, no floating-point atomics, no scratch.
+ * Device memory unless marked HOST.  All arithmetic below is IEEE float64 (inputs widened), one rounding per operation, no fused
+ * multiply-add, IEEE division and square root.
+ *
+ * sks_associate_people.  detections (N,V,M,J,2), pixel x, y of up to M candidate skeletons per view in arbitrary slot order, as
+ *   float (detections) or double (detections_f64), exactly one; valid optional (N,V,M,J) bytes, 0 = this joint of this candidate is
+ *   not KEPT (NULL: all kept); proj, rig_stride: as sks_triangulate takes them.  1 <= V <= SKS_MAX_VIEWS, 1 <= M <=
+ *   SKS_PEOPLE_MAX_SLOTS, D = V * M <= SKS_PEOPLE_MAX_DETS, 1 <= J <= SKS_MAX_CHANNELS, 1 <= K <= SKS_PEOPLE_MAX, max_px finite and
+ *   >= 0, 1 <= min_joints <= J, 2 <= min_views <= SKS_MAX_VIEWS; anything else is refused on the host.  Detection a = v * M + m.
+ *   FUNDAMENTAL MATRIX of views va < vb, from the two 3x4 matrices alone (Hartley & Zisserman 17.3; no pseudo-inverse, no SVD, no
+ *   square root).  For a view's matrix P and i = 0, 1, 2 let r0 < r1 be the two rows other than i and
+ *       m(P,i) = (m01, m02, m03, m12, m13, m23),  m_pq = r0[p] * r1[q] - r0[q] * r1[p].
+ *   With A = m(P_va, i) and B = m(P_vb, j), the 4x4 determinant of [P_va without row i; P_vb without row j] is expanded along its
+ *   first two rows in this order:
+ *       det = ((((A01 * B23 - A02 * B13) + A03 * B12) + A12 * B03) - A13 * B02) + A23 * B01,
+ *   and F[j][i] = det when i + j is even, -det when it is odd; x_b^T F x_a = 0 for the images of one point.
+ *   PAIR COST of a < b in different views (va < vb), over the joints j = 0 .. J-1 in ascending order.  Joint j is skipped unless
+ *   both detections are kept and their four coordinates (xa, ya), (xb, yb) are finite.  Then
+ *       l_k = (F[k][0] * xa + F[k][1] * ya) + F[k][2]  (k = 0, 1, 2),  db = |(l_0 * xb + l_1 * yb) + l_2| / sqrt(l_0 * l_0 + l_1 * l_1),
+ *       t_k = (F[0][k] * xb + F[1][k] * yb) + F[2][k],                 da = |(t_0 * xa + t_1 * ya) + t_2| / sqrt(t_0 * t_0 + t_1 * t_1),
+ *       d = 0.5 * (db + da);
+ *   a d that is not finite is skipped too; every other joint is COMMON: sum = sum + d, n = n + 1.  With n >= min_joints the pair is
+ *   MEASURED and c_ab = sum / n; otherwise it is unmeasured.  A measured pair with c_ab <= max_px is an EDGE, any other measured
+ *   pair a VETO.
+ *   CLUSTERING (constrained complete-link agglomeration).  Every detection starts as its own cluster.  The edges are taken in
+ *   ascending (c_ab, a, b); the clusters of a and b are merged unless they are the same cluster, or they share a view, or some
+ *   pair (one member of each) is a veto.  Unmeasured pairs never veto.  A cluster is labelled by its lowest member.
+ *   PEOPLE: the clusters with at least min_views members, by member count descending, then by label ascending.  The first K are
+ *   written, the rest are counted.  Outputs: assign (N,K,V) ints, the slot m of person k in view v or -1; n_people (N) = people
+ *   written, n_overflow (N) = people not written; n_unassigned (N) = detections with at least one joint that is kept and has
+ *   two finite coordinates, and that are in no written person; cost (N,K) doubles = the mean of the edges' c_ab over the pairs a < b
+ *   of the person's members, added in ascending (a, b) and divided by their number, NaN for an empty slot; and the gathered
+ *   detections (N,K,V,J,2) in the input's type (gathered resp. gathered_f64): the input's own bits where person k has a detection
+ *   in view v and the joint is kept, NaN elsewhere -- as (N*K,V,J,2) what sks_triangulate takes.  CONTRACT: a NaN or inf coordinate
+ *   drops its joint from every pair (it is copied by the gather); a frame without detections has no people and every slot empty;
+ *   a person seen in one view is no person and is counted in n_unassigned; of two near-identical detections in one view at most
+ *   one joins the person (the view rule), the other is unassigned.  A frame's outputs depend on its own inputs, V, M, J, K and the
+ *   three parameters only, never on N, on its place in the batch or on the stream.
+ *   One workgroup of 256 threads per frame; the pair costs are spread over the threads; the edge list is compacted and sorted
+ *   (bitonic, one sorter for every length, on (bits of c_ab, a, b)) in LDS; the merge walk is sequential over the edges, its three
+ *   tests run across the lanes of one wavefront over 128-bit member masks, 64-bit view masks and the D x D veto bit matrix.
+ * sks_track_people.  joints (N,K,J,3) floats, the triangulated people, an absent person all NaN; groups (N) ints, the recording of
+ *   every frame, with 1 <= n_groups <= SKS_PEOPLE_MAX_GROUPS, or NULL with n_groups = 1; 1 <= K <= SKS_PEOPLE_MAX, 1 <= J <=
+ *   SKS_MAX_CHANNELS, max_mm finite and >= 0, max_gap >= 0 frames, 1 <= min_joints <= J.  Each recording is tracked on its own, its
+ *   frames in ascending index order, with SKS_PEOPLE_MAX track slots, all free at first, and ids counted from 0.  A joint is FINITE
+ *   when its three floats are.  Per frame:  person k is PRESENT with at least min_joints finite joints.  The cost of (alive slot s,
+ *   present person k), with q the slot's last matched pose (the whole pose of the person it matched last), over the joints finite
+ *   in both, ascending:  d = x - q per coordinate (widened), sum = sum + sqrt((d_0 * d_0 + d_1 * d_1) + d_2 * d_2), n = n + 1;  with
+ *   n >= min_joints the cost is sum / n and the pair is a candidate when cost <= max_mm.  The candidates are matched greedily in
+ *   ascending (cost, s, k), one to one.  A matched slot takes the person's pose and age 0, the person the slot's id.  An unmatched
+ *   alive slot ages by one frame and is freed once its age exceeds max_gap -- before any track opens in the same frame.  Then the
+ *   unmatched present people open tracks in ascending k: each takes the lowest free slot and the next id of its recording; with no
+ *   free slot the person gets -1 and is counted.  Outputs: track_id (N,K) ints, -1 = absent or dropped (and every person of a frame
+ *   whose group id names no recording); n_tracks, n_dropped (n_groups) ints.  One wavefront per recording, lane = 8 s + k.
+ * sks_people_launch: HOST only, no GPU call: the threads and LDS bytes of the association's workgroup and the entries of its edge
+ *   list for V views of M slots, and the tracker's threads, at the SKS_PEOPLE_* indices below. */
+#define SKS_PEOPLE_MAX_DETS    128   /* detections a frame, V * M */
+#define SKS_PEOPLE_MAX_SLOTS   16    /* candidates a view, M */
+#define SKS_PEOPLE_MAX         8     /* people written a frame, K; track slots of a recording */
+#define SKS_PEOPLE_MAX_GROUPS  65535
+#define SKS_PEOPLE_ASSOC_THREADS       0
+#define SKS_PEOPLE_ASSOC_LDS_BYTES     1
+#define SKS_PEOPLE_ASSOC_LIST_ENTRIES  2
+#define SKS_PEOPLE_TRACK_THREADS       3
+#define SKS_PEOPLE_LAUNCH_INTS         4
+int sks_associate_people(int N, int V, int M, int J, int K, const double* proj, size_t rig_stride, const float* detections,
+                         const double* detections_f64, const unsigned char* valid, double max_px, int min_joints, int min_views,
+                         int* assign, int* n_people, int* n_overflow, int* n_unassigned, double* cost, float* gathered,
+                         double* gathered_f64, void* stream);
+int sks_track_people(int N, int K, int J, const float* joints, const int* groups, int n_groups, double max_mm, int max_gap,
+                     int min_joints, int* track_id, int* n_tracks, int* n_dropped, void* stream);
+int sks_people_launch(int V, int M, int* out /*HOST SKS_PEOPLE_LAUNCH_INTS*/);
+
 /* Replaces fusedssim (submodules/fused-ssim/ssim.cu:368-404, binding ext.cpp): img1, img2, ssim_map and the three
  * optional partial-derivative maps (train == true) are (B,CH,H,W) fp32; "same" zero padding. */
 int sks_fused_ssim_fwd(int B, int CH, int H, int W, float C1, float C2, const float* img1, const float* img2,

@@ -38,6 +38,11 @@ SKS_BONES_MAX_JOINTS = 32
 SKS_BONES_MAX_GROUPS = 256
 SKS_BONES_MAX_ITERS = 16
 SKS_BONES_LAUNCH_INTS = 8
+SKS_PEOPLE_MAX_DETS = 128
+SKS_PEOPLE_MAX_SLOTS = 16
+SKS_PEOPLE_MAX = 8
+SKS_PEOPLE_MAX_GROUPS = 65535
+SKS_PEOPLE_LAUNCH_INTS = 4
 SKS_ALIGN_RIGID, SKS_ALIGN_SIMILARITY, SKS_ALIGN_SCALE = 0, 1, 2
 SKS_PREVIEW_LAUNCH_INTS = 4
 SKS_HEATMAP_MAX_RADIUS = 1 << 18     # a truncation radius beyond it draws no impulse (sks_heatmap_factors, DESIGN.md "Degenerate footprints")
@@ -202,6 +207,10 @@ SIGNATURES = {
     "sks_bone_lengths": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "sks_bone_project": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, C.c_double, _i, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "sks_bones_launch": (_i, [_i, _i, _i, _i, _vp]),
+    "sks_associate_people": (_i, [_i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp]),
+    "sks_track_people": (_i, [_i, _i, _i, _vp, _vp, _i, C.c_double, _i, _i, _vp, _vp, _vp, _vp]),
+    "sks_people_launch": (_i, [_i, _i, _vp]),
     **{name: (_i, [ct for _, ct in params]) for name, params in {**STEP_PARAMS, **DV_PARAMS, **VW_STEP_PARAMS}.items()},
     "sks_pose_errors": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "sks_loop_report": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
@@ -345,6 +354,18 @@ def bones_launch(N, J, B, n_groups=1):
     out = (_i * SKS_BONES_LAUNCH_INTS)()
     check(load().sks_bones_launch(N, J, B, n_groups, C.cast(out, _vp)), "sks_bones_launch")
     return {name: out[i] for i, name in enumerate(BONES_LAUNCH_FIELDS)}
+
+
+# sks_people_launch's record: field name -> index (include/skelsplat_hip.h, SKS_PEOPLE_*)
+PEOPLE_LAUNCH_FIELDS = ("assoc_threads", "assoc_lds_bytes", "assoc_list_entries", "track_threads")
+
+
+def people_launch(V, M):
+    """The association's workgroup for V views of M candidate slots, as a dict over PEOPLE_LAUNCH_FIELDS: its threads, its LDS
+    bytes and the entries of its edge list; and the tracker's threads (host only: sks_people_launch)."""
+    out = (_i * SKS_PEOPLE_LAUNCH_INTS)()
+    check(load().sks_people_launch(V, M, C.cast(out, _vp)), "sks_people_launch")
+    return {name: out[i] for i, name in enumerate(PEOPLE_LAUNCH_FIELDS)}
 
 
 def prefill_planes(V, P, C_, W, H, flags=0):

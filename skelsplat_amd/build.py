@@ -15,7 +15,8 @@ LIB = os.path.join(HERE, "libskelsplat_hip.so")
 # source -> extra flags.  sks_ssim.hip: see its header (the SLP vectoriser's packing costs more moves than it saves)
 SOURCES = {"sks_raster.hip": [], "sks_ops.hip": [], "sks_ssim.hip": ["-fno-slp-vectorize"], "sks_loop.hip": [],
            "sks_triangulate.hip": [], "sks_keypoint.hip": [], "sks_fuse.hip": [], "sks_report.hip": [], "sks_uncertainty.hip": [],
-           "sks_align.hip": [], "sks_preview.hip": [], "sks_reproject.hip": [], "sks_smooth.hip": [], "sks_bones.hip": []}
+           "sks_align.hip": [], "sks_preview.hip": [], "sks_reproject.hip": [], "sks_smooth.hip": [], "sks_bones.hip": [],
+           "sks_people.hip": []}
 # -ffp-contract=off is part of the numeric contract (DESIGN.md "Numerics"): tile lists, n_contrib and the forward
 # image must not depend on the compiler's FMA-contraction choices.
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off",
